@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the KBNet inference hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step` = the
+milliseconds of one of those K steps).  `--dump-outputs DIR` writes what the timed path computed in its last step --
+the gathered depth maps -- to DIR/depth.npy (float32; a fixed seeded sample of whole frames if they exceed 64 MB); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.  Everything else below
+(the sustained run, the roofline pass, the side measurements, the N-rank report, the CPU baseline and the parity check
+against the oracle) runs only with `--full`; the `--no-*` switches select among them.
 
 Both forms work for any N: started WITHOUT torchrun's environment (no WORLD_SIZE) and with --gpus N > 1, the script
 re-launches itself as N ranks under `torch.distributed.run --standalone`-style arguments on 127.0.0.1 (`self_spawn`),
@@ -21,7 +28,7 @@ formulation, 2 * N * Hout * Wout * Cin * 9 * Cout) over their time and over the 
 its MFMAs run on; a split-operand kernel takes three fp16 products per fp32 product, so its ceiling is
 1/3 (`ceiling_frac`); `issued` carries the FLOPs of the MFMA instructions it really issues (padding that
 is issued included: the figure SQ_INSTS_MFMA x 32768 of the PMC collection gives);
-`config.sustained` repeats the timed region for >= 300 steps and >= 3 s (and replaces `value` when it is
+With --full: `config.sustained` repeats the timed region for >= 300 steps and >= 3 s (and replaces `value` when it is
 more than 3 % lower), `config.batch1` is the graph-replayed latency of one frame;
 `cpu_baseline` times the CPU oracle (the port of the reference, bit-identical to it) on
 this box's host cores over a bounded sample.
@@ -458,6 +465,24 @@ def base_result(fps, world, steps, warmup, ms_per_step):
             "pipe": "fp16x3-split", "data": "synthetic"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out, rank: int):
+    """--dump-outputs: rank 0 writes the gathered output of the last timed step as DIR/depth.npy (float32).  Above
+    DUMP_LIMIT_BYTES a fixed sample of whole frames is kept (Philox seed 0, in frame order), the same for every run with the same
+    arguments."""
+    import numpy as np
+    if rank != 0:
+        return
+    depth = out.detach().float().cpu().numpy()
+    if depth.nbytes > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // depth[0].nbytes
+        depth = depth[np.sort(np.random.Generator(np.random.Philox(0)).choice(depth.shape[0], keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "depth.npy"), depth)
+
+
 def emit(result, rank: int):
     """Rank 0 prints the ONE JSON line."""
     if rank == 0:
@@ -482,6 +507,11 @@ def main(argv=None, backend: str = "nccl", forward_factory=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames-per-gpu", type=int, default=FRAMES_PER_GPU)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the gathered depth maps of the last timed step to DIR/depth.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: sustained run, roofline pass, side measurements, N-rank report, "
+                         "CPU baseline and parity check (the --no-* switches below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-void", action="store_true", help="skip the VOID 480x640 side measurement")
     ap.add_argument("--no-side-batch", action="store_true", help="skip the batch-8 (configs[1]) side measurement")
@@ -527,8 +557,13 @@ def main(argv=None, backend: str = "nccl", forward_factory=None):
     if forward_factory is not None:   # test hook: the plumbing alone
         runner = kb.dist.ShardedRunner(forward_factory(rank, dev, frames), rank, world)
         elapsed, out, local_seconds = timed_steps(runner, frames, args.steps, args.warmup, dev, per_rank=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, rank)
         result = base_result(per * world * args.steps / elapsed, world, args.steps, args.warmup, 1e3 * elapsed / args.steps)
-        multi_gpu = multi_gpu_report(runner.forward_fn, frames, out, per, world, rank, dev, result["value"], local_seconds, args.steps, reps=3)
+        multi_gpu = None
+        if args.full:
+            multi_gpu = multi_gpu_report(runner.forward_fn, frames, out, per, world, rank, dev, result["value"], local_seconds, args.steps,
+                                         reps=3)
         result["config"] = {"workload": "stand-in forward (plumbing test)", "frames_per_gpu": per, "global_batch": per * world,
                             "multi_gpu": multi_gpu,
                             "gathered_frames": int(out.shape[0]), "rank_seeds": [1 + r for r in range(world)],
@@ -559,10 +594,30 @@ def main(argv=None, backend: str = "nccl", forward_factory=None):
 
     elapsed, out, local_seconds = timed_steps(runner, step_inputs, args.steps, args.warmup, dev, per_rank=True)
     out = out.clone()
-    # this rank's slice of the gathered tensor must be the bits its own forward produces (the gather reads the graph's output in place)
-    gather_ok = bool(torch.equal(out[rank * per:(rank + 1) * per], forward(*step_inputs)))
     if tuple(out.shape) != (per * world, 1, HEIGHT, WIDTH):
         raise SystemExit(f"gathered output has shape {tuple(out.shape)}, expected {(per * world, 1, HEIGHT, WIDTH)}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
+    if not args.full:
+        # the plain run: the headline of the K timed steps and nothing else
+        result = base_result(per * world * args.steps / elapsed, world, args.steps, args.warmup, 1e3 * elapsed / args.steps)
+        result["config"] = {"workload": f"KITTI 352x1216, batch {per}/GPU, fp32, full KBNet forward in HIP, random xavier weights",
+                            "frames_per_gpu": per, "global_batch": per * world, "height": HEIGHT, "width": WIDTH,
+                            "n_ranks_seen": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
+                            "collective_backend": backend, "gathered_frames": int(out.shape[0]),
+                            "launch": "eager" if args.eager else
+                                      f"HIP graph replay, {getattr(forward, 'branches', 1)} concurrent sub-batch branch(es)"
+                                      + (", one graph per branch on its own stream" if getattr(forward, "split_graphs", False) else ""),
+                            "value_source": f"{args.steps} timed steps"}
+        result["roofline"] = None
+        result["cpu_baseline"] = None
+        emit(result, rank)
+        if world > 1:
+            kb.dist.barrier()
+            torch.distributed.destroy_process_group()
+        return result
+    # this rank's slice of the gathered tensor must be the bits its own forward produces (the gather reads the graph's output in place)
+    gather_ok = bool(torch.equal(out[rank * per:(rank + 1) * per], forward(*step_inputs)))
 
     # Sustained rate: the SAME runner and graph for at least 300 more steps and at least 3 s (the part is power-capped: clocks settle
     # over seconds, and K = 50 steps is half a second).  Reported beside `value`; if it falls more than 3 % below, it REPLACES `value`.

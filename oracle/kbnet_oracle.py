@@ -12,12 +12,12 @@ measured as the product:
 
 Pinning (see DESIGN.md "Oracle"): the reference holds no tests or golden
 vectors for this path.  The oracle is pinned against the
-reference ITSELF: `tests/golden/gen_golden.py` imports `/root/reference/src`
-in the build container, runs it on seeded inputs and commits the input/output
-vectors under `tests/golden/*.npz`; `tests/test_oracle_golden.py` checks this
-file against those vectors bit-for-bit, and `tests/test_oracle_vs_reference.py`
-(skipped where `/root/reference` is absent) repeats the comparison at the full
-352x1216 / 480x640 sizes.
+reference ITSELF: `tests/golden/gen_golden.py` imports the reference's `src/`,
+runs it on seeded inputs and commits the input/output vectors under
+`tests/golden/*.npz`; `tests/test_oracle_golden.py` checks this file against
+those vectors bit-for-bit, and `tests/test_oracle_vs_reference.py` repeats the
+comparison at the full 352x1216 / 480x640 sizes against recorded digests of
+the reference's outputs (`tests/golden/fwd_full_size.npz`).
 
 Weights are passed as plain dicts keyed exactly like the reference's
 `state_dict()` (without the DataParallel `module.` prefix, which `strip_prefix`

@@ -26,6 +26,8 @@ Cases
              the reference then calls calibrated_backprojection4 twice (quirk Q3; levels 2 and 3 of equal width).
   ckpt_kitti_narrow.pth  written by the reference's KBNetModel.save_model (same weights as fwd_kitti): the
              `.pth` layout restore_model must read (module.-prefixed keys, three state_dicts, optimizer state).
+  fwd_full_size  KBNetModel.forward at the full KITTI / VOID sizes (--only-full-size): digests and a sample of the
+             outputs, see gen_full_size.
   io/*       input pipeline: small PNG / .npy files written by this script's own PNG writer
              (every scanline filter type, split IDAT, gray / RGB / RGBA / palette / 16-bit gray) and what the
              reference's data_utils.load_image, datasets.load_image_triplet / load_depth and
@@ -546,7 +548,56 @@ def gen_saved_depth():
     print("saved_depth: %d bytes, max sample %d" % (os.path.getsize(path), int(back.max() * 256)))
 
 
+# ------------------------------------------------------- full-size forwards (digests)
+# The cases of tests/test_oracle_vs_reference.py.  A full-size depth map (1.7 MB at 352x1216) is larger than a committed file may
+# be, so the fixture holds the SHA-256 of the reference's output bits, a seeded sample of its values for the failure message, and
+# the SHA-256 of the inputs and weights the synthetic module drew (a change there is reported as such, not as a mismatch).
+FULL_SIZE_CASES = (("kitti", (352, 1216), {}), ("void", (480, 640), {}),
+                   ("kitti", (352, 1216), {"deconv_type": "transpose", "activation_func": "elu"}),
+                   ("void", (480, 640), {"activation_func": "sigmoid"}))
+
+
+def full_size_key(preset, shape, options):
+    return "_".join([preset, "%dx%d" % shape] + [str(options[k]) for k in sorted(options)])
+
+
+def sha256_of(tensors):
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(np.ascontiguousarray(t.detach().cpu().numpy()).tobytes())
+    return h.hexdigest()
+
+
+def gen_full_size():
+    import dataclasses
+    flat = {}
+    for preset, shape, options in FULL_SIZE_CASES:
+        cfg = dataclasses.replace(kb.PRESETS[preset](), **options)
+        sds = kb.synthetic.make_state_dicts(cfg, seed=0, gain=kb.synthetic.PARITY_GAIN[preset] if options else 1.0)
+        model = build_reference_model(cfg)
+        load(model.sparse_to_dense_pool, sds[0])
+        load(model.encoder, sds[1])
+        load(model.decoder, sds[2])
+        model.eval()
+        frames = kb.synthetic.make_frames(1, *shape, preset, seed=1)
+        out = model.forward(*frames)
+        key = full_size_key(preset, shape, options)
+        idx = np.sort(np.random.Generator(np.random.Philox(7)).choice(out.numel(), 4096, replace=False))
+        flat[key + "::shape"] = np.array(out.shape)
+        flat[key + "::output_sha256"] = np.array(sha256_of([out]))
+        flat[key + "::inputs_sha256"] = np.array(sha256_of(list(frames) + [sd[k] for sd in sds for k in sorted(sd)]))
+        flat[key + "::sample_index"] = idx
+        flat[key + "::sample"] = out.numpy().reshape(-1)[idx]
+    path = os.path.join(HERE, "fwd_full_size.npz")
+    np.savez_compressed(path, **flat)
+    print(f"fwd_full_size: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 if __name__ == "__main__":
+    if "--only-full-size" in sys.argv:    # the full-size forwards of tests/test_oracle_vs_reference.py, as digests
+        gen_full_size()
+        sys.exit(0)
     if "--only-save-depth" in sys.argv:   # round 5: the writer of run_kbnet.py --save_outputs
         gen_saved_depth()
         sys.exit(0)

@@ -268,7 +268,7 @@ def _bench_worker(rank, world, port, outdir, q):
 
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        res = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--frames-per-gpu", "4"],
+        res = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--frames-per-gpu", "4", "--full"],
                          backend="gloo", forward_factory=factory)
     lines = [ln for ln in buf.getvalue().splitlines() if ln.strip()]
     ok = seen["rank"] == rank and seen["dev"].type == "cpu"
@@ -325,7 +325,7 @@ def test_bench_plain_python_launch_spawns_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["KBN_BENCH_TEST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--frames-per-gpu", "4"], env=env, capture_output=True, text=True, timeout=240)
+                        "--frames-per-gpu", "4", "--full"], env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -339,6 +339,63 @@ def test_bench_plain_python_launch_spawns_its_ranks():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "0", "--warmup", "0",
                           "--frames-per-gpu", "2"], env=env, capture_output=True, text=True, timeout=240)
     assert bad.returncode != 0
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_output(tmp_path, monkeypatch):
+    """Without --full a run is the headline alone: W + K forwards and nothing after them, the contract's keys, no side report.
+    --dump-outputs writes the gathered output of the last timed step as float32, the same values in two runs with the same
+    arguments (seeded inputs)."""
+    import contextlib
+    import io
+    import json
+    import numpy as np
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "KBN_BENCH_TEST_BACKEND"):
+        monkeypatch.delenv(k, raising=False)
+    bench = _load_bench()
+    bench.HEIGHT, bench.WIDTH = 16, 24
+    calls = []
+
+    def counting_forward(*frames):
+        calls.append(frames[0].shape[0])
+        return _fake_forward(*frames)
+
+    lines = []
+    for run in range(2):
+        calls.clear()
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main(["--gpus", "1", "--steps", "5", "--warmup", "2", "--frames-per-gpu", "3", "--dump-outputs", str(tmp_path / str(run))],
+                       backend="gloo", forward_factory=lambda *a: counting_forward)
+        assert calls == [3] * (2 + 5)
+        printed = [ln for ln in buf.getvalue().splitlines() if ln.strip()]
+        assert len(printed) == 1
+        lines.append(json.loads(printed[0]))
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["dtype"] == "f32" and line["unit"] == "frames/s"
+    assert abs(line["value"] - 3 * 5 / (line["ms_per_step"] * 5e-3)) < 1e-2 * line["value"]
+    assert line["config"]["multi_gpu"] is None and line["roofline"] is None and line["cpu_baseline"] is None
+    first, second = (np.load(tmp_path / str(run) / "depth.npy") for run in range(2))
+    assert first.dtype == np.float32 and first.shape == (3, 1, 16, 24)
+    expect = _fake_forward(*kb.synthetic.make_frames(3, 16, 24, "kitti", seed=1)).numpy()
+    assert np.array_equal(first, expect) and np.array_equal(second, first)
+
+
+def test_bench_dump_keeps_a_fixed_sample_of_frames_above_the_limit(tmp_path, monkeypatch):
+    """An output larger than the dump limit is cut to a seeded sample of whole frames, in frame order, the same every time."""
+    import numpy as np
+    bench = _load_bench()
+    out = torch.arange(10 * 2 * 3, dtype=torch.float32).view(10, 1, 2, 3)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * out[0].numel() * 4 + 5)
+    bench.dump_outputs(str(tmp_path / "a"), out, 0)
+    bench.dump_outputs(str(tmp_path / "b"), out, 0)
+    bench.dump_outputs(str(tmp_path / "c"), out, 1)       # only rank 0 writes
+    a, b = np.load(tmp_path / "a" / "depth.npy"), np.load(tmp_path / "b" / "depth.npy")
+    assert a.shape == (4, 1, 2, 3) and a.dtype == np.float32 and np.array_equal(a, b)
+    rows = [int(f[0, 0, 0]) // 6 for f in a]
+    assert rows == sorted(set(rows)) and all(np.array_equal(f, out[r].numpy()) for f, r in zip(a, rows))
+    assert not (tmp_path / "c").exists()
 
 
 class _FakeEvent:

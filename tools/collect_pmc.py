@@ -26,7 +26,7 @@ PASSES = {"FETCH_SIZE": ["FETCH_SIZE"], "WRITE_SIZE": ["WRITE_SIZE"],
 res = collections.defaultdict(lambda: collections.defaultdict(float))
 for tag, counters in PASSES.items():
     subprocess.run(["rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", tmp, "-o", tag, "--",
-                    sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--eager",
+                    sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--eager",
                     "--no-cpu-baseline", "--no-void", "--no-side-batch", "--frames-per-gpu", str(frames)], cwd="/tmp", env=env, check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, stdin=subprocess.DEVNULL)
     f = glob.glob(os.path.join(tmp, "**", tag + "_counter_collection.csv"), recursive=True)[0]
@@ -56,7 +56,7 @@ for name, e in res.items():
     final[name] = row
 json.dump({"note": "rocprofv3 --pmc, three separate passes (FETCH_SIZE x2 on gfx950 | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES "
                    "SQ_INSTS_MFMA GRBM_GUI_ACTIVE), averaged over the whole-batch launches of "
-                   f"bench.py --eager --steps 2 --warmup 1 --no-void --frames-per-gpu {frames} with the tuner's choices replayed; "
+                   f"bench.py --full --eager --steps 2 --warmup 1 --no-void --frames-per-gpu {frames} with the tuner's choices replayed; "
                    "mfma_busy_frac = MFMA busy cycles / (GUI_ACTIVE per XCD x 1024 SIMDs)",
            "frames_per_gpu": frames, "kernels": final}, open(out_json, "w"), indent=1)
 print(json.dumps({k: [round(v["hbm_bytes_per_launch"] / 1e6, 1), round(v.get("mfma_busy_frac", 0), 3)] for k, v in final.items()}, indent=1))

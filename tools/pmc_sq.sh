@@ -8,7 +8,7 @@ cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/pmc_sq
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS"; do
   tag=$(echo $set | cut -d' ' -f1)
-  timeout 600 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_sq/$tag -o p -- python $R/bench.py --steps 2 --warmup 1 --eager --no-cpu-baseline --no-void --no-side-batch < /dev/null > /tmp/pmc_sq_$tag.log 2>&1 || tail -5 /tmp/pmc_sq_$tag.log
+  timeout 600 rocprofv3 --pmc $set --output-format csv -d $TMPDIR/pmc_sq/$tag -o p -- python $R/bench.py --full --steps 2 --warmup 1 --eager --no-cpu-baseline --no-void --no-side-batch < /dev/null > $TMPDIR/pmc_sq_$tag.log 2>&1 || tail -5 $TMPDIR/pmc_sq_$tag.log
 done
 python - "$OUT" <<'PY'
 import csv, glob, collections, re, sys

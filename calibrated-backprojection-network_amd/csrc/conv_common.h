@@ -143,11 +143,11 @@ __device__ __forceinline__ void store_tile_dst(const StoreDst& p, const f32x4 (&
             float* o = outn + (long long)oc * HWo + (long long)oy * p.outW + ox;
             if (vec_ok && ox + 3 < p.outW) {
                 *reinterpret_cast<f32x4*>(o) = v;
-                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                amax = fmaxf(fmaxf(amax, fmaxf(fin_abs(v[0]), fin_abs(v[1]))), fmaxf(fin_abs(v[2]), fin_abs(v[3])));
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (ox + r < p.outW) { o[r] = v[r]; amax = fmaxf(amax, fabsf(v[r])); }
+                    if (ox + r < p.outW) { o[r] = v[r]; amax = fmaxf(amax, fin_abs(v[r])); }
             }
         }
     }
@@ -197,11 +197,11 @@ __device__ __forceinline__ void store_tile_lds(const StoreDst& p, const f32x4 (&
             float* o = outn + (long long)oc * HWo + (long long)oy * p.outW + ox;
             if (vec_ok && ox + 3 < p.outW) {
                 *reinterpret_cast<f32x4*>(o) = v;
-                amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                amax = fmaxf(fmaxf(amax, fmaxf(fin_abs(v[0]), fin_abs(v[1]))), fmaxf(fin_abs(v[2]), fin_abs(v[3])));
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (ox + r < p.outW) { o[r] = v[r]; amax = fmaxf(amax, fabsf(v[r])); }
+                    if (ox + r < p.outW) { o[r] = v[r]; amax = fmaxf(amax, fin_abs(v[r])); }
             }
         }
     }

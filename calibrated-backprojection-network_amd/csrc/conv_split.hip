@@ -154,7 +154,7 @@ __device__ __forceinline__ void sp_act_scale(const SplitConvParams& p, int n, fl
     }
 }
 __device__ __forceinline__ float sp_amax4(float m, const f32x4& v) {
-    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    return fmaxf(fmaxf(m, fmaxf(fin_abs(v[0]), fin_abs(v[1]))), fmaxf(fin_abs(v[2]), fin_abs(v[3])));
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -323,9 +323,9 @@ __global__ __launch_bounds__(256) void absmax_frames_kernel(const float* __restr
             m = sp_amax4(sp_amax4(sp_amax4(sp_amax4(m, a), b), c), d);
         }
         for (; i < n4; i += stride) m = sp_amax4(m, x4[i]);
-        for (long long t = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; t < per_frame; t += stride) m = fmaxf(m, fabsf(xn[t]));
+        for (long long t = (n4 << 2) + (long long)blockIdx.x * 256 + threadIdx.x; t < per_frame; t += stride) m = fmaxf(m, fin_abs(xn[t]));
     } else {
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_frame; i += stride) m = fmaxf(m, fabsf(xn[i]));
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_frame; i += stride) m = fmaxf(m, fin_abs(xn[i]));
     }
     absmax_commit(slots + blockIdx.y, m);
 }
@@ -1325,7 +1325,7 @@ __global__ __launch_bounds__(SP_THREADS, 1) void conv1x1s2_split_kernel(const Sp
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (X + j < W) { o[8 * q4 + j] = v[j]; amax = fmaxf(amax, fabsf(v[j])); }
+                        if (X + j < W) { o[8 * q4 + j] = v[j]; amax = fmaxf(amax, fin_abs(v[j])); }
                 }
             }
         }
@@ -1390,7 +1390,7 @@ __global__ __launch_bounds__(256) void ksplit_reduce_kernel(const float* __restr
                 for (int k = 1; k < ksplit; ++k) a += src[(long long)k * ks_stride];
                 a = a > 0.f ? a : a * slope;
                 out[(long long)n * out_bstride + i] = a;
-                m = fmaxf(m, fabsf(a));
+                m = fmaxf(m, fin_abs(a));
             }
         }
     }

@@ -500,7 +500,7 @@
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
-                        if (X + j < W) { o[8 * q4 + j] = v[j]; amax = fmaxf(amax, fabsf(v[j])); }
+                        if (X + j < W) { o[8 * q4 + j] = v[j]; amax = fmaxf(amax, fin_abs(v[j])); }
                 }
             }
         }

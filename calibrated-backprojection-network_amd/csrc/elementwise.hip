@@ -30,18 +30,18 @@ __global__ __launch_bounds__(256) void activation_kernel(float* __restrict__ x, 
             float4 v = reinterpret_cast<float4*>(xn)[i];
             v.x = act_apply<KIND>(v.x); v.y = act_apply<KIND>(v.y); v.z = act_apply<KIND>(v.z); v.w = act_apply<KIND>(v.w);
             reinterpret_cast<float4*>(xn)[i] = v;
-            m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            m = fmaxf(fmaxf(m, fmaxf(fin_abs(v.x), fin_abs(v.y))), fmaxf(fin_abs(v.z), fin_abs(v.w)));
         }
         for (long long i = (quads << 2) + (long long)blockIdx.x * 256 + threadIdx.x; i < per_frame; i += step) {
             const float v = act_apply<KIND>(xn[i]);
             xn[i] = v;
-            m = fmaxf(m, fabsf(v));
+            m = fmaxf(m, fin_abs(v));
         }
     } else {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_frame; i += step) {
             const float v = act_apply<KIND>(xn[i]);
             xn[i] = v;
-            m = fmaxf(m, fabsf(v));
+            m = fmaxf(m, fin_abs(v));
         }
     }
     if (out_absmax) absmax_commit(out_absmax + blockIdx.y, m);

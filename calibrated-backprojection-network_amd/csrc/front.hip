@@ -120,7 +120,7 @@ __global__ __launch_bounds__(FR_THREADS, NEXT ? 4 : 2) void kb1_front_kernel(con
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 raw[u][j] = (ok && j < p.Cin) ? src[(long long)(j < p.Cin ? j : 0) * plane] : 0.f;
-                tm = fmaxf(tm, fabsf(raw[u][j]));
+                tm = fmaxf(tm, fin_abs(raw[u][j]));
             }
         }
         tm = __uint_as_float(wave_max_bits(tm));
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(FR_THREADS, NEXT ? 4 : 2) void kb1_front_kernel(con
                 mI[nb] = vI; mF[nb] = vF;
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (p.vec4 || Xo + r < p.w) { amI = fmaxf(amI, fabsf(vI[r])); amF = fmaxf(amF, fabsf(vF[r])); }
+                    if (p.vec4 || Xo + r < p.w) { amI = fmaxf(amI, fin_abs(vI[r])); amF = fmaxf(amF, fin_abs(vF[r])); }
                 continue;
             }
             float* oi = p.out_image + (long long)n * p.out_image_bstride + f * oplane + pix;
@@ -359,13 +359,13 @@ __global__ __launch_bounds__(FR_THREADS, NEXT ? 4 : 2) void kb1_front_kernel(con
                 *reinterpret_cast<ff4*>(oi) = vI;
                 *reinterpret_cast<ff4*>(of) = vF;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { amI = fmaxf(amI, fabsf(vI[r])); amF = fmaxf(amF, fabsf(vF[r])); }
+                for (int r = 0; r < 4; ++r) { amI = fmaxf(amI, fin_abs(vI[r])); amF = fmaxf(amF, fin_abs(vF[r])); }
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (Xo + r < p.w) {
                         oi[r] = vI[r]; of[r] = vF[r];
-                        amI = fmaxf(amI, fabsf(vI[r])); amF = fmaxf(amF, fabsf(vF[r]));
+                        amI = fmaxf(amI, fin_abs(vI[r])); amF = fmaxf(amF, fin_abs(vF[r]));
                     }
             }
         }
@@ -410,7 +410,7 @@ __global__ __launch_bounds__(FR_THREADS, NEXT ? 4 : 2) void kb1_front_kernel(con
         if (even_row) {
 #pragma unroll
             for (int nb = 0; nb < NBI; ++nb)
-                tm = fmaxf(fmaxf(tm, fmaxf(fabsf(eI[nb][0]), fabsf(eI[nb][1]))), fmaxf(fabsf(eF[nb][0]), fabsf(eF[nb][1])));
+                tm = fmaxf(fmaxf(tm, fmaxf(fin_abs(eI[nb][0]), fin_abs(eI[nb][1]))), fmaxf(fin_abs(eF[nb][0]), fin_abs(eF[nb][1])));
         }
         {
             const unsigned tb = wave_max_bits(tm);
@@ -506,11 +506,11 @@ __global__ __launch_bounds__(FR_THREADS, NEXT ? 4 : 2) void kb1_front_kernel(con
                     if (p.vec4_2) {
                         *reinterpret_cast<ff4*>(op) = v;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) am2 = fmaxf(am2, fabsf(v[r]));
+                        for (int r = 0; r < 4; ++r) am2 = fmaxf(am2, fin_abs(v[r]));
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            if (X2 + r < p.w2) { op[r] = v[r]; am2 = fmaxf(am2, fabsf(v[r])); }
+                            if (X2 + r < p.w2) { op[r] = v[r]; am2 = fmaxf(am2, fin_abs(v[r])); }
                     }
                 }
             }
@@ -634,7 +634,7 @@ __global__ __launch_bounds__(FR_THREADS, 2) void kb1_depth_front_kernel(const De
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 raw[u][j] = (ok && j < p.Cin) ? src[(long long)(j < p.Cin ? j : 0) * plane] : 0.f;
-                tm = fmaxf(tm, fabsf(raw[u][j]));
+                tm = fmaxf(tm, fin_abs(raw[u][j]));
             }
         }
         tm = __uint_as_float(wave_max_bits(tm));
@@ -835,7 +835,7 @@ __global__ __launch_bounds__(FR_THREADS, 2) void kb1_depth_front_kernel(const De
         } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (Xo + r < p.w) { o[r] = v[r]; am = fmaxf(am, fabsf(v[r])); }
+                if (Xo + r < p.w) { o[r] = v[r]; am = fmaxf(am, fin_abs(v[r])); }
         }
     }
     if (p.amax_out_depth) absmax_commit(p.amax_out_depth + n, am);

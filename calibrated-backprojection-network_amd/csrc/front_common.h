@@ -42,7 +42,7 @@ __device__ __forceinline__ _Float16 fr_term(float ws, int term) {
 }
 
 __device__ __forceinline__ float sp_amax4f(float m, const ff4& v) {
-    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    return fmaxf(fmaxf(m, fmaxf(fin_abs(v[0]), fin_abs(v[1]))), fmaxf(fin_abs(v[2]), fin_abs(v[3])));
 }
 
 // two-term split of four scaled values: h1 = fp16(v), h2 = fp16((v - h1) 2^11)

@@ -23,6 +23,8 @@ __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; 
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
 __device__ __forceinline__ float leaky_relu(float v, float slope) { return v > 0.f ? v : v * slope; }
+// |v| for the running maxima behind the fp16 windows (absmax slots, per-tile maxima): 0 for Inf and NaN
+__device__ __forceinline__ float fin_abs(float v) { const float a = fabsf(v); return a < __builtin_inff() ? a : 0.f; }
 
 // ---- per-frame activation statistics ("absmax slots") ------------------------------------------------
 // A slot is one unsigned per frame: the bit pattern of max |a| over a tensor's frame (bit patterns of non-negative
@@ -30,7 +32,9 @@ __device__ __forceinline__ float leaky_relu(float v, float slope) { return v > 0
 // slot of its output tensor (out_absmax) in its epilogue; the split-operand kernels read the slots of their inputs
 // (kbn_conv_src.absmax) and place their fp16 window on them (sp_act_scale, conv_split.hip) -- the exponent follows the
 // data of THIS forward, frame by frame, with no host round trip and no state between calls.
-// `m` >= 0: this thread's maximum (NaNs never enter: fmaxf drops them).  One atomic per wave, and only when the wave
+// `m` >= 0: this thread's maximum over the FINITE values (fin_abs: an Inf or NaN counts as 0).  A window placed on an Inf maximum
+// would be 2^-100 and flush every finite value of the frame to zero; the non-finite values themselves still propagate through
+// the convs (a split of Inf is Inf / NaN), as in the reference.  One atomic per wave, and only when the wave
 // would raise the slot (the plain load may be stale -- then the atomic is merely redundant).
 // Bit pattern of the maximum of a NON-NEGATIVE float over the wave, wave-uniform (an SGPR).  DPP butterflies inside each row of 16
 // lanes (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: max is idempotent, any covering pattern does), then the four rows

@@ -104,7 +104,7 @@ __device__ __forceinline__ void s2d_stage_run(const S2DStageParams& sp, unsigned
             const int X = XF + 4 * q + j;
             const bool ok = item && Y >= 0 && Y < H && X >= 0 && X < W;
             vr[j] = ok ? xz[plane + (long long)Y * W + X] : 0.f;
-            tm = fmaxf(tm, fabsf(vr[j]));
+            tm = fmaxf(tm, fin_abs(vr[j]));
         }
         constexpr int MAXE = (ZH * ZW + FR_THREADS - 1) / FR_THREADS;
         const bool z_inside = YZ >= 0 && YZ + ZH <= H && XZ >= 0 && XZ + ZW <= W;   // block-uniform
@@ -123,7 +123,7 @@ __device__ __forceinline__ void s2d_stage_run(const S2DStageParams& sp, unsigned
             if (e < ZH * ZW) {
                 zmax[e] = vz[u];                                                                  // -inf outside the image
                 zmin[e] = (vz[u] == 0.f) ? 999.f : ((vz[u] == -INFINITY) ? INFINITY : vz[u]);   // where(z == 0, 999, z)
-                if (vz[u] != -INFINITY) tm = fmaxf(tm, fabsf(vz[u]));
+                if (vz[u] != -INFINITY) tm = fmaxf(tm, fin_abs(vz[u]));
             }
         }
         tm = __uint_as_float(wave_max_bits(tm));

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(TL_THREADS, 2) void conv_tail_kernel(const TailPara
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 raw[u][j] = (ok && j < C) ? src[(long long)(j < C ? j : 0) * plane] : 0.f;
-                tm = fmaxf(tm, fabsf(raw[u][j]));
+                tm = fmaxf(tm, fin_abs(raw[u][j]));
             }
         }
         tm = __uint_as_float(wave_max_bits(tm));

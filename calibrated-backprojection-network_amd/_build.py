@@ -16,11 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkbnet_hip.so")
 OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
-# longest translation units first (conv_split.hip alone takes 100-110 s): the pool then ends with the short ones
-SOURCES = ["conv_split.hip", "conv_igemm.hip", "conv_dma_t1.hip", "conv_dma_t2.hip", "conv_dma_t4.hip", "conv_up2x.hip", "front.hip", "kb_pair_nb3.hip",
-           "kb_pair_nb4.hip", "conv_wino.hip", "s2d.hip", "kb_pair.hip", "head.hip", "tail.hip", "kb.hip", "conv_dma.hip", "tune.hip", "abi.hip", "pre_eval.hip",
-           "unpack.hip", "io_png.hip", "elementwise.hip"]
-HEADERS = ["kbn_common.h", "conv_common.h", "conv_dma_impl.h", "kb_pair_impl.h", "front_common.h", "s2d_pools.h", "s2d_stage.h", "conv_split_body.inc", "upconv64_split_body.inc", os.path.join("..", "..", "include", "kbnet_hip.h")]
+# longest translation units first: the pool then ends with the short ones
+SOURCES = ["conv_igemm.hip", "conv_dma_t1.hip", "conv_dma_t2.hip", "conv_dma_t4.hip", "conv_split.hip", "upconv_split.hip", "conv_up2x.hip", "front.hip",
+           "kb_pair_nb3.hip", "conv_wino.hip", "s2d.hip", "kb_pair_nb4.hip", "conv1x1s2_split.hip", "kb_pair.hip", "head.hip", "tail.hip", "kb.hip", "conv_dma.hip",
+           "tune.hip", "abi.hip", "pre_eval.hip", "unpack.hip", "io_png.hip", "elementwise.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
          "-Wno-unused-function"]
 
@@ -39,21 +38,33 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _depfile_deps(depfile: str):
+    """The prerequisites hipcc -MMD wrote for one object (the source and every header it included), or None when the
+    depfile is missing or unreadable."""
+    try:
+        with open(depfile) as f:
+            text = f.read().replace("\\\n", " ")
+        deps = text.split(":", 1)[1].split()
+    except (OSError, IndexError):
+        return None
+    return deps if deps and all(os.path.exists(d) for d in deps) else None
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     extra = os.environ.get("KBN_HIPCC_FLAGS", "").split()  # experiments, e.g. -DKBN_WAVES_PER_SIMD=3
     if extra:
         force = True
     os.makedirs(OBJ_DIR, exist_ok=True)
-    hdrs = [os.path.normpath(os.path.join(CSRC, h)) for h in HEADERS]
     jobs = []
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + hdrs):
-            jobs.append([hipcc] + FLAGS + extra + ["-c", s, "-o", o])
+        deps = _depfile_deps(o + ".d")   # written by the compiler with the object: the source and every header it read
+        if force or deps is None or _stale(o, [s] + deps):
+            jobs.append([hipcc] + FLAGS + extra + ["-MMD", "-MF", o + ".d", "-c", s, "-o", o])
 
     def run(cmd):
         if verbose:

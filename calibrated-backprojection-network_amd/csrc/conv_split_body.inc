@@ -3,7 +3,7 @@
     static_assert(APART, "the two small terms share the scale 2^11 and an accumulator of their own");
     static_assert(!(PIN0 || POUT) || (MODE == 0 && BLDS) || (MODE == 2 && !BLDS), "pair tensors: the concat kernel and the stride-2 kernel");
     using G = SpGeom<MODE>;
-    constexpr bool UP = G::UP, S2 = G::S2;
+    constexpr bool S2 = G::S2;
     constexpr int NB = NBW, FG = 8 / RG;
     constexpr int NT = 32 * NB * FG, NPIX = G::NPIX, PR = G::PR, COLS = TP ? 18 : G::COLS;
     static_assert(!TP || NPIX == 34 * 18, "the transposed region has the staged tile's size");
@@ -63,7 +63,7 @@
     for (int u = 0; u < PR; ++u) {
         const int pix = u * 256 + t256;
         const int r = pix / COLS, c = pix - r * COLS;
-        const int Y = (UP ? (oy0 >> 1) : (S2 ? 2 * oy0 : oy0)) - 1 + r, X = (UP ? (ox0 >> 1) : (S2 ? 2 * ox0 : ox0)) - 1 + c;
+        const int Y = (S2 ? 2 * oy0 : oy0) - 1 + r, X = (S2 ? 2 * ox0 : ox0) - 1 + c;
         goff[u] = (pix < NPIX && Y >= 0 && Y < sH && X >= 0 && X < sW) ? (Y * sW + X) * 4 : -1;
         slot[u] = S2 ? r * COLS + ((c & 1) ? (COLS + 1) / 2 + (c >> 1) : (c >> 1)) : pix;
     }
@@ -125,21 +125,20 @@
 
     // A fragments are fetched one GROUP (GM m-blocks) ahead of the MFMAs that use them, ping-pong registers;
     // sched_barriers pin that order.  Fragment of (row MB rg + mb, pixel lm, tap (ky, kx)): staged pixel
-    // (MB rg + mb + ky, lm + kx); up-conv: the low-resolution pixel ((MB rg + mb + ky + 1) >> 1, (lm + kx + 1) >> 1);
-    // stride 2: (2 (MB rg + mb) + ky, 2 lm + kx) = slot lm (kx 0), 33 + lm (kx 1), lm + 1 (kx 2) of the de-interleaved row.
+    // (MB rg + mb + ky, lm + kx); stride 2: (2 (MB rg + mb) + ky, 2 lm + kx) = slot lm (kx 0), 33 + lm (kx 1), lm + 1 (kx 2)
+    // of the de-interleaved row.
     constexpr int GM = 1, GPT = MB / GM, NGROUP = 9 * GPT;
     const unsigned char* aptr[3];
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx)
         aptr[kx] = TP ? smem + (g * NPIX + (2 * MB * rg + (lm >> 4)) * COLS + (lm & 15) + kx) * 16   // block = rows 2 b, 2 b + 1 x 16 columns
-                      : smem + (g * NPIX + (UP ? MB / 2 : (S2 ? 2 * MB : MB)) * rg * COLS +
-                                (UP ? ((lm + kx + 1) >> 1) : (S2 ? (kx == 1 ? (COLS + 1) / 2 + lm : lm + (kx >> 1)) : lm + kx))) * 16;
+                      : smem + (g * NPIX + (S2 ? 2 * MB : MB) * rg * COLS + (S2 ? (kx == 1 ? (COLS + 1) / 2 + lm : lm + (kx >> 1)) : lm + kx)) * 16;
     auto load_a = [&](sph8 (&a)[GM][2], int abuf_off, int grp) {
         const int tap = grp / GPT, mb0 = (grp % GPT) * GM;
         const int ky = tap / 3, kx = tap % 3;
 #pragma unroll
         for (int m = 0; m < GM; ++m) {
-            const int r = UP ? ((mb0 + m + ky + 1) >> 1) : ((S2 || TP) ? 2 * (mb0 + m) + ky : mb0 + m + ky);
+            const int r = (S2 || TP) ? 2 * (mb0 + m) + ky : mb0 + m + ky;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
                 a[m][t] = *reinterpret_cast<const sph8*>(aptr[kx] + abuf_off + t * G::A_PART + r * COLS * 16);

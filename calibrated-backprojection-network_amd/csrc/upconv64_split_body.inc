@@ -1,4 +1,4 @@
-// The body of upconv2x_split64_kernel (csrc/conv_split.hip), included once per tile form: in scope are the kernel's template
+// The body of upconv2x_split64_kernel (csrc/upconv_split.hip), included once per tile form: in scope are the kernel's template
 // parameters PIN / POUT, `p`, `smem`, the compile-time `TP` and the tile's `block`, `nblocks`, `tilesX`, `tilesY`.
     // TP: transposed tiles for a narrow last tile column (see conv3x3_split_kernel): 16 low-resolution rows x 16 columns, a wave's
     // 32-pixel block = rows 2 rg, 2 rg + 1 x 16 pixels, the staged region 18 x 18 pixels in a buffer sized for the 10 x 34 of the

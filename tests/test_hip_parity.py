@@ -2045,7 +2045,7 @@ def test_forward_full_size_saturated_logits_keep_the_fp64_criterion(dev, slow):
 
 def test_forward_full_size_intra_frame_dynamic_range(dev, kenv):
     """a large dynamic range INSIDE one frame.  The fp16 windows of the split-operand convs sit on the per-frame
-    maximum and keep 22 bits for 29 binades below it (csrc/conv_split.hip:15-22); every `amag` case of the op tests scales a whole
+    maximum and keep 22 bits for 29 binades below it (csrc/split_common.h:18-25); every `amag` case of the op tests scales a whole
     tensor.  Here frame 0 carries a handful of image pixels 1e4 x the rest (a saturated sensor patch before normalisation) and a
     sparse depth map that mixes 0.004 m and 655 m returns (the 16-bit PNG's extremes, src/data_utils.py:109-112) with ordinary ones;
     frame 1 is the same frame with the image outliers clamped.
@@ -2108,7 +2108,7 @@ def test_forward_full_size_trained_like_weights(dev, preset, shape, seeds, fuse_
     an fp16 window -- so the full-size forward is stressed with TRAINED-LIKE statistics (synthetic.make_state_dicts(
     trained_like=True): Student-t entries, per-filter scales spread log-uniformly over 2^7, 10 % of the filters exactly zero =
     dead channels).  A few filters then own a layer's output range: the pair tensors' window "from a bound" (max |a| of the
-    sources x the widest filter's L1 norm, csrc/conv_split.hip sp_pair_out_scale) overshoots the true maximum by more binades
+    sources x the widest filter's L1 norm, csrc/split_common.h sp_pair_out_scale) overshoots the true maximum by more binades
     than on xavier weights, and most channels sit far below the window's top.  Asserted per seed: the 1e-4 gate against the
     fp32 oracle; against an fp64 evaluation the HIP path is at most 2x as far from the exact result as the fp32 oracle is
     (or within 2e-5: the resolution of a max over 4e5 pixels); every pair tensor's window slack stays below the 16 binades

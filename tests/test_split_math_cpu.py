@@ -1,4 +1,4 @@
-"""The arithmetic of csrc/conv_split.hip restated in numpy (no GPU): fp32 operands as pairs of fp16 values,
+"""The arithmetic of the split-operand kernels (csrc/split_common.h) restated in numpy (no GPU): fp32 operands as pairs of fp16 values,
 a 2^k = h1 + 2^-11 h2, w 2^e = w1 + w2, a w = 2^-(e+k) (h1 w1 + h1 w2 + h2 (w1 2^-11)) -- the 3x3 kernels in the form
 h1 w1 + 2^-11 (h1 (w2 2^11) + h2 w1), the folded up-conv with w1 2^-11 formed per weight set.  Checks the representation
 error of the scheme against fp64 and the exponent rule of the host mirror (ops.act_exponent_for)."""
@@ -52,7 +52,7 @@ def test_split_product_representation_error(amag, folded):
 
 
 def test_act_exponent_rule():
-    """ops.act_exponent_for restates the device rule (sp_act_scale, csrc/conv_split.hip): the frame's maximum lands in
+    """ops.act_exponent_for restates the device rule (sp_act_scale, csrc/split_common.h): the frame's maximum lands in
     [2^14, 2^15) of the fp16 window -- below the overflow at 65504 even after h1's rounding -- and degenerate maxima
     give finite scales."""
     for amax in (1e-30, 1e-6, 0.0039, 1.0, 255.9, 256.0, 300.0, 65504.0, 4.0e6, 3.0e30):
@@ -81,7 +81,7 @@ def test_window_slack_costs_nothing():
 
 
 def _bound_scale(bound):
-    """sp_scale_of_bound (csrc/conv_split.hip): 2^k with bound 2^k in [2^14, 2^15), finite for 0 / Inf / NaN."""
+    """sp_scale_of_bound (csrc/split_common.h): 2^k with bound 2^k in [2^14, 2^15), finite for 0 / Inf / NaN."""
     bits = int(np.float32(bound).view(np.uint32))
     k = 14 + 127 - ((bits >> 23) & 255)
     return 2.0 ** max(-100, min(100, k))

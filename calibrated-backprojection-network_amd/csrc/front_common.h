@@ -1,5 +1,5 @@
 // front_common.h -- shared by the tile kernels that run 16x16x32 fp16 MFMAs over split operands on 8 x 16 half-resolution
-// tiles (csrc/front.hip: the encoder's full-resolution front; csrc/kb_level.hip: the KB blocks of levels 1-3 and conv5).
+// tiles: the encoder's full-resolution front (csrc/kb1_front.hip: the image branch; csrc/kb1_depth_front.hip: the depth branch).
 #pragma once
 
 #include "conv_common.h"

@@ -165,11 +165,9 @@ extern "C" int kbn_depth_head_forward(const float* x, const float* weight, float
         const long long blocks = (long long)tilesX * tilesY * n;
         if (blocks > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
         const size_t lds = sizeof(float) * (size_t)channels * HQ_PLANE;
-        static kbn::DeviceOnce once;
-        if (int rc = kbn::set_max_dynamic_lds(once, reinterpret_cast<const void*>(depth_head_dma_kernel), 160 * 1024))
+        if (int rc = launch_lds<depth_head_dma_kernel, 160 * 1024>((unsigned)blocks, 256, lds, (hipStream_t)stream, x, weight, depth, logits,
+                                                                   channels, height, width, tilesX, tilesY, min_predict_depth, ratio))
             return rc;
-        hipLaunchKernelGGL(depth_head_dma_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, x, weight,
-                           depth, logits, channels, height, width, tilesX, tilesY, min_predict_depth, ratio);
         KBN_CHECK_LAUNCH();
         return KBN_OK;
     }
@@ -442,21 +440,16 @@ extern "C" int kbn_conv_head_forward(const float* x, long long x_batch_stride, c
     p.dmin = min_predict_depth;
     p.ratio = (float)((double)min_predict_depth / (double)max_predict_depth);   // evaluated in double like the reference's scalar
     const size_t lds = sizeof(float) * ((size_t)channels * CH_PLANE + (size_t)9 * (channels / 4) * 64);
-    auto launch = [&](auto kern, DeviceOnce& once) -> int {
-        if (int rc = set_max_dynamic_lds(once, reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-        int cus = device_cu_count();
-        if (cus < 1) cus = 256;
-        const long long grid = blocks < 2LL * cus ? blocks : 2LL * cus;   // persistent: two workgroups per CU
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(CH_THREADS), lds, (hipStream_t)stream, p);
-        return KBN_OK;
-    };
-    static DeviceOnce o1, o2, o3, o4;
+    int cus = device_cu_count();
+    if (cus < 1) cus = 256;
+    const unsigned grid = (unsigned)(blocks < 2LL * cus ? blocks : 2LL * cus);   // persistent: two workgroups per CU
+    auto launch = [&](auto C4) { return launch_lds<conv_head_kernel<decltype(C4)::value>, 160 * 1024>(grid, CH_THREADS, lds, (hipStream_t)stream, p); };
     int rc;
     switch (channels / 4) {
-        case 1: rc = launch(conv_head_kernel<1>, o1); break;
-        case 2: rc = launch(conv_head_kernel<2>, o2); break;
-        case 3: rc = launch(conv_head_kernel<3>, o3); break;
-        default: rc = launch(conv_head_kernel<4>, o4); break;
+        case 1: rc = launch(std::integral_constant<int, 1>{}); break;
+        case 2: rc = launch(std::integral_constant<int, 2>{}); break;
+        case 3: rc = launch(std::integral_constant<int, 3>{}); break;
+        default: rc = launch(std::integral_constant<int, 4>{}); break;
     }
     if (rc != KBN_OK) return rc;
     KBN_CHECK_LAUNCH();

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/kbnet_hip.h"
 
@@ -91,6 +92,26 @@ inline int set_max_dynamic_lds(DeviceOnce& once, const void* kernel, int bytes) 
         return KBN_ERR_LAUNCH;   // not a stream operation: legal while a stream is being captured
     word.fetch_or(bit, std::memory_order_relaxed);
     return KBN_OK;
+}
+// One launch of the kernel (instantiation) K with `lds` bytes of dynamic LDS, its limit raised to MAX_LDS bytes once per device.
+// The flag that records the raise is lds_once<K>: it belongs to K by construction, no call site pairs a flag with a kernel by hand
+// (a wrong pairing compiles, works on the first device and fails on a second one only).  The caller checks the launch (KBN_CHECK_LAUNCH).
+template <auto K>
+inline DeviceOnce lds_once;
+template <auto K, int MAX_LDS, class... Args>
+int launch_lds(unsigned blocks, unsigned threads, size_t lds, hipStream_t stream, const Args&... args) {
+    if (int rc = set_max_dynamic_lds(lds_once<K>, reinterpret_cast<const void*>(K), MAX_LDS)) return rc;
+    hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), lds, stream, args...);
+    return KBN_OK;
+}
+// f(std::bool_constant<flags>...): run-time flags (in the kernel's template order) as compile-time ones.  Instantiates f for every
+// combination of the flags passed; a form that lacks a flag does not pass it.
+template <class F>
+int flag_dispatch(F&& f) { return f(); }
+template <class F, class... Flags>
+int flag_dispatch(F&& f, bool flag, Flags... rest) {
+    auto bind = [&](auto c) { return flag_dispatch([&](auto... more) { return f(c, more...); }, rest...); };
+    return flag ? bind(std::true_type{}) : bind(std::false_type{});
 }
 int device_cu_count();   // abi.hip: compute units of the current device (cached per device), <= 0 on error
 

@@ -492,21 +492,15 @@ static int s2d_launch(S2DParams& p, const int* min_pool_sizes, int n_min, const 
             if (p.ksize[i++] != k) return false;
         return true;
     };
-    auto launch = [&](auto kern, DeviceOnce& once) -> int {
-        if (int rc = set_max_dynamic_lds(once, reinterpret_cast<const void*>(kern), 160 * 1024)) return rc;
-        int cus = device_cu_count();
-        if (cus < 1) cus = 256;
-        const long long per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
-        const long long grid = blocks < per_cu * cus ? blocks : per_cu * cus;   // persistent workgroups
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(S2D_THREADS), lds, stream, p);
-        return KBN_OK;
-    };
-    static DeviceOnce set_kitti, set_void, set_voidtrain, set_dyn;
+    int cus = device_cu_count();
+    if (cus < 1) cus = 256;
+    const long long per_cu = (2 * lds <= 160 * 1024) ? 2 : 1;
+    const unsigned grid = (unsigned)(blocks < per_cu * cus ? blocks : per_cu * cus);   // persistent workgroups
     int rc;
-    if (matches(5, {5, 7, 9, 11, 13, 15, 17})) rc = launch(s2d_kernel<KittiPools>, set_kitti);
-    else if (matches(2, {15, 17, 23, 27, 29})) rc = launch(s2d_kernel<VoidPools>, set_void);
-    else if (matches(3, {15, 17, 19, 23, 27})) rc = launch(s2d_kernel<VoidTrainPools>, set_voidtrain);
-    else rc = launch(s2d_kernel<DynamicPools>, set_dyn);
+    if (matches(5, {5, 7, 9, 11, 13, 15, 17})) rc = launch_lds<s2d_kernel<KittiPools>, 160 * 1024>(grid, S2D_THREADS, lds, stream, p);
+    else if (matches(2, {15, 17, 23, 27, 29})) rc = launch_lds<s2d_kernel<VoidPools>, 160 * 1024>(grid, S2D_THREADS, lds, stream, p);
+    else if (matches(3, {15, 17, 19, 23, 27})) rc = launch_lds<s2d_kernel<VoidTrainPools>, 160 * 1024>(grid, S2D_THREADS, lds, stream, p);
+    else rc = launch_lds<s2d_kernel<DynamicPools>, 160 * 1024>(grid, S2D_THREADS, lds, stream, p);
     if (rc != KBN_OK) return rc;
     KBN_CHECK_LAUNCH();
     return KBN_OK;

@@ -1,5 +1,5 @@
 // s2d_stage.h -- SparseToDensePool.forward (reference src/networks.py:2168-2196) evaluated ON CHIP for the 19 x 35 full-resolution
-// pixels one tile of the encoder's depth front reads (csrc/front.hip: kb1_depth_front_kernel<CFG>), with its convolutions on
+// pixels one tile of the encoder's depth front reads (csrc/kb1_depth_front.hip: kb1_depth_front_kernel<CFG>), with its convolutions on
 // the 16-bit matrix core.  The S2D tensor (8 channels at full resolution: 13.7 MB per KITTI frame written by kbn_s2d_forward and
 // read back by kbn_kb1_depth_front_forward) then exists only as the split granules of conv0_depth's input tile in LDS.
 //
@@ -13,7 +13,7 @@
 //       (up to four) blocks layer by layer: D[filter | filter][pixel] -- rows 0-7 the filters at pixel 32 b + n (B k-groups 0, 1 =
 //       its h1, h2), rows 8-15 the same filters at pixel 32 b + 16 + n (k-groups 2, 3).  TWO instructions per layer carry the
 //       three products of the two-term split: A0 = [w1 | w1 2^-11] . [h1 ; h2] and A1 = [w2 | 0] . [h1 ; h2] (8 channels per
-//       k-group; s2d_stage_pack_kernel in csrc/front.hip writes exactly this operand layout).  A lane ends up with 4 consecutive
+//       k-group; s2d_stage_pack_kernel in csrc/kb1_depth_front.hip writes exactly this operand layout).  A lane ends up with 4 consecutive
 //       channels of a pixel = half a granule: scale, LeakyReLU, split, ds_write_b64.
 //   P5  the 3x3 conv over cat[features, z, v] (10 -> 8): 8 filters fill half of a 16-row MFMA, so a block computes pixel
 //       PAIRS -- rows 0-7 the filters at pixel 2p, rows 8-15 the same filters at pixel 2p + 1 -- over the 3 x 4 window the two
@@ -23,7 +23,7 @@
 //       outside the image (conv0_depth's padding), split -> IN [term][19 x 35 pixels][8 channels], what phase B of the depth
 //       front reads.
 // Windows: every on-chip tensor takes its 2^k from a BOUND (max |input| x the widest filter's L1 norm, layer by layer), as
-// csrc/front.hip does for conv0; the bounds sit a few binades above the data and 2^16 of slack costs nothing.
+// csrc/kb1_depth_front.hip does for conv0; the bounds sit a few binades above the data and 2^16 of slack costs nothing.
 #pragma once
 
 #include "front_common.h"

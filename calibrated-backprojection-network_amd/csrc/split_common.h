@@ -226,25 +226,14 @@ __host__ __device__ constexpr bool uf_wide(int out_channels) {   // whole 64-wid
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// One launch of the kernel instantiation K with `lds` bytes of dynamic LDS.  The once-per-device raise of its LDS limit
-// is recorded in a flag that belongs to this instantiation of the helper, i.e. to K alone.
+// One launch of the split-conv kernel instantiation K (launch_lds, kbn_common.h: the once-per-device flag belongs to K); its flags
+// PIN, POUT, TP, ONE come from flag_dispatch
 template <auto K>
 int split_launch(unsigned blocks, unsigned threads, size_t lds, hipStream_t stream, const SplitConvParams& p) {
-    static DeviceOnce once;
-    if (int rc = set_max_dynamic_lds(once, reinterpret_cast<const void*>(K), 160 * 1024)) return rc;
-    hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), lds, stream, p);
-    return KBN_OK;
+    return launch_lds<K, 160 * 1024>(blocks, threads, lds, stream, p);
 }
-
-// f(std::bool_constant<flags>...): the run-time flags (PIN, POUT, TP, ONE of a launch, in the kernel's template order) as
-// compile-time ones.  Instantiates f for every combination of the flags passed; a form that lacks a flag does not pass it.
-template <class F>
-int split_dispatch(F&& f) { return f(); }
-template <class F, class... Flags>
-int split_dispatch(F&& f, bool flag, Flags... rest) {
-    auto bind = [&](auto c) { return split_dispatch([&](auto... more) { return f(c, more...); }, rest...); };
-    return flag ? bind(std::true_type{}) : bind(std::false_type{});
-}
+template <class... A>
+int split_dispatch(A&&... a) { return flag_dispatch(std::forward<A>(a)...); }
 
 // Launchers shared between the translation units of the split-operand kernels.
 // conv_split.hip: per-filter exponents (split_scale_kernel over `per_filter` weights of each of ceil(OC / NT) * NT filters) and

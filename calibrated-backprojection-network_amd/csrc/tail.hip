@@ -4,7 +4,7 @@
 //     depth    = d_min / (sigmoid(logits) + d_min / d_max)                              reference src/kbnet_model.py:181-184
 // Same fusion as conv_head_kernel (csrc/head.hip; the full-resolution feature tensor between the two convs never leaves the
 // CU), but the C -> C conv (C <= 16; KBNet: 12) takes its fp32 products as three fp16 MFMAs over two-term splits of both
-// operands like csrc/conv_split.hip / csrc/front.hip instead of running on the fp32 MFMAs: at 12 x 12 x 9 multiply-adds per
+// operands like csrc/conv_split.hip / csrc/kb1_front.hip instead of running on the fp32 MFMAs: at 12 x 12 x 9 multiply-adds per
 // pixel of a full-resolution map the fp32 pipe was what bound the launch (conv_head_kernel: 0.60 busy, 737 us per 32 KITTI
 // frames for 35 GFLOP).  The fp16 window of the input follows the data tile by tile (max |x| over the pixels the workgroup
 // loads); the features stay fp32 in LDS and the one-filter head + sigmoid mapping run on the vector ALU as before.
@@ -367,15 +367,10 @@ static int conv_tail_launch(const float* x, long long x_batch_stride, const void
     p.dmin = min_predict_depth;
     p.ratio = (float)((double)min_predict_depth / (double)max_predict_depth);   // evaluated in double like the reference's scalar
     const size_t lds = (size_t)2 * 2 * TL_NP0 * 16 + (size_t)channels * TL_FP * 4 + (size_t)channels * 9 * 4;
-    static DeviceOnce once, oncep, once1, oncep1;
     const bool one_term = knob(KNOB_FP16_ONE_TERM) != 0;   // THROUGHPUT-ONLY: h1 w1 alone
-    auto go = [&](auto kern, DeviceOnce& o) -> int {
-        if (int rc = set_max_dynamic_lds(o, reinterpret_cast<const void*>(kern), 80 * 1024)) return rc;
-        hipLaunchKernelGGL(kern, dim3(p.ntiles), dim3(TL_THREADS), lds, (hipStream_t)stream, p);
-        return KBN_OK;
-    };
-    if (int rc = x_pair ? (one_term ? go(conv_tail_kernel<true, true>, oncep1) : go(conv_tail_kernel<true, false>, oncep))
-                        : (one_term ? go(conv_tail_kernel<false, true>, once1) : go(conv_tail_kernel<false, false>, once)))
+    if (int rc = flag_dispatch([&](auto PAIR, auto ONE) {
+            return launch_lds<conv_tail_kernel<PAIR, ONE>, 80 * 1024>(p.ntiles, TL_THREADS, lds, (hipStream_t)stream, p);
+        }, x_pair != nullptr, one_term))
         return rc;
     KBN_CHECK_LAUNCH();
     return KBN_OK;

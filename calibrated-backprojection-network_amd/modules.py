@@ -859,7 +859,7 @@ class KBNetEncoder(torch.nn.Module):
             self.conv5_depth = VGGNetBlock(fd[3], fd[4], n_convolutions_depth[4], 2, weight_initializer, act)
         self._f = (list(fi), list(fd), list(ff))
         # conv0_image + the level-0 KB block's conv_image / conv_fused as ONE launch, conv0's output kept on the CU
-        # (ops.kb1_front, csrc/front.hip): KBNet's level 0 (48 / 48 filters) in all presets; other widths keep the
+        # (ops.kb1_front, csrc/kb1_front.hip): KBNet's level 0 (48 / 48 filters) in all presets; other widths keep the
         # separate kernels
         self.front = True
         # OFF by default (the reference computes it): do not launch conv_image of KB level 3, whose output nothing reads

@@ -385,7 +385,7 @@ int kbn_kb_block_forward(const float* image, long long image_batch_stride, const
  *     conv_fused  = act(conv1x1 s2 (cat[conv0_image, xyz]))      reference src/net_utils.py:1352-1369 (level 0: no `fused` input)
  * conv0_image (conv0_filters channels at full resolution) is consumed by nothing else, so it is computed per tile and kept
  * on the CU: it never reaches HBM.  All three convs on split fp16 operands (see the split-operand section above; same
- * accuracy class, same parity gate); csrc/front.hip.
+ * accuracy class, same parity gate); csrc/kb1_front.hip.
  *   image           N x image_channels x H x W (image_channels <= 4), frames image_batch_stride apart
  *                   (the fp16 windows of the image and of conv0's on-chip output follow the data tile by tile, inside the kernel)
  *   packed_weight   from kbn_kb1_front_pack_weight: conv0_image.conv.weight (conv0_filters x image_channels x 3 x 3),

@@ -1136,7 +1136,7 @@ def test_conv1x1s2_split_kernel(dev, ci, cf, cd, cout, hw, amag):
 @pytest.mark.parametrize("amag", [1.0, 255.0, 1e-3])
 def test_kb1_front_kernel(dev, hw, amag):
     """kbn_kb1_front_forward: conv0_image -> conv_image (3x3 s2) and conv_fused (1x1 s2 over cat[conv0_image, xyz]) in one
-    launch on split fp16 operands, conv0's output kept on the CU (csrc/front.hip).  Same bars as the other split kernels:
+    launch on split fp16 operands, conv0's output kept on the CU (csrc/kb1_front.hip).  Same bars as the other split kernels:
     against an fp64 evaluation of the three convs its error stays within 3.5x the oracle's fp32 convs' (in units of the
     output's rms per filter), and within the suite's single-op tolerance of the oracle.  Odd sizes, widths that are not
     multiples of 4, tiles cut by the border; image magnitudes that move both fp16 windows; frame 1 scaled differently

@@ -1520,8 +1520,27 @@ class KBNetModel(object):
         has nothing to wrap and changes nothing; checkpoints still carry the `module.` prefix its wrappers produce (save_model)."""
         return self
 
-    def compute_loss(self, *args, **kwargs):
-        raise KbnError("the HIP path is inference only (reference src/kbnet_model.py:188-304 is the training loss)")
+    def compute_loss(self, image0=None, image1=None, image2=None, output_depth0=None, sparse_depth0=None, validity_map_depth0=None,
+                     intrinsics=None, pose01=None, pose02=None, w_color=0.15, w_structure=0.95, w_sparse_depth=0.60, w_smoothness=0.04):
+        """The FORWARD VALUE of the reference's objective (src/kbnet_model.py:188-304): warp image1 / image2 into image0's view with
+        the predicted depth and the relative poses, then colour L1 + SSIM + sparse-depth L1 + edge-aware smoothness -- a quality score
+        that needs no ground truth.  Returns (loss, loss_info) with the reference's keys (0-dim fp32 tensors and the two warped
+        images), plus loss_info['per_frame']: N x 4 fp64, the (colour, structure, sparse depth, smoothness) of each frame.  One
+        kernel launch (ops.photometric_loss) and a few scalar torch ops on its N x 8 sums; nothing synchronises with the host.
+        A frame without a valid sparse point makes the sparse-depth term (and the loss) NaN, as in the reference.  There is no
+        backward pass: the HIP path does not train."""
+        given = {"image0": image0, "image1": image1, "image2": image2, "output_depth0": output_depth0, "sparse_depth0": sparse_depth0,
+                 "validity_map_depth0": validity_map_depth0, "intrinsics": intrinsics, "pose01": pose01, "pose02": pose02}
+        missing = [k for k, v in given.items() if v is None]
+        if missing:
+            raise KbnError("compute_loss: missing " + ", ".join(missing) + " (reference src/kbnet_model.py:188-201)")
+        sums, image01, image02 = ops.photometric_loss(image0, image1, image2, output_depth0, sparse_depth0, validity_map_depth0,
+                                                      intrinsics, pose01, pose02, return_images=True)
+        per_frame = ops.loss_terms(sums, image0.shape[2], image0.shape[3])
+        color, structure, sparse, smooth = per_frame.mean(dim=0).float().unbind(0)
+        loss = w_color * color + w_structure * structure + w_sparse_depth * sparse + w_smoothness * smooth
+        return loss, {"loss_color": color, "loss_structure": structure, "loss_sparse_depth": sparse, "loss_smoothness": smooth,
+                      "loss": loss, "image01": image01, "image02": image02, "per_frame": per_frame}
 
     def load_state_dicts(self, sd_s2d, sd_encoder, sd_decoder):
         """Accepts keys with or without the DataParallel `module.` prefix."""

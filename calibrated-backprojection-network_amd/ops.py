@@ -1357,3 +1357,76 @@ def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate
     cnt = sums[:, 4:5].clamp_min(1.0)
     mean = sums[:, :4] / cnt
     return torch.stack([mean[:, 0], mean[:, 1].sqrt(), mean[:, 2], mean[:, 3].sqrt()], dim=1)
+
+
+# ------------------------------------------------------------------ forward value of the objective
+_LOSS_ARGS = ("image0", "image1", "image2", "output_depth", "sparse_depth", "validity_map", "intrinsics", "pose01", "pose02")
+
+
+@_on_tensor_device
+def photometric_loss(image0, image1, image2, output_depth, sparse_depth, validity_map, intrinsics, pose01, pose02,
+                     return_images: bool = False):
+    """The sums behind KBNetModel.compute_loss (reference src/kbnet_model.py:188-304) in one kernel: an N x 8 fp64 tensor
+    {sum |image01 - image0|, sum |image02 - image0|, sum ssim01, sum ssim02, sum v |sparse - depth|, sum v, sum wx |dx depth|,
+    sum wy |dy depth|} per frame (kbn_photometric_loss_forward), where image01 / image02 are image1 / image2 sampled where the
+    depth and the relative poses put each pixel of image0.  `return_images`: also the two warped images (N x 3 x H x W), which the
+    reference hands back for logging; without it nothing image-sized is written."""
+    lib = _lib.load()
+    tensors = (image0, image1, image2, output_depth, sparse_depth, validity_map, intrinsics, pose01, pose02)
+    for t, name in zip(tensors, _LOSS_ARGS):
+        if not isinstance(t, torch.Tensor):
+            raise KbnError(f"photometric_loss: {name} must be a tensor, got {type(t).__name__}")
+    if image0.dim() != 4 or image0.shape[1] != 3:
+        raise KbnError(f"photometric_loss: image0 must be N x 3 x H x W, got {tuple(image0.shape)}")
+    n, _, h, w = image0.shape
+    if n < 1 or h < 3 or w < 3:
+        raise KbnError(f"photometric_loss: needs at least one frame of at least 3 x 3 pixels (SSIM pools 3 x 3 windows), got {tuple(image0.shape)}")
+    want = {"image1": (n, 3, h, w), "image2": (n, 3, h, w), "output_depth": (n, 1, h, w), "sparse_depth": (n, 1, h, w),
+            "validity_map": (n, 1, h, w), "intrinsics": (n, 3, 3), "pose01": (n, 4, 4), "pose02": (n, 4, 4)}
+    for t, name in zip(tensors, _LOSS_ARGS):
+        if name in want and tuple(t.shape) != want[name]:
+            raise KbnError(f"photometric_loss: {name} must be {want[name]} beside image0 {tuple(image0.shape)}, got {tuple(t.shape)}")
+    for t, name in zip(tensors, _LOSS_ARGS):
+        _require(t, name)
+    i0, i1, i2, d, s, v, k, p1, p2 = (t.contiguous() for t in tensors)
+    sums = torch.empty((n, 8), device=i0.device, dtype=torch.float64)   # the entry zeroes it on the stream
+    w1 = torch.empty_like(i0) if return_images else None
+    w2 = torch.empty_like(i0) if return_images else None
+    check(lib.kbn_photometric_loss_forward(i0.data_ptr(), i1.data_ptr(), i2.data_ptr(), d.data_ptr(), s.data_ptr(), v.data_ptr(),
+                                           k.data_ptr(), p1.data_ptr(), p2.data_ptr(), sums.data_ptr(),
+                                           w1.data_ptr() if return_images else None, w2.data_ptr() if return_images else None,
+                                           n, h, w, _stream()), "kbn_photometric_loss_forward")
+    return (sums, w1, w2) if return_images else sums
+
+
+def loss_terms(sums: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """N x 8 sums of `photometric_loss` -> N x 4 fp64 (colour, structure, sparse depth, smoothness) of each frame, normalised as the
+    reference normalises the batch (src/losses.py): colour and structure sum the 3 channels and divide by H W (three times a
+    per-channel mean); sparse depth divides by the frame's number of valid points (NaN for a frame without one, as in the
+    reference); smoothness is mean over H (W-1) plus mean over (H-1) W.  The batch's terms are the means of the columns."""
+    hw = float(height * width)
+    return torch.stack([(sums[:, 0] + sums[:, 1]) / hw, (sums[:, 2] + sums[:, 3]) / hw, sums[:, 4] / sums[:, 5],
+                        sums[:, 6] / float(height * (width - 1)) + sums[:, 7] / float((height - 1) * width)], dim=1)
+
+
+def pose_matrix(v: torch.Tensor) -> torch.Tensor:
+    """N x 6 -> N x 4 x 4 as the reference's net_utils.pose_matrix (src/net_utils.py:1493-1595): the FIRST three entries are the
+    axis-angle rotation and the LAST three the translation (its docstring says the opposite; the code decides), axis = r / (|r| + 1e-7),
+    M = T(t) R.  Plain torch on the tensor's device and in its dtype: 16 numbers per frame."""
+    if not isinstance(v, torch.Tensor) or v.dim() != 2 or v.shape[1] != 6:
+        raise KbnError(f"pose_matrix: expected an N x 6 tensor, got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
+    r, t = v[:, :3], v[:, 3:]
+    angle = torch.linalg.vector_norm(r, dim=1, keepdim=True)
+    axis = r / (angle + 1e-7)
+    ca, sa = torch.cos(angle[:, 0]), torch.sin(angle[:, 0])
+    c = 1 - ca
+    x, y, z = axis[:, 0], axis[:, 1], axis[:, 2]
+    xs, ys, zs = x * sa, y * sa, z * sa
+    xc, yc, zc = x * c, y * c, z * c
+    xyc, yzc, zxc = x * yc, y * zc, z * xc
+    zero, one = torch.zeros_like(ca), torch.ones_like(ca)
+    rows = [x * xc + ca, xyc - zs, zxc + ys, t[:, 0],
+            xyc + zs, y * yc + ca, yzc - xs, t[:, 1],
+            zxc - ys, yzc + xs, z * zc + ca, t[:, 2],
+            zero, zero, zero, one]
+    return torch.stack(rows, dim=1).reshape(-1, 4, 4)

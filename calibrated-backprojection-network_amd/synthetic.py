@@ -113,3 +113,60 @@ def make_state_dicts(cfg: KBNetConfig, seed: int = 0, gain: float = 1.0, trained
         else:
             out.append({k: gain * _xavier_normal(part + "/" + k, s, seed) for k, s in shapes.items()})
     return tuple(out)
+
+
+def _box2(a: np.ndarray, radius: int) -> np.ndarray:
+    """Two passes of a (2 radius + 1)^2 box mean over the last two axes, 'valid' (each pass trims `radius` per side), in fp64."""
+    k = 2 * radius + 1
+    for _ in range(2):
+        for axis in (-2, -1):
+            c = np.cumsum(np.insert(a, 0, 0.0, axis=axis), axis=axis)
+            n = c.shape[axis]
+            a = (np.take(c, range(k, n), axis=axis) - np.take(c, range(0, n - k), axis=axis)) / k
+    return a
+
+
+def _smooth_field(g: np.random.Generator, shape, height: int, width: int, radius: int) -> np.ndarray:
+    """Band-limited noise, shape + (height, width), each map stretched to span [0, 1]."""
+    a = _box2(g.random(tuple(shape) + (height + 4 * radius, width + 4 * radius)), radius) if radius > 0 else g.random(tuple(shape) + (height, width))
+    lo, hi = a.min(axis=(-2, -1), keepdims=True), a.max(axis=(-2, -1), keepdims=True)
+    return (a - lo) / np.maximum(hi - lo, 1e-12)
+
+
+def make_triplet(n: int, height: int, width: int, kind: str = "kitti", seed: int = 1, radius: int = 4):
+    """Inputs of KBNetModel.compute_loss: (image0, image1, image2 N3HW in [0, 1], output_depth N1HW, sparse_depth N1HW,
+    validity N1HW, intrinsics N33, pose01, pose02 N6: axis-angle rotation first, translation last, as ops.pose_matrix reads them),
+    CPU fp32.  The images are BAND-LIMITED (uniform noise box-filtered twice with `radius`, the three frames sharing 80 % of
+    their content at small offsets): a warped pixel inherits the rounding of its sample position (about W 2^-23 pixels in fp32)
+    times the local image gradient, and on independent pixels (make_frames) that alone puts two correct fp32 evaluations 2e-4
+    apart.  The dense depth is smooth inside the preset's range (its nearer fifth, where a 0.5 m translation moves pixels);
+    the sparse depth samples it at the preset's density (at least one point per frame) with 1 % noise, rounded to 1/256 m like the 16-bit PNGs.  The principal
+    point and focal length follow the frame size (focal 0.6 x the longer side: a 40 degree half field of view)."""
+    density, (lo, hi), _ = FRAME_STATS[kind]
+    g = _rng(seed)
+    off = 2
+    scene = _smooth_field(g, (n, 3), height + 2 * off, width + 2 * off, radius)
+    images = []
+    for dy, dx in ((0, 0), (1, -2), (-1, 2)):
+        own = _smooth_field(g, (n, 3), height, width, radius)
+        images.append(0.8 * scene[..., off + dy:off + dy + height, off + dx:off + dx + width] + 0.2 * own)
+    near, far = lo + 0.02 * (hi - lo), lo + 0.27 * (hi - lo)
+    depth = near + (far - near) * _smooth_field(g, (n, 1), height, width, 2 * radius)
+    mask = g.random((n, 1, height, width)) < density
+    mask.reshape(n, -1)[np.arange(n), g.integers(height * width, size=n)] = True   # never a frame without a point (tiny frames)
+    noisy = depth * (1.0 + 0.01 * g.standard_normal((n, 1, height, width)))
+    sparse = np.round(noisy * 256.0) / 256.0 * mask
+    validity = sparse > 0
+    k = np.zeros((n, 3, 3))
+    k[:, 0, 0] = k[:, 1, 1] = 0.6 * max(width, height)
+    k[:, 0, 2] = 0.5 * (width - 1)
+    k[:, 1, 2] = 0.5 * (height - 1)
+    k[:, 2, 2] = 1.0
+    step = 0.025 * (near + far)          # translation that moves a mid-range point by ~0.03 W pixels
+    poses = []
+    for sign in (1.0, -1.0):
+        p = np.concatenate([0.02 * (2.0 * g.random((n, 3)) - 1.0), step * (2.0 * g.random((n, 3)) - 1.0)], axis=1)
+        p[:, 5] = sign * np.abs(p[:, 5])   # one neighbour frame ahead, one behind
+        poses.append(p)
+    arrays = images + [depth, sparse, validity, k] + poses
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in arrays)

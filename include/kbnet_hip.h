@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define KBN_ABI_VERSION 7
+#define KBN_ABI_VERSION 8
 
 typedef void* kbn_stream_t; /* hipStream_t */
 
@@ -552,6 +552,29 @@ int kbn_eval_accumulate(const float* output_depth, const float* ground_truth,
                         const float* ground_truth_validity, double* sums, int n, int height,
                         int width, float min_evaluate_depth, float max_evaluate_depth,
                         kbn_stream_t stream);
+
+/* ------------------------------------------------- forward value of the objective ----
+ * KBNetModel.compute_loss                              reference src/kbnet_model.py:188-304
+ *   net_utils.backproject_to_camera / project_to_pixel  reference src/net_utils.py:1638-1704
+ *     points = K^-1 [x y 1]^T z;  xy = (T p)[0:2] / ((T p)[2] + 1e-7),  T = rows 0-2 of (K | 0) pose
+ *   net_utils.grid_sample (bilinear, border, align_corners)  reference src/net_utils.py:1706-1739
+ *   losses.color_consistency_loss_func, structural_consistency_loss_func (ssim: AvgPool2d(3, 1),
+ *     stretched back to H x W with nearest interpolation), sparse_depth_consistency_loss_func,
+ *     smoothness_loss_func                              reference src/losses.py:23-158
+ * in ONE image-sized launch, without an image-sized intermediate.  image0 / image1 / image2:
+ * N x 3 x H x W; output_depth / sparse_depth / validity_map: N x 1 x H x W; intrinsics N x 3 x 3;
+ * pose01 / pose02 N x 4 x 4 (image0 -> image1, image0 -> image2).  WRITES sums[n*8 + k] (fp64; the
+ * entry zeroes them on `stream` first): k=0 sum|image01 - image0|, 1 sum|image02 - image0| (over
+ * the 3 channels), 2 / 3 sum of the up-sampled 1-SSIM maps of the two pairs (3 channels), 4 sum
+ * v|sparse - depth|, 5 sum v, 6 sum wx|dx depth| (H (W-1) terms), 7 sum wy|dy depth| ((H-1) W terms).
+ * image01 / image02 (N x 3 x H x W): the warped neighbour frames, or both NULL.  height, width >= 3.
+ * Sample positions of any value (points behind the camera, Inf, NaN) read inside the planes. */
+int kbn_photometric_loss_forward(const float* image0, const float* image1, const float* image2,
+                                 const float* output_depth, const float* sparse_depth,
+                                 const float* validity_map, const float* intrinsics,
+                                 const float* pose01, const float* pose02, double* sums,
+                                 float* image01, float* image02, int n, int height, int width,
+                                 kbn_stream_t stream);
 
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:

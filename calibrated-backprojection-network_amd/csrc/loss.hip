@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(
                     const float numer = (2.0f * mu_xy + 1e-4f) * (2.0f * sg_xy + 9e-4f);
                     const float denom = (mu_xx + mu_yy + 1e-4f) * (sg_x + sg_y + 9e-4f);
                     float v = (1.0f - numer / denom) / 2.0f;
-                    v = fminf(fmaxf(v, 0.f), 1.f);
+                    v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);   // torch.clamp keeps NaN; fminf(fmaxf()) would turn it into 0
                     if (wgt > 0.f) ss += v * wgt;
                 }
             }

@@ -23,6 +23,13 @@ Cases (inputs from synthetic.make_triplet, band-limited images of radius 4)
                   (near z = 0 the sample position jumps from one border to the other and fp32 and fp64 disagree by a whole
                   image, so no fixture goes there: asserted below for every case)
   loss_novalid    frame 1 has no valid sparse point: the sparse-depth term and the loss are NaN
+
+Cases from tests/loss_cases.py (the inputs make_triplet does not produce; see its docstring)
+  loss_general_camera     3 x 37 x 45: every frame its own K (fx != fy, skew, principal point off the centre) and its own poses
+  loss_two_plane          2 x 37 x 45: a near and a far plane in 11 x 11 cells, the camera between them.  The only case with points
+                          on both sides of the camera; |z| > 0.1 holds for it like for every other
+  loss_weighted_validity  2 x 24 x 40: validity in {0, 0.25, 1}
+  loss_textured           2 x 37 x 45: images of radius 1
 """
 import os
 import sys
@@ -34,9 +41,11 @@ sys.dont_write_bytecode = True
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, "/root/reference/src")
 
 import kbnet_amd as kb  # noqa: E402
+import loss_cases  # noqa: E402  (tests/)
 import losses  # noqa: E402  (reference)
 import net_utils  # noqa: E402  (reference)
 
@@ -102,8 +111,8 @@ def save(name, vectors, inputs, r32, r64, dist, matrices64):
     return size
 
 
-def case(name, n, h, w, kind, seed, edit=None):
-    i0, i1, i2, depth, sparse, validity, k, v01, v02 = kb.synthetic.make_triplet(n, h, w, kind, seed=seed, radius=4)
+def case(name, n, h, w, kind, seed, edit=None, radius=4, both_sides=False):
+    i0, i1, i2, depth, sparse, validity, k, v01, v02 = kb.synthetic.make_triplet(n, h, w, kind, seed=seed, radius=radius)
     t = {"image0": i0, "image1": i1, "image2": i2, "depth": depth, "sparse": sparse, "validity": validity, "k": k, "v01": v01, "v02": v02}
     if edit:
         edit(t)
@@ -117,8 +126,9 @@ def case(name, n, h, w, kind, seed, edit=None):
     inputs = (t["image0"], t["image1"], t["image2"], t["depth"], t["sparse"], t["validity"], t["k"], poses[0], poses[1])
     r32, r64, dist, outside, (closest, zmin, zmax) = evaluate(inputs)
     # no fixture near z = 0 (see the module docstring): points stay clearly in front of the camera, or (loss_behind, which
-    # asserts its own 0.5 m) clearly behind it
-    assert closest > 0.1 and (min(zmin) > 0 or max(zmax) < 0), (name, closest, zmin, zmax)
+    # asserts its own 0.5 m) clearly behind it; `both_sides` (loss_two_plane alone) has points on either side, none near z = 0
+    assert closest > 0.1 and (both_sides or min(zmin) > 0 or max(zmax) < 0), (name, closest, zmin, zmax)
+    assert not both_sides or (min(zmin) < 0 < max(zmax)), (name, zmin, zmax)
     size = save(name, vectors, inputs, r32, r64, dist, matrices64)
     print(f"{name}: {size / 1024:.0f} KiB  outside {outside[0]:.3f} / {outside[1]:.3f}  z in [{min(zmin):.2f}, {max(zmax):.2f}]  "
           + "  ".join(f"{k} {float(r64[k]):.6g} (fp32 {dist[k]:.1e})" for k in SCALARS)
@@ -155,6 +165,13 @@ def main():
         t["sparse"][1] = 0
         t["validity"][1] = 0
     case("loss_novalid", 2, 24, 40, "kitti", 18, novalid)
+
+    def family(name, seed):
+        return lambda t: loss_cases.apply(t, (name,), seed)
+    case("loss_general_camera", 3, 37, 45, "void", 41, family("general_camera", 41))
+    case("loss_two_plane", 2, 37, 45, "kitti", 42, family("two_plane", 42), both_sides=True)
+    case("loss_weighted_validity", 2, 24, 40, "kitti", 43, family("weighted_validity", 43))
+    case("loss_textured", 2, 37, 45, "void", 44, radius=loss_cases.radius(("textured",)))
 
 
 if __name__ == "__main__":

@@ -83,19 +83,45 @@ def _gradients(t):
     return t[..., :, :-1] - t[..., :, 1:], t[..., :-1, :] - t[..., 1:, :]
 
 
+def _pixel_maps(image0, image01, image02, depth, sparse, validity):
+    """The eight per-pixel maps whose per-frame sums the kernel returns, in its order: |image01 - image0|, |image02 - image0|,
+    the two stretched SSIM distances, v |sparse - depth|, v, wx |dx depth| (N x 1 x H x (W-1)), wy |dy depth| (N x 1 x (H-1) x W)."""
+    h, w = image0.shape[2:]
+    c = [(image0 - im).abs() for im in (image01, image02)]
+    s = [F.interpolate(ssim_distance(im, image0), size=(h, w), mode="nearest") for im in (image01, image02)]
+    ix, iy = _gradients(image0)
+    dx, dy = _gradients(depth)
+    sx = torch.exp(-ix.abs().mean(1, keepdim=True)) * dx.abs()
+    sy = torch.exp(-iy.abs().mean(1, keepdim=True)) * dy.abs()
+    return c[0], c[1], s[0], s[1], validity * (sparse - depth).abs(), validity, sx, sy
+
+
+def frame_sums(image0, image01, image02, depth, sparse, validity):
+    """-> N x 8, in the dtype of the inputs: what kbn_photometric_loss_forward writes for each frame (ops.photometric_loss),
+    { sum |image01 - image0|, sum |image02 - image0|, sum ssim01, sum ssim02, sum v |sparse - depth|, sum v, sum wx |dx depth|,
+    sum wy |dy depth| }."""
+    return torch.stack([_frame_sums(m) for m in _pixel_maps(image0, image01, image02, depth, sparse, validity)], 1)
+
+
+def loss_sums(image0, image1, image2, depth, sparse, validity, intrinsics, pose01, pose02):
+    """compute_loss's arguments -> frame_sums of its two warped images."""
+    h, w = image0.shape[2:]
+    points = backproject(depth, intrinsics)
+    image01 = warp(image1, project(points, pose01, intrinsics, h, w))
+    image02 = warp(image2, project(points, pose02, intrinsics, h, w))
+    return frame_sums(image0, image01, image02, depth, sparse, validity)
+
+
 def loss_terms(image0, image01, image02, depth, sparse, validity):
     """-> (terms, per_frame): the batch's (colour, structure, sparse depth, smoothness) as 0-dim tensors, formed in the order the
     reference forms them (each pair's batch mean first, the smoothness means over the whole batch), and the N x 4 terms of each
     frame.  The column means of per_frame equal the batch terms up to rounding."""
     h, w = image0.shape[2:]
     hw = float(h * w)
-    c = [_frame_sums((image0 - im).abs()) / hw for im in (image01, image02)]
-    s = [_frame_sums(F.interpolate(ssim_distance(im, image0), size=(h, w), mode="nearest")) / hw for im in (image01, image02)]
-    sp = _frame_sums(validity * (sparse - depth).abs()) / _frame_sums(validity)
-    ix, iy = _gradients(image0)
-    dx, dy = _gradients(depth)
-    sx = torch.exp(-ix.abs().mean(1, keepdim=True)) * dx.abs()
-    sy = torch.exp(-iy.abs().mean(1, keepdim=True)) * dy.abs()
+    c01, c02, s01, s02, spd, v, sx, sy = _pixel_maps(image0, image01, image02, depth, sparse, validity)
+    c = [_frame_sums(m) / hw for m in (c01, c02)]
+    s = [_frame_sums(m) / hw for m in (s01, s02)]
+    sp = _frame_sums(spd) / _frame_sums(v)
     terms = (c[0].mean() + c[1].mean(), s[0].mean() + s[1].mean(), sp.mean(), sx.mean() + sy.mean())
     per_frame = torch.stack([c[0] + c[1], s[0] + s[1], sp, sx.mean(dim=(1, 2, 3)) + sy.mean(dim=(1, 2, 3))], 1)
     return terms, per_frame

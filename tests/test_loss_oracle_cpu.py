@@ -10,6 +10,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -32,7 +33,8 @@ def _rel(a, b):
 
 
 def test_the_fixtures_cover_the_cases():
-    assert {"loss_even", "loss_odd", "loss_3x3", "loss_3x4", "loss_identity", "loss_outside", "loss_behind", "loss_novalid"} <= set(CASES)
+    assert {"loss_even", "loss_odd", "loss_3x3", "loss_3x4", "loss_identity", "loss_outside", "loss_behind", "loss_novalid",
+            "loss_general_camera", "loss_two_plane", "loss_weighted_validity", "loss_textured"} <= set(CASES)
     for name in CASES:
         assert os.path.getsize(os.path.join(GOLDEN_DIR, name + ".npz")) < 1 << 20
 
@@ -127,6 +129,74 @@ def test_oracle_against_the_imported_reference_full_size(kind, shape):
         own, ref = float((o32[name].double() - warp64[i]).abs().max()), float((warp32[i].double() - warp64[i]).abs().max())
         print(f"{kind} {name}: oracle fp32 {own:.2e}, reference fp32 {ref:.2e}")
         assert own <= 2 * ref, name
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_frame_sums_are_the_terms_taken_apart(name):
+    """lo.loss_sums (what the GPU tests gate ops.photometric_loss against, sum by sum) recombines into per_frame."""
+    g = load_golden(name)
+    args = [g[k].double() for k in INPUTS]
+    sums, out = lo.loss_sums(*args), lo.compute_loss(*args)
+    assert tuple(sums.shape) == (args[0].shape[0], 8) and sums.dtype == torch.float64
+    assert lo.loss_sums(*[g[k] for k in INPUTS]).dtype == torch.float32
+    got = kb.ops.loss_terms(sums, *args[0].shape[2:])
+    assert all(_rel(a, b) <= 1e-12 for a, b in zip(got.flatten(), out["per_frame"].flatten()))
+    if name in ("loss_general_camera", "loss_two_plane", "loss_weighted_validity", "loss_textured"):
+        assert float((sums[:, 0] - sums[:, 1]).abs().min()) > 0 and float((sums[:, 2] - sums[:, 3]).abs().min()) > 0
+
+
+def test_the_new_fixtures_are_what_they_claim():
+    k = load_golden("loss_general_camera")["intrinsics"]
+    assert bool(((k[:, 0, 0] / k[:, 1, 1] - 1).abs() >= 0.05).all()) and bool((k[:, 0, 1] != 0).all()) and not torch.equal(k[0], k[1])
+    g = load_golden("loss_two_plane")
+    step = (g["output_depth"][..., :, 1:] - g["output_depth"][..., :, :-1]).abs()
+    assert float(step.max()) > 5 and float(step.median()) < 0.1
+    assert set(load_golden("loss_weighted_validity")["validity_map"].unique().tolist()) == {0.0, 0.25, 1.0}
+    smooth, rough = load_golden("loss_odd")["image0"], load_golden("loss_textured")["image0"]
+    tv = lambda im: float((im[..., :, 1:] - im[..., :, :-1]).abs().mean())
+    assert tv(rough) > 2 * tv(smooth)
+
+
+# ---------------------------------------------------------------- the nearest stretch of the SSIM scores, restated on the host
+def nearest_src_index(dst, in_size, out_size):
+    """csrc/kbn_common.h nearest_src_index in numpy float32, operation for operation; `dst`: an int array."""
+    if in_size == out_size:
+        return dst
+    if out_size == 2 * in_size:
+        return dst >> 1
+    scale = np.float32(in_size) / np.float32(out_size)
+    s = np.floor(dst.astype(np.float32) * scale).astype(np.int64)
+    return np.minimum(s, in_size - 1)
+
+
+def ssim_axis_weight(s, size):
+    """csrc/loss.hip ssim_axis_weight: how many of the `size` output pixels take score `s` of the (size - 2)-long axis, searched
+    as the kernel searches them: d = s .. s + 3, d < size."""
+    cnt = np.zeros_like(s)
+    for k in range(4):
+        d = s + k
+        cnt += (d < size) & (nearest_src_index(np.minimum(d, size - 1), size - 2, size) == s)
+    return cnt
+
+
+def test_nearest_stretch_of_the_ssim_scores_for_every_length():
+    """The kernel's index and weight against interpolate(mode='nearest') in fp32 and fp64, for every length from 3 to 2048; and the
+    fact the weight's four-pixel search rests on: an output pixel is at most 2 past its source."""
+    for size in range(3, 2049):
+        d = np.arange(size)
+        mine = nearest_src_index(d, size - 2, size)
+        assert ((d - mine >= 0) & (d - mine <= 2)).all(), size
+        weights = ssim_axis_weight(np.arange(size - 2), size)
+        assert weights.sum() == size and weights.min() >= 1, size
+        for dtype in (torch.float32, torch.float64):
+            src = torch.arange(size - 2, dtype=dtype).reshape(1, 1, size - 2)
+            want = torch.nn.functional.interpolate(src, size=size, mode="nearest").flatten().long()
+            assert want.tolist() == mine.tolist(), (size, dtype)
+            assert torch.bincount(want, minlength=size - 2).tolist() == weights.tolist(), (size, dtype)
+        for dtype in (torch.float32, torch.float64) if size in (3, 4, 5, 17, 130, 257, 2048) else ():
+            src = torch.arange(size - 2, dtype=dtype).reshape(1, 1, size - 2, 1).expand(1, 1, size - 2, 3).contiguous()   # 2-D, as the loss
+            want = torch.nn.functional.interpolate(src, size=(size, 5), mode="nearest")[0, 0, :, 0].long()
+            assert want.tolist() == mine.tolist(), (size, dtype)
 
 
 # ---------------------------------------------------------------- host-side checks of the public surface (no GPU needed)

@@ -1564,3 +1564,6 @@ class KBNetModel(object):
                     "sparse_to_dense_pool_state_dict": pref(self.sparse_to_dense_pool.state_dict()),
                     "encoder_state_dict": pref(self.encoder.state_dict()),
                     "decoder_state_dict": pref(self.decoder.state_dict())}, checkpoint_path)
+
+
+from .posenet import PoseDecoder, PoseEncoder, PoseNetModel  # noqa: E402,F401  (posenet.py: the pose network beside KBNetModel)

@@ -1430,3 +1430,106 @@ def pose_matrix(v: torch.Tensor) -> torch.Tensor:
             zxc - ys, yzc + xs, z * zc + ca, t[:, 2],
             zero, zero, zero, one]
     return torch.stack(rows, dim=1).reshape(-1, 4, 4)
+
+
+# ------------------------------------------------------------------ pose network (eval mode)
+@_on_tensor_device
+def pack_conv2d_s2_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW (k in {3, 5, 7}, any channel counts) -> the [filter tile][K chunk][16][filters] order conv2d_s2_affine reads
+    (kbn_conv2d_s2_affine_pack_weight); `out`: an existing blob of the right size to re-pack into."""
+    lib = _lib.load()
+    w = weight.detach().contiguous()
+    _require(w, "weight", 4)
+    oc, cin, kh, kw = w.shape
+    if kh != kw:
+        raise KbnError("square kernels only")
+    nbytes = lib.kbn_conv2d_s2_affine_packed_weight_bytes(oc, cin, kh)
+    if nbytes == 0:
+        raise KbnError(f"conv2d_s2_affine: unsupported weight shape {tuple(w.shape)} (kernel size 3, 5 or 7)")
+    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+    check(lib.kbn_conv2d_s2_affine_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, kh, _stream()),
+          "kbn_conv2d_s2_affine_pack_weight")
+    return packed
+
+
+@_on_tensor_device
+def conv2d_s2_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                     out_channels: int, kernel_size: int, negative_slope: Optional[float] = 0.2,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(conv_{k x k, stride 2, padding k // 2}(cat(inputs, 1)) * scale + shift) (kbn_conv2d_s2_affine_forward): the conv +
+    eval-mode BatchNorm2d + activation of a PoseEncoder layer (reference src/net_utils.py:120-141) in one launch.  `inputs`: one
+    or two N x C_i x H x W tensors read in place (no concat); `scale` / `shift`: out_channels floats; `negative_slope` None: no
+    activation; `out`: an N x out_channels x ceil(H / 2) x ceil(W / 2) tensor or channel slice to write into."""
+    lib = _lib.load()
+    inputs = list(inputs)
+    if not 1 <= len(inputs) <= 2:
+        raise KbnError(f"conv2d_s2_affine: one or two inputs, got {len(inputs)}")
+    if kernel_size not in (3, 5, 7):
+        raise KbnError(f"conv2d_s2_affine: kernel size 3, 5 or 7, got {kernel_size}")
+    srcs = [tensor_src(t, f"inputs[{i}]") for i, t in enumerate(inputs)]
+    n, _, h, w = inputs[0].shape
+    for i, t in enumerate(inputs[1:], 1):
+        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
+            raise KbnError(f"conv2d_s2_affine: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
+    if n < 1 or h < 1 or w < 1:
+        raise KbnError(f"conv2d_s2_affine: empty input {tuple(inputs[0].shape)}")
+    cin = sum(s.channels for s in srcs)
+    _require(packed_weight, "packed_weight", 1)
+    want = lib.kbn_conv2d_s2_affine_packed_weight_bytes(out_channels, cin, kernel_size) // 4
+    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
+        raise KbnError(f"conv2d_s2_affine: packed_weight holds {packed_weight.numel()} floats, a {out_channels} x {cin} x "
+                       f"{kernel_size} x {kernel_size} weight packs into {want}")
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        _require(t, name, 1)
+        if t.numel() != out_channels or not t.is_contiguous():
+            raise KbnError(f"conv2d_s2_affine: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    if out is None:
+        out = torch.empty((n, out_channels, oh, ow), device=inputs[0].device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, out_channels, oh, ow):
+        raise KbnError(f"out has shape {tuple(out.shape)}, expected {(n, out_channels, oh, ow)}")
+    optr, obs = _planes(out, "out")
+    arr = (ConvSrc * len(srcs))(*srcs)
+    k2 = kernel_size * kernel_size
+    kpad = -(-cin * k2 // 16) * 16
+    nt = 16 if out_channels <= 16 else (32 if out_channels <= 32 else 64)
+    check(_launch(f"conv_s2_affine<{kernel_size},{nt // 16}>", 2.0 * n * oh * ow * cin * k2 * out_channels,
+                  lambda: lib.kbn_conv2d_s2_affine_forward(arr, len(srcs), packed_weight.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                                           optr, obs, n, out_channels, kernel_size, h, w,
+                                                           0 if negative_slope is None else 1,
+                                                           0.0 if negative_slope is None else float(negative_slope), _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 128) * 128) * kpad * (-(-out_channels // nt) * nt), pipe="fp32",
+                  nbytes=_src_bytes(srcs, n) + 4.0 * n * oh * ow * out_channels), "kbn_conv2d_s2_affine_forward")
+    return out
+
+
+@_on_tensor_device
+def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = False, out: Optional[torch.Tensor] = None,
+              dof_out: Optional[torch.Tensor] = None):
+    """PoseDecoder.forward without hidden layers (reference src/networks.py:2067-2075) in one launch (kbn_pose_head_forward):
+    latent N x C x h x w, weight 6 x C (x 1 x 1) -> N x 4 x 4 = pose_matrix(0.01 * mean_hw(conv1x1(latent))).  `return_dof`: also
+    the N x 6 vector.  `out` / `dof_out`: contiguous N x 4 x 4 / N x 6 tensors to write into."""
+    lib = _lib.load()
+    ptr, bs = _planes(latent, "latent")
+    n, c, h, w = latent.shape
+    _require(weight, "weight")
+    if weight.numel() != 6 * c or weight.shape[0] != 6 or not weight.is_contiguous():
+        raise KbnError(f"pose_head: weight must be a contiguous 6 x {c} (x 1 x 1) tensor, got {tuple(weight.shape)}")
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"pose_head: empty latent {tuple(latent.shape)}")
+    if out is None:
+        out = torch.empty((n, 4, 4), device=latent.device, dtype=torch.float32)
+    _require(out, "out", 3)
+    if tuple(out.shape) != (n, 4, 4) or not out.is_contiguous():
+        raise KbnError(f"pose_head: out must be a contiguous {(n, 4, 4)} tensor, got {tuple(out.shape)}")
+    if return_dof or dof_out is not None:
+        if dof_out is None:
+            dof_out = torch.empty((n, 6), device=latent.device, dtype=torch.float32)
+        _require(dof_out, "dof_out", 2)
+        if tuple(dof_out.shape) != (n, 6) or not dof_out.is_contiguous():
+            raise KbnError(f"pose_head: dof_out must be a contiguous {(n, 6)} tensor, got {tuple(dof_out.shape)}")
+    check(_launch("pose_head", 2.0 * n * h * w * c * 6,
+                  lambda: lib.kbn_pose_head_forward(ptr, bs, weight.data_ptr(), out.data_ptr(),
+                                                    dof_out.data_ptr() if dof_out is not None else None, n, c, h, w, _stream()),
+                  nbytes=4.0 * n * c * h * w), "kbn_pose_head_forward")
+    return (out, dof_out) if return_dof else out

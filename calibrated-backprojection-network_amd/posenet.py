@@ -1,0 +1,247 @@
+"""The reference's pose network, eval-mode forward, on the HIP kernels of csrc/posenet.hip.
+
+  reference class                                           here
+  networks.PoseEncoder        src/networks.py:536-671       PoseEncoder
+  networks.PoseDecoder        src/networks.py:1992-2075     PoseDecoder
+  posenet_model.PoseNetModel  src/posenet_model.py:21-206   PoseNetModel
+
+Same constructor arguments, `forward(image0, image1)` and `state_dict()` keys as the reference, so a `pose_model-*.pth`
+checkpoint loads with strict=True.  Inference only: BatchNorm2d uses its running statistics (a per-channel scale and shift in
+the conv's epilogue), there is no autograd and no CPU path.  Eight launches per forward: seven convs and the head.
+"""
+
+from __future__ import annotations
+
+from typing import List, Optional
+
+import torch
+
+from . import ops
+from ._lib import KbnError
+
+POSENET_FILTERS = (16, 32, 64, 128, 256, 256, 256)
+POSENET_KERNELS = (7, 5, 3, 3, 3, 3, 3)
+
+
+def _fused_slope(activation_func: str) -> Optional[float]:
+    """The reference's factory (src/net_utils.py:23-45: same substring tests, same order) narrowed to what the conv's epilogue
+    fuses: max(v, slope v)."""
+    if "linear" in activation_func:
+        return None
+    if "leaky_relu" in activation_func:
+        return 0.20
+    if "relu" in activation_func:
+        return 0.0
+    raise KbnError(f"PoseNet on the HIP path fuses leaky_relu, relu or linear into its convs, not {activation_func!r}")
+
+
+def _init_weight(weight, weight_initializer):
+    if weight_initializer == "kaiming_normal":
+        torch.nn.init.kaiming_normal_(weight)
+    elif weight_initializer == "xavier_normal":
+        torch.nn.init.xavier_normal_(weight)
+    elif weight_initializer == "xavier_uniform":
+        torch.nn.init.xavier_uniform_(weight)
+    elif weight_initializer != "kaiming_uniform":
+        raise ValueError("Unsupported weight initializer: {}".format(weight_initializer))
+
+
+def _state(*tensors):
+    return tuple((t.data_ptr(), t._version, t.device) for t in tensors)
+
+
+class _BareConv(torch.nn.Module):
+    """Holds `conv.weight` under the reference's key (its net_utils.Conv2d wraps a torch.nn.Conv2d named `conv`)."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size), requires_grad=False)
+        torch.nn.init.kaiming_uniform_(self.weight, a=5 ** 0.5)   # torch.nn.Conv2d's default: what 'kaiming_uniform' leaves in place
+
+
+class PoseConv2d(torch.nn.Module):
+    """net_utils.Conv2d(stride=2, use_batch_norm=True) in eval mode: conv, BatchNorm2d on its running statistics, activation, in
+    one launch (ops.conv2d_s2_affine).  The packed weight and the scale / shift vectors are cached and rebuilt when a parameter
+    or buffer changes (in place, replaced or moved), like modules._PackedWeight."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, weight_initializer, slope):
+        super().__init__()
+        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self.slope = slope
+        self.conv = _BareConv(in_channels, out_channels, kernel_size)
+        _init_weight(self.conv.weight, weight_initializer)
+        self.batch_norm = torch.nn.BatchNorm2d(out_channels)
+        for p in self.batch_norm.parameters():
+            p.requires_grad_(False)
+        self._wkey = self._akey = None
+        self._packed = self._scale = self._shift = None
+
+    def packed(self):
+        w = self.conv.weight
+        key = _state(w)
+        if key != self._wkey:
+            self._packed = ops.pack_conv2d_s2_affine_weight(w, out=self._packed)
+            self._wkey = key
+        return self._packed
+
+    def affine(self):
+        """scale = g * rsqrt(var + eps), shift = b - mean * scale (BatchNorm2d.eval()), fp32 on the weights' device."""
+        bn = self.batch_norm
+        key = _state(bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        if key != self._akey:
+            with torch.no_grad():
+                scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
+                shift = bn.bias - bn.running_mean * scale
+            if self._scale is not None and self._scale.device == scale.device:
+                self._scale.copy_(scale)
+                self._shift.copy_(shift)
+            else:
+                self._scale, self._shift = scale.contiguous(), shift.contiguous()
+            self._akey = key
+        return self._scale, self._shift
+
+    @torch.no_grad()
+    def run(self, inputs: List[torch.Tensor], out=None):
+        if self.training:
+            raise KbnError("PoseNet on the HIP path is inference only: BatchNorm2d runs on its running statistics (call eval())")
+        scale, shift = self.affine()
+        return ops.conv2d_s2_affine(inputs, self.packed(), scale, shift, self.out_channels, self.kernel_size,
+                                    negative_slope=self.slope, out=out)
+
+    def forward(self, x):
+        return self.run([x])
+
+
+class PoseEncoder(torch.nn.Module):
+    """reference networks.PoseEncoder (src/networks.py:536-671) with use_batch_norm=True, eval mode.  `forward(x)` takes the
+    6-channel concat like the reference; `encode([image0, image1])` reads the two images in place."""
+
+    def __init__(self, input_channels=6, n_filters=list(POSENET_FILTERS), weight_initializer="kaiming_uniform",
+                 activation_func="leaky_relu", use_batch_norm=True, use_instance_norm=False):
+        super().__init__()
+        if use_instance_norm or not use_batch_norm:
+            raise KbnError("PoseEncoder on the HIP path: use_batch_norm=True, use_instance_norm=False (what PoseNetModel builds)")
+        if len(n_filters) != len(POSENET_KERNELS):
+            raise KbnError(f"PoseEncoder has {len(POSENET_KERNELS)} layers, got {len(n_filters)} filter counts")
+        slope = _fused_slope(activation_func)
+        cin = input_channels
+        for i, (f, k) in enumerate(zip(n_filters, POSENET_KERNELS), 1):
+            setattr(self, f"conv{i}", PoseConv2d(cin, f, k, weight_initializer, slope))
+            cin = f
+        self.eval()
+
+    def layers(self):
+        return [getattr(self, f"conv{i}") for i in range(1, len(POSENET_KERNELS) + 1)]
+
+    def encode(self, inputs: List[torch.Tensor], return_layers: bool = False):
+        outs = []
+        x = list(inputs)
+        for layer in self.layers():
+            outs.append(layer.run(x))
+            x = [outs[-1]]
+        return outs if return_layers else outs[-1]
+
+    def forward(self, x):
+        return self.encode([x]), None
+
+
+class _DecoderConv(torch.nn.Module):
+    def __init__(self, in_channels, weight_initializer):
+        super().__init__()
+        self.conv = _BareConv(in_channels, 6, 1)
+        _init_weight(self.conv.weight, weight_initializer)
+
+
+class PoseDecoder(torch.nn.Module):
+    """reference networks.PoseDecoder (src/networks.py:1992-2075) with n_filters=[]: 1 x 1 conv to 6 channels, mean over H W,
+    x 0.01, pose_matrix -- one launch (ops.pose_head)."""
+
+    def __init__(self, rotation_parameterization="axis", input_channels=256, n_filters=[], weight_initializer="kaiming_uniform",
+                 activation_func="leaky_relu", use_batch_norm=False, use_instance_norm=False):
+        super().__init__()
+        if rotation_parameterization != "axis":
+            raise KbnError(f"PoseDecoder: rotation_parameterization 'axis' only (the reference's pose_matrix knows no other), got "
+                           f"{rotation_parameterization!r}")
+        if len(n_filters) or use_batch_norm or use_instance_norm:
+            raise KbnError("PoseDecoder on the HIP path has no hidden layers (n_filters=[]: the decoder of encoder_type='posenet')")
+        self.rotation_parameterization = rotation_parameterization
+        self.conv = _DecoderConv(input_channels, weight_initializer)
+        self.eval()
+
+    @torch.no_grad()
+    def forward(self, x, return_dof: bool = False):
+        return ops.pose_head(x, self.conv.conv.weight, return_dof=return_dof)
+
+
+class PoseNetModel(object):
+    """Inference counterpart of reference `PoseNetModel` (src/posenet_model.py:21-206): same constructor arguments and
+    `forward(image0, image1)` -> N x 4 x 4, the pose KBNetModel.compute_loss takes as pose01 / pose02."""
+
+    def __init__(self, encoder_type="posenet", rotation_parameterization="axis", weight_initializer="xavier_normal",
+                 activation_func="leaky_relu", device=torch.device("cuda"), n_filters=POSENET_FILTERS):
+        if encoder_type in ("resnet18", "resnet34"):
+            raise KbnError(f"PoseNetModel on the HIP path implements encoder_type='posenet' only, not {encoder_type!r} "
+                           "(the ResNet pose encoders are out of scope)")
+        if encoder_type != "posenet":
+            raise ValueError("Unsupported PoseNet encoder type: {}".format(encoder_type))
+        self.device = device
+        self.encoder = PoseEncoder(input_channels=6, n_filters=list(n_filters), weight_initializer=weight_initializer,
+                                   activation_func=activation_func, use_batch_norm=True)
+        self.decoder = PoseDecoder(rotation_parameterization=rotation_parameterization, weight_initializer=weight_initializer,
+                                   input_channels=list(n_filters)[-1])
+        self.data_parallel()
+        self.to(device)
+        self.eval()
+
+    @torch.no_grad()
+    def forward(self, image0, image1, return_all: bool = False):
+        """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone."""
+        if not isinstance(image0, torch.Tensor) or not isinstance(image1, torch.Tensor) or image0.dim() != 4 or \
+                image0.shape[1] != 3 or image0.shape != image1.shape:
+            raise KbnError("PoseNetModel.forward: image0 and image1 must be N x 3 x H x W tensors of one shape")
+        layers = self.encoder.encode([image0, image1], return_layers=True)
+        pose, dof = self.decoder(layers[-1], return_dof=True)
+        return (pose, dof, layers) if return_all else pose
+
+    def modules(self):
+        return (self.encoder, self.decoder)
+
+    def parameters(self):
+        return list(self.encoder.parameters()) + list(self.decoder.parameters())
+
+    def train(self):
+        raise KbnError("the HIP path is inference only")
+
+    def eval(self):
+        for m in self.modules():
+            m.eval()
+
+    def to(self, device):
+        for m in self.modules():
+            m.to(device)
+        self.device = device
+
+    def data_parallel(self):
+        """A no-op, as KBNetModel.data_parallel: one process drives one GPU; checkpoints still carry the `module.` prefix."""
+        return self
+
+    def load_state_dicts(self, sd_encoder, sd_decoder):
+        """Accepts keys with or without the DataParallel `module.` prefix."""
+        for m, sd in zip(self.modules(), (sd_encoder, sd_decoder)):
+            sd = {(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()}
+            m.load_state_dict(sd, strict=True)
+
+    def restore_model(self, checkpoint_path, optimizer=None):
+        """Loads a reference checkpoint (reference src/posenet_model.py:174-198)."""
+        ckpt = torch.load(checkpoint_path, map_location=self.device)
+        self.load_state_dicts(ckpt["encoder_state_dict"], ckpt["decoder_state_dict"])
+        return ckpt.get("train_step", 0), optimizer
+
+    def save_model(self, checkpoint_path, step=0, optimizer=None):
+        """Writes the reference's checkpoint layout (src/posenet_model.py:150-172), keys prefixed with `module.` like its
+        DataParallel-wrapped modules produce."""
+        pref = lambda sd: {"module." + k: v for k, v in sd.items()}
+        torch.save({"train_step": step,
+                    "optimizer_state_dict": optimizer.state_dict() if optimizer is not None else {},
+                    "encoder_state_dict": pref(self.encoder.state_dict()),
+                    "decoder_state_dict": pref(self.decoder.state_dict())}, checkpoint_path)

@@ -170,3 +170,41 @@ def make_triplet(n: int, height: int, width: int, kind: str = "kitti", seed: int
         poses.append(p)
     arrays = images + [depth, sparse, validity, k] + poses
     return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in arrays)
+
+
+POSENET_KERNELS = (7, 5, 3, 3, 3, 3, 3)
+
+
+def make_posenet_weights(filters=(16, 32, 64, 128, 256, 256, 256), seed: int = 0, gain: float = 0.5):
+    """Two dicts (encoder, decoder) keyed like the state_dicts of the reference's PoseEncoder(use_batch_norm=True) /
+    PoseDecoder(n_filters=[]) (src/networks.py:536-671, 1992-2075; no `module.` prefix).  Conv weights: xavier normal (x gain).
+    BatchNorm2d: gamma uniform in [0.5, 1.5], beta and running mean 0.2 N(0, 1), running variance uniform in [0.25, 1.75] with
+    TWO channels of every layer at 1e-3 -- there eps = 1e-5 is 1 % of the variance, so a forward that drops it is 0.5 % off in
+    those channels, far outside any parity gate.  Those channels also amplify 30-fold, layer after layer; gain = 0.5 keeps
+    the activations O(1) to O(100) and the pose vector between 1e-3 and a few radians / metres at both the full and a narrow width."""
+    enc, dec = {}, {}
+    cin = 6
+    for i, (f, k) in enumerate(zip(filters, POSENET_KERNELS), 1):
+        enc[f"conv{i}.conv.weight"] = gain * _xavier_normal(f"pose/conv{i}.conv.weight", (f, cin, k, k), seed)
+        g = _rng((seed << 32) ^ zlib.crc32(f"pose/conv{i}.batch_norm".encode()))
+        var = 0.25 + 1.5 * g.random(f)
+        var[g.choice(f, size=min(2, f), replace=False)] = 1e-3
+        enc[f"conv{i}.batch_norm.weight"] = torch.from_numpy((0.5 + g.random(f)).astype(np.float32))
+        enc[f"conv{i}.batch_norm.bias"] = torch.from_numpy((0.2 * g.standard_normal(f)).astype(np.float32))
+        enc[f"conv{i}.batch_norm.running_mean"] = torch.from_numpy((0.2 * g.standard_normal(f)).astype(np.float32))
+        enc[f"conv{i}.batch_norm.running_var"] = torch.from_numpy(var.astype(np.float32))
+        enc[f"conv{i}.batch_norm.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+        cin = f
+    dec["conv.conv.weight"] = gain * _xavier_normal("pose/conv.conv.weight", (6, cin, 1, 1), seed)
+    return enc, dec
+
+
+def make_image_pair(n: int, height: int, width: int, seed: int = 1, radius: int = 2):
+    """(image0, image1) N x 3 x H x W in [0, 1], CPU fp32: band-limited noise, image1 sharing 80 % of image0's content two
+    pixels to the side -- every frame its own images."""
+    g = _rng(seed)
+    scene = _smooth_field(g, (n, 3), height, width + 2, radius)
+    own = _smooth_field(g, (n, 3), height, width, radius)
+    image0 = scene[..., :, :width]
+    image1 = 0.8 * scene[..., :, 2:] + 0.2 * own
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in (image0, image1))

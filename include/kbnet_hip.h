@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define KBN_ABI_VERSION 8
+#define KBN_ABI_VERSION 9
 
 typedef void* kbn_stream_t; /* hipStream_t */
 
@@ -575,6 +575,37 @@ int kbn_photometric_loss_forward(const float* image0, const float* image1, const
                                  const float* pose01, const float* pose02, double* sums,
                                  float* image01, float* image02, int n, int height, int width,
                                  kbn_stream_t stream);
+
+/* ------------------------------------------------- pose network (eval mode) ----
+ * PoseNetModel.forward                                 reference src/posenet_model.py:95-112
+ *   networks.PoseEncoder                               reference src/networks.py:536-671
+ *     seven net_utils.Conv2d (src/net_utils.py:51-141): bias-free conv, kernel 7, 5, 3, 3, 3, 3, 3, stride 2, padding k / 2,
+ *     BatchNorm2d (eval: running statistics), LeakyReLU(0.20)
+ *   networks.PoseDecoder                               reference src/networks.py:1992-2075
+ *     1 x 1 conv to 6 channels, mean over H W, x 0.01, net_utils.pose_matrix (src/net_utils.py:1493-1595)
+ *
+ * kbn_conv2d_s2_affine_forward: out[n, o, oy, ox] = act((sum_c,ky,kx W[o, c, ky, kx] in[n, c, 2 oy + ky - k/2, 2 ox + kx - k/2])
+ * * scale[o] + shift[o]), act = max(v, slope v) when apply_activation.  `in` is the channel concat of one or two
+ * KBN_SRC_TENSOR sources of in_height x in_width (the two images are read in place, src/posenet_model.py:109); taps outside
+ * the image are zero.  kernel_size in {3, 5, 7}; any channel counts.  scale / shift: out_channels floats each -- BatchNorm2d in
+ * eval mode is scale = g / sqrt(var + eps), shift = b - mean * scale; the scale is applied to the finished sum, not folded
+ * into the weights.  out: out_channels x ceil(in_h / 2) x ceil(in_w / 2) per frame, frames out_batch_stride elements apart.
+ * Every output pixel is a function of its frame and the weights alone. */
+size_t kbn_conv2d_s2_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
+int kbn_conv2d_s2_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
+                                     int kernel_size, kbn_stream_t stream);
+int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src, const float* packed_weight, const float* scale,
+                                 const float* shift, float* out, long long out_batch_stride, int n, int out_channels,
+                                 int kernel_size, int in_height, int in_width, int apply_activation,
+                                 float negative_slope, kbn_stream_t stream);
+
+/* PoseDecoder.forward with n_filters = [] (reference src/networks.py:2067-2075) in one launch, one workgroup per frame:
+ * latent N x channels x height x width (frames latent_batch_stride elements apart), weight 6 x channels (the 1 x 1 conv) ->
+ * pose N x 16 (row-major 4 x 4: rotation from the axis-angle dof[0:3], translation dof[3:6], last row 0 0 0 1) and, when
+ * `dof` is not NULL, the N x 6 vector 0.01 * mean(conv(latent)) itself.  The spatial sums run in a fixed order without
+ * atomics, and the mean is taken before the 6 x channels product (the conv of the mean is the mean of the conv). */
+int kbn_pose_head_forward(const float* latent, long long latent_batch_stride, const float* weight, float* pose,
+                          float* dof, int n, int channels, int height, int width, kbn_stream_t stream);
 
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:

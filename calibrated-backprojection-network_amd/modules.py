@@ -70,7 +70,7 @@ def _post(act) -> Optional[str]:
     return None
 
 
-def _finish(layer, out, out_absmax, stats=None):
+def _finish(layer, out, out_absmax):
     """The activation pass of a layer whose activation the kernels do not fuse (ELU, sigmoid); it folds max |out| per frame into the
     tensor's slot -- the conv in front of it was given none -- so that split-operand convs downstream place their fp16 windows on
     the activated values."""
@@ -92,85 +92,33 @@ def _init_weight(weight, weight_initializer):
         raise ValueError("Unsupported weight initializer: {}".format(weight_initializer))
 
 
-class _PackedWeight:
-    """Caches the MFMA-ordered copy of a conv weight; re-packs when the parameter is
-    modified in place (version bump), replaced or moved.  A re-pack of an unchanged shape on the
-    same device goes INTO the existing blob, so device pointers recorded in a captured HIP graph
-    stay valid (GraphedForward re-packs before replaying when it sees a parameter change)."""
+class _PackedBlob:
+    """Caches the blob a packer (`pack(*weights, out=None, **opts)`, one of ops.pack_*_weight) makes of one or more weights; re-packs
+    when a weight is modified in place (version bump), replaced or moved, or when an option changes.  A re-pack goes INTO the
+    existing blob (`out=`: same size, same device), so device pointers recorded in a captured HIP graph stay valid
+    (GraphedForward re-packs before replaying when it sees a parameter change: KBNetModel.refresh_packed finds every instance
+    that is an attribute of a sub-module, see packed_blobs)."""
 
-    def __init__(self):
-        self._key = None
-        self._packed = None
-        self._args = None
+    def __init__(self, pack):
+        self._pack = pack
+        self._key = self._blob = self._args = None
 
-    def get(self, weight: torch.Tensor, stride: int, up2x: bool = False) -> torch.Tensor:
-        key = (weight.data_ptr(), weight._version, weight.device, stride, up2x)
+    def get(self, *weights, **opts):
+        key = ([(w.data_ptr(), w._version, w.device) for w in weights], opts)
         if key != self._key:
-            if up2x == "split":   # fp32-grade products on the 16-bit matrix core (ops.conv3x3_split)
-                self._packed = ops.pack_conv3x3_split_weight(weight, out=self._packed, stride=stride)
-            elif up2x == "split_up":   # the same for the folded nearest-2x up-conv
-                self._packed = ops.pack_conv3x3_split_weight(weight, out=self._packed, folded_up2x=True)
-            elif up2x == "split_up_t":   # ... and for the transposed conv on those kernels (TransposeConv2d)
-                self._packed = ops.pack_conv3x3_split_weight(weight, out=self._packed, folded_up2x=True, transposed=True)
-            elif up2x == "up2x_t":       # the transposed conv on the fp32 four-phase kernels
-                self._packed = ops.pack_upconv2x_weight(weight, out=self._packed, transposed=True)
-            elif isinstance(up2x, tuple) and up2x[0] == "split_1x1s2":   # conv_fused of the KB block; up2x[1] = first xyz channel
-                self._packed = ops.pack_conv1x1s2_split_weight(weight, up2x[1], out=self._packed)
-            else:
-                self._packed = (ops.pack_upconv2x_weight(weight, out=self._packed) if up2x
-                                else ops.pack_conv_weight(weight, stride, out=self._packed))
-            self._key = key
-            self._args = (stride, up2x)
-        return self._packed
-
-    def refresh(self, weight: torch.Tensor):
-        """Re-packs if (and only if) this blob has been built before and the weight changed since."""
-        if self._packed is not None:
-            self.get(weight, *self._args)
-
-
-class _PackedTail:
-    """The blob of ops.conv_tail, rebuilt (in place when possible) when the weight changes."""
-
-    def __init__(self):
-        self._key = None
-        self._packed = None
-        self._w = None
-
-    def get(self, w):
-        key = (w.data_ptr(), w._version, w.device)
-        if key != self._key:
-            self._packed = ops.pack_conv_tail_weight(w, out=self._packed)
-            self._key = key
-            self._w = w
-        return self._packed
+            self._blob = self._pack(*weights, out=self._blob, **opts)
+            self._key, self._args = key, (weights, opts)
+        return self._blob
 
     def refresh(self):
-        if self._packed is not None:
-            self.get(self._w)
+        """Re-packs if (and only if) this blob has been built before and a weight changed since."""
+        if self._blob is not None:
+            self.get(*self._args[0], **self._args[1])
 
 
-class _PackedFront:
-    """The blob of ops.kb1_front / ops.kb1_depth_front / ops.s2d_depth_front (`pack`), rebuilt (in place when possible) when one
-    of its weights changes."""
-
-    def __init__(self, pack=None):
-        self._key = None
-        self._packed = None
-        self._args = None
-        self._pack = pack or ops.pack_kb1_front_weight
-
-    def get(self, *ws):
-        key = tuple((w.data_ptr(), w._version, w.device) for w in ws)
-        if key != self._key:
-            self._packed = self._pack(*ws, out=self._packed)
-            self._key = key
-            self._args = ws
-        return self._packed
-
-    def refresh(self):
-        if self._packed is not None:
-            self.get(*self._args)
+def packed_blobs(model):
+    """Every _PackedBlob that is an instance attribute of a sub-module of `model` (a KBNetModel / PoseNetModel)."""
+    return [v for top in model.modules() for sub in top.modules() for v in vars(sub).values() if isinstance(v, _PackedBlob)]
 
 
 # ------------------------------------------------------------------------ layers
@@ -200,8 +148,7 @@ def _run_split(layer, weight, srcs, n, h, w, out=None, up2x=False, out_absmax=No
             out.absmax = out_absmax
     elif out is None:
         out = torch.empty((n, layer.out_channels, h, w), device=dev, dtype=torch.float32)
-    packed = (layer._packed_split_up.get(weight, 1, up2x="split_up_t" if transposed else "split_up") if up2x
-              else layer._packed_split.get(weight, layer.stride, up2x="split"))
+    packed = layer._split_blob(up2x)
     # the latency form (KBNetModel.set_latency_mode): a launch too small for the chip spreads every tile's K loop over several workgroups
     ks = 1
     if getattr(layer, "latency", 0) and not pair_out and all(s.kind == _lib.KBN_SRC_TENSOR for s in srcs):
@@ -234,10 +181,10 @@ class Conv2d(torch.nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self._slope = _slope(activation_func)
         self._post = _post(activation_func)
-        self._packed = _PackedWeight()
-        self._packed_split = _PackedWeight()
-        self._packed_split_up = _PackedWeight()
-        self._packed_split_1x1 = _PackedWeight()
+        self._packed = _PackedBlob(ops.pack_conv_weight)
+        self._packed_split = _PackedBlob(ops.pack_conv3x3_split_weight)      # fp32-grade products on the 16-bit matrix core (ops.conv3x3_split)
+        self._packed_split_up = _PackedBlob(ops.pack_conv3x3_split_weight)   # the same for the folded nearest-2x up-conv
+        self._packed_split_1x1 = _PackedBlob(ops.pack_conv1x1s2_split_weight)   # conv_fused of the KB block
         # conv_fused on split operands from this width on: KB3 / KB4 (192 / 384 filters: 239 vs 285 and 152 vs 253 us per 32
         # KITTI frames); at KB2's 96 filters the layer is bound by its stride-2 HBM reads either way (365 vs 342 us)
         self.split_fused_min_filters = 192
@@ -260,6 +207,12 @@ class Conv2d(torch.nn.Module):
                 s.absmax = slot.data_ptr()
                 s._keep = (s._keep[0], slot)
         return srcs
+
+    def _split_blob(self, up2x):
+        """The blob ops.conv3x3_split reads for this layer; `up2x`: as the folded nearest-2x up-conv."""
+        if up2x:
+            return self._packed_split_up.get(self.conv.weight, folded_up2x=True)
+        return self._packed_split.get(self.conv.weight, stride=self.stride)
 
     def run_split(self, srcs, n, h, w, out=None, up2x=False, out_absmax=None, stats=None, pair_out=False):
         """3x3 stride-1 conv with two-term fp16 splits of both operands (ops.conv3x3_split, fp32-grade results); `h` x `w`
@@ -285,12 +238,12 @@ class Conv2d(torch.nn.Module):
             image, amax_image = image.sub, image.absmax
         srcs = [ops.tensor_src(image, "image", amax_image)] + ([] if fused is None else [ops.tensor_src(fused, "fused", amax_fused)])
         srcs = self._with_slots(srcs, n, image.device, stats)
-        packed = self._packed_split_1x1.get(self.conv.weight, 2, up2x=("split_1x1s2", ci))
+        packed = self._packed_split_1x1.get(self.conv.weight, xyz_offset=ci)   # (the first xyz channel)
         return ops.conv1x1s2_split(srcs, packed, xyz, n, self.out_channels, h, w, out, negative_slope=self._slope,
                                    out_absmax=out_absmax)
 
     def packed(self):
-        return self._packed.get(self.conv.weight, self.stride)
+        return self._packed.get(self.conv.weight, stride=self.stride)
 
     def run(self, srcs, n, in_h, in_w, out=None, resize=False, out_absmax=None, stats=None):
         """`out_absmax`: slot (ops.ActStats) that receives max |out| per frame; `stats`: where slots for unmeasured
@@ -299,25 +252,16 @@ class Conv2d(torch.nn.Module):
         if cin != self.in_channels:   # the packed blob carries no size: a wrong count would read past the weight panel
             raise KbnError(f"expected {self.in_channels} input channels in total, got {cin}")
         oh, ow = -(-in_h // self.stride), -(-in_w // self.stride)
-        if self._post is not None:   # ELU / sigmoid: the conv without activation (split operands where the shape qualifies), then the activation in place
-            if not resize:
-                res = self.run_split(srcs, n, oh, ow, out=out, out_absmax=out_absmax, stats=stats)   # (_run_split finishes the layer)
-                if res is not None:
-                    return res
-            if out is None:
-                out = torch.empty((n, self.out_channels, oh, ow), device=self.conv.weight.device, dtype=torch.float32)
-            res = ops.conv2d(srcs, self.packed(), n, self.out_channels, self.kernel_size, self.stride, in_h, in_w, out,
-                             resize=resize, negative_slope=None)
-            return _finish(self, res, out_absmax, stats)
         if not resize:
-            res = self.run_split(srcs, n, oh, ow, out=out, out_absmax=out_absmax, stats=stats)
+            res = self.run_split(srcs, n, oh, ow, out=out, out_absmax=out_absmax, stats=stats)   # (_run_split finishes the layer)
             if res is not None:
                 return res
         if out is None:
-            out = torch.empty((n, self.out_channels, oh, ow), device=self.conv.weight.device,
-                              dtype=torch.float32)
-        return ops.conv2d(srcs, self.packed(), n, self.out_channels, self.kernel_size, self.stride,
-                          in_h, in_w, out, resize=resize, negative_slope=self._slope, out_absmax=out_absmax)
+            out = torch.empty((n, self.out_channels, oh, ow), device=self.conv.weight.device, dtype=torch.float32)
+        # ELU / sigmoid (_post): the conv without activation and without the slot, then the activation in place (_finish fills the slot)
+        res = ops.conv2d(srcs, self.packed(), n, self.out_channels, self.kernel_size, self.stride, in_h, in_w, out,
+                         resize=resize, negative_slope=self._slope, out_absmax=None if self._post else out_absmax)
+        return _finish(self, res, out_absmax)
 
     def forward(self, x):
         if x.shape[1] != self.in_channels:
@@ -405,7 +349,7 @@ class UpConv2d(torch.nn.Module):
         self.conv = Conv2d(in_channels, out_channels, kernel_size=kernel_size, stride=1,
                            weight_initializer=weight_initializer, activation_func=activation_func,
                            use_batch_norm=use_batch_norm, use_instance_norm=use_instance_norm)
-        self._packed_up2x = _PackedWeight()
+        self._packed_up2x = _PackedBlob(ops.pack_upconv2x_weight)
         self.split_up = True    # folded 16-product form on split operands (ops.conv3x3_split(folded_up2x=True))
 
     out_channels = property(lambda self: self.conv.out_channels)
@@ -437,9 +381,9 @@ class UpConv2d(torch.nn.Module):
                     return res
             # exact 2x: four 2x2 phase convs on the low-res input (4/9 of the MACs)
             out = torch.empty((n, self.conv.out_channels, oh, ow), device=x.device, dtype=torch.float32)
-            res = ops.upconv2x(x, self._packed_up2x.get(self.conv.conv.weight, 1, up2x=True), self.conv.out_channels, out,
+            res = ops.upconv2x(x, self._packed_up2x.get(self.conv.conv.weight), self.conv.out_channels, out,
                                self.conv._slope, out_absmax=None if self.conv._post else out_absmax)
-            return _finish(self.conv, res, out_absmax, stats)
+            return _finish(self.conv, res, out_absmax)
         return self.conv.run([ops.tensor_src(x, "x", amax)], n, oh, ow, resize=True, out_absmax=out_absmax, stats=stats)
 
 
@@ -465,11 +409,13 @@ class TransposeConv2d(torch.nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self._slope = _slope(activation_func)
         self._post = _post(activation_func)
-        self._packed_split = None                         # (never used: the layer has no plain-conv form)
-        self._packed_split_up = _PackedWeight()
-        self._packed_up2x = _PackedWeight()
+        self._packed_split_up = _PackedBlob(ops.pack_conv3x3_split_weight)   # the folded up-conv kernels on the layer's own taps
+        self._packed_up2x = _PackedBlob(ops.pack_upconv2x_weight)            # the fp32 four-phase kernels
         self.split = True
         self.split_narrow_up = True
+
+    def _split_blob(self, up2x=True):
+        return self._packed_split_up.get(self.deconv.weight, folded_up2x=True, transposed=True)
 
     def forward(self, x, shape=None, amax=None, out_absmax=None, stats=None, pair_out=False):
         """`shape` is accepted and ignored, as in the reference's DecoderBlock (:1468-1469: the transposed conv fixes the size).
@@ -488,9 +434,9 @@ class TransposeConv2d(torch.nn.Module):
         if res is not None or pair_in or pair_out:
             return res
         out = torch.empty((n, self.out_channels, oh, ow), device=x.device, dtype=torch.float32)
-        res = ops.upconv2x(x, self._packed_up2x.get(w_t, 1, up2x="up2x_t"), self.out_channels, out, self._slope,
+        res = ops.upconv2x(x, self._packed_up2x.get(w_t, transposed=True), self.out_channels, out, self._slope,
                            out_absmax=None if self._post else out_absmax, transposed=True)
-        return _finish(self, res, out_absmax, stats)
+        return _finish(self, res, out_absmax)
 
 
 class VGGNetBlock(torch.nn.Module):
@@ -864,12 +810,12 @@ class KBNetEncoder(torch.nn.Module):
         self.front = True
         # OFF by default (the reference computes it): do not launch conv_image of KB level 3, whose output nothing reads
         self.skip_unused_image = False
-        self._packed_front = _PackedFront()
-        self._packed_front_next = _PackedFront(lambda w, out=None: ops.pack_kb1_front_next_weight(w, fi[0], out=out))
-        self._packed_depth_front = _PackedFront(ops.pack_kb1_depth_front_weight)
+        self._packed_front = _PackedBlob(ops.pack_kb1_front_weight)
+        self._packed_front_next = _PackedBlob(ops.pack_kb1_front_next_weight)
+        self._packed_depth_front = _PackedBlob(ops.pack_kb1_depth_front_weight)
         # the blob of the on-chip S2D stage (`fuse_s2d`): KBNetModel.forward hands encode() the S2D module and its input instead of the
         # S2D tensor, and _front decides where the layer runs
-        self._packed_s2d_front = _PackedFront(lambda a, b, c, d, out=None: ops.pack_s2d_depth_front_weight([a, b, c], d, out=out))
+        self._packed_s2d_front = _PackedBlob(lambda *ws, out=None: ops.pack_s2d_depth_front_weight(ws[:-1], ws[-1], out=out))
 
     def _front(self, image, depth, kinv, stats, s2d=None, kinv_next=None):
         """Level 0 with conv0_image / conv0_depth fused in (their outputs stay on the CU): (skip, conv_image, conv_depth,
@@ -936,7 +882,7 @@ class KBNetEncoder(torch.nn.Module):
                 and blk2.conv_image.conv_block[0].split
                 and blk2.conv_fused.in_channels == ci.out_channels + 3 + cf.out_channels and blk2.proj_depth._slope is not None
                 and ops.kb1_front_next_supported(image.shape[1], c0.out_channels, ci.out_channels, blk2.n_filter_fused, h, w, c0._slope)):
-            packed_n = self._packed_front_next.get(blk2.conv_fused.conv.weight)
+            packed_n = self._packed_front_next.get(blk2.conv_fused.conv.weight, image_channels=fi[0])
             if packed_n is not None:
                 h2, w2 = (oh + 1) // 2, (ow + 1) // 2
                 skip2 = torch.empty((n, ff[1] + fd[1], h2, w2), device=dev, dtype=torch.float32)
@@ -1112,7 +1058,7 @@ class MultiScaleDecoder(torch.nn.Module):
                                              deconv_type=deconv_type))
             cin = n_filters[i]
         self.output0 = Conv2d(n_filters[4], output_channels, 3, 1, weight_initializer, None)
-        self._packed_tail = _PackedTail()
+        self._packed_tail = _PackedBlob(ops.pack_conv_tail_weight)
 
     def features(self, x, skips, shape):
         """Everything up to (not including) output0."""
@@ -1474,25 +1420,8 @@ class KBNetModel(object):
 
     def refresh_packed(self):
         """Re-packs (in place) the MFMA-ordered blobs of weights that changed since they were packed."""
-        for m in self.modules():
-            for sub in m.modules():
-                if isinstance(sub, Conv2d):
-                    sub._packed.refresh(sub.conv.weight)
-                    sub._packed_split.refresh(sub.conv.weight)
-                    sub._packed_split_up.refresh(sub.conv.weight)
-                    sub._packed_split_1x1.refresh(sub.conv.weight)
-                elif isinstance(sub, UpConv2d):
-                    sub._packed_up2x.refresh(sub.conv.conv.weight)
-                elif isinstance(sub, TransposeConv2d):
-                    sub._packed_up2x.refresh(sub.deconv.weight)
-                    sub._packed_split_up.refresh(sub.deconv.weight)
-                elif isinstance(sub, MultiScaleDecoder):
-                    sub._packed_tail.refresh()
-                elif isinstance(sub, KBNetEncoder):
-                    sub._packed_front.refresh()
-                    sub._packed_front_next.refresh()
-                    sub._packed_depth_front.refresh()
-                    sub._packed_s2d_front.refresh()
+        for blob in packed_blobs(self):
+            blob.refresh()
 
     # -- nn.Module-like plumbing the reference driver uses ------------------------
     def modules(self):

@@ -95,6 +95,23 @@ def _launch(name: str, work: float, fn, executed=None, pipe: Optional[str] = Non
     return status
 
 
+def _launched(what: str, name: str, work: float, fn, **record) -> bool:
+    """_launch for an entry point that may decline the problem: False on KBN_ERR_UNSUPPORTED, with the profile record dropped (the
+    wrapper returns None and whatever the caller launches instead records itself); any other status goes through `check`."""
+    status = _launch(name, work, fn, **record)
+    if status == _lib.KBN_ERR_UNSUPPORTED:
+        if PROFILE is not None:
+            PROFILE.pop()
+        return False
+    check(status, what)
+    return True
+
+
+def _act_args(negative_slope: Optional[float]):
+    """(has_activation, negative_slope) as the entry points take max(v, slope v); None: no activation."""
+    return (0, 0.0) if negative_slope is None else (1, float(negative_slope))
+
+
 def _src_bytes(srcs, n: int) -> float:
     """fp32-equivalent bytes the tensor / pair sources of a conv hold (4 B per value in both formats)."""
     total = 0
@@ -155,6 +172,24 @@ def _require(t: torch.Tensor, name: str, ndim: Optional[int] = None):
         raise KbnError(f"{name}: expected float32, got {t.dtype}")
     if ndim is not None and t.dim() != ndim:
         raise KbnError(f"{name}: expected {ndim} dims, got {tuple(t.shape)}")
+
+
+def _weight(t: torch.Tensor, name: str = "weight") -> torch.Tensor:
+    """A 4-d fp32 parameter as the dense device tensor the C side reads."""
+    w = t.detach().contiguous()
+    _require(w, name, 4)
+    return w
+
+
+def _out_tensor(out: Optional[torch.Tensor], shape, device, name: str = "out", planes: bool = False) -> torch.Tensor:
+    """A new fp32 tensor of `shape`, or the given `out` once it is known to be an fp32 device tensor of that shape, contiguous
+    (`planes`: dense frames suffice, e.g. a channel slice; the caller takes its pointer with _planes)."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    _require(out, name, len(shape))
+    if tuple(out.shape) != tuple(shape) or not (planes or out.is_contiguous()):
+        raise KbnError(f"{name} has shape {tuple(out.shape)}, expected {'' if planes else 'a contiguous '}{tuple(shape)}")
+    return out
 
 
 def _planes(t: torch.Tensor, name: str):
@@ -238,20 +273,14 @@ def s2d_forward(x, w_pool_convs: List[torch.Tensor], w_conv, min_pool_sizes, max
     _require(x, "x", 4)
     x = x.contiguous()
     n, cin, h, w = x.shape
-    ws = [wt.detach().contiguous() for wt in w_pool_convs]
-    for i, wt in enumerate(ws):
-        _require(wt, f"pool_convs.{i}.weight", 4)
-    wc = w_conv.detach().contiguous()
-    _require(wc, "conv.weight", 4)
+    ws = [_weight(wt, f"pool_convs.{i}.weight") for i, wt in enumerate(w_pool_convs)]
+    wc = _weight(w_conv, "conv.weight")
     nf = wc.shape[0]
     mins = [int(s) for s in min_pool_sizes if s > 1]
     maxs = [int(s) for s in max_pool_sizes if s > 1]
     if ws[0].shape[1] != len(mins) + len(maxs) or wc.shape[1] != nf + cin:
         raise KbnError("S2D weight shapes do not match the pool lists / input channels")
-    if out is None:
-        out = torch.empty((n, nf, h, w), device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != (n, nf, h, w) or not out.is_contiguous():
-        raise KbnError("s2d_forward: `out` must be a contiguous N x n_filter x H x W tensor")
+    out = _out_tensor(out, (n, nf, h, w), x.device, "s2d_forward: out")
     wptrs = (C.c_void_p * len(ws))(*[wt.data_ptr() for wt in ws])
     amin, amax = _int_array(mins), _int_array(maxs)
     # (work = the layer's multiply-adds x 2: nothing is skipped or padded, so executed = algorithmic; its bytes travel as `nbytes`)
@@ -305,29 +334,31 @@ def camera_coordinates(kinv, height: int, width: int):
 
 
 # --------------------------------------------------------------------------- conv2d
-def _reusable(blob, nfloats, like):
-    return (blob is not None and blob.numel() == nfloats and blob.device == like.device and
-            blob.dtype == torch.float32 and blob.is_contiguous())
+def _pack_into(out: Optional[torch.Tensor], nbytes: int, like: torch.Tensor, pack, what: str) -> torch.Tensor:
+    """The blob of `nbytes` that `pack(ptr)` -- a C packer, returning its status -- fills: `out` when that is a blob of this size on
+    `like`'s device (a re-pack in place: the device pointer a captured graph holds stays valid), otherwise a new one."""
+    n = nbytes // 4
+    if out is None or out.numel() != n or out.device != like.device or out.dtype != torch.float32 or not out.is_contiguous():
+        out = torch.empty(n, device=like.device, dtype=torch.float32)
+    check(pack(out.data_ptr()), what)
+    return out
 
 
 @_on_tensor_device
 def pack_conv_weight(weight: torch.Tensor, stride: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """OIHW -> MFMA fragment order for a conv of this stride (done once per weight; see
-    _PackedWeight in modules.py).  `out`: an existing blob of the right size to re-pack into (keeps
+    _PackedBlob in modules.py).  `out`: an existing blob of the right size to re-pack into (keeps
     the device pointer a captured graph holds valid)."""
     lib = _lib.load()
-    w = weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(weight)
     oc, cin, kh, kw = w.shape
     if kh != kw:
         raise KbnError("square kernels only")
     nbytes = lib.kbn_conv2d_packed_weight_bytes(oc, cin, kh, stride)
     if nbytes == 0:
         raise KbnError(f"unsupported conv weight shape {tuple(w.shape)}")
-    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    check(lib.kbn_conv2d_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, kh, stride, _stream()),
-          "kbn_conv2d_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_pack_weight(w.data_ptr(), p, oc, cin, kh, stride, _stream()),
+                      "kbn_conv2d_pack_weight")
 
 
 def tensor_src(t: torch.Tensor, name="src", absmax: Optional[torch.Tensor] = None) -> ConvSrc:
@@ -464,9 +495,7 @@ def conv2d(srcs: List[ConvSrc], packed_weight: torch.Tensor, n: int, out_channel
                   lambda: lib.kbn_conv2d_forward(arr, len(srcs), packed_weight.data_ptr(), optr, obs, n,
                                                  out_channels, kernel_size, stride, in_height, in_width,
                                                  _lib.KBN_RESIZE_NEAREST if resize else _lib.KBN_RESIZE_NONE,
-                                                 0 if negative_slope is None else 1,
-                                                 0.0 if negative_slope is None else float(negative_slope),
-                                                 _slot_ptr(out_absmax, n), _stream()),
+                                                 *_act_args(negative_slope), _slot_ptr(out_absmax, n), _stream()),
                   executed=lambda: conv_executed_flops(n, out_channels, cin, kernel_size, stride, in_height, in_width,
                                                        resize),
                   pipe="fp32",
@@ -503,11 +532,8 @@ def scale_planes(x: torch.Tensor, z: torch.Tensor, out: Optional[torch.Tensor] =
     n, c, h, w = x.shape
     if tuple(z.shape) != (n, 1, h, w):
         raise KbnError(f"scale_planes: z has shape {tuple(z.shape)}, expected {(n, 1, h, w)}")
-    if out is None:
-        out = torch.empty((n, c, h, w), device=x.device, dtype=torch.float32)
+    out = _out_tensor(out, (n, c, h, w), x.device, "scale_planes: out", planes=True)
     optr, obs = _planes(out, "out")
-    if tuple(out.shape) != (n, c, h, w):
-        raise KbnError(f"scale_planes: out has shape {tuple(out.shape)}, expected {(n, c, h, w)}")
     check(_launch("scale_planes", 1.0 * n * c * h * w,
                   lambda: lib.kbn_scale_planes_forward(xptr, xbs, zptr, zbs, optr, obs, n, c, h, w, _stream()),
                   nbytes=4.0 * n * h * w * (2 * c + 1)), "kbn_scale_planes_forward")
@@ -526,19 +552,13 @@ def pack_upconv2x_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = Non
     ConvTranspose2d(kernel 3, stride 2, padding 1, output_padding 1) parameter, in x out x 3 x 3, and the blob is
     for `upconv2x(transposed=True)` (kbn_deconv2x_pack_weight)."""
     lib = _lib.load()
-    w = _deconv_weight(weight) if transposed else weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(_deconv_weight(weight) if transposed else weight)
     oc, cin, kh, kw = w.shape
     if (kh, kw) != (3, 3):
         raise KbnError("upconv2x needs a 3x3 weight")
-    nfloats = lib.kbn_upconv2x_packed_weight_bytes(oc, cin) // 4
-    packed = out if _reusable(out, nfloats, w) else torch.empty(nfloats, device=w.device, dtype=torch.float32)
-    if transposed:
-        check(lib.kbn_deconv2x_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, _stream()), "kbn_deconv2x_pack_weight")
-    else:
-        check(lib.kbn_upconv2x_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, _stream()),
-              "kbn_upconv2x_pack_weight")
-    return packed
+    pack = lib.kbn_deconv2x_pack_weight if transposed else lib.kbn_upconv2x_pack_weight
+    return _pack_into(out, lib.kbn_upconv2x_packed_weight_bytes(oc, cin), w, lambda p: pack(w.data_ptr(), p, oc, cin, _stream()),
+                      "kbn_deconv2x_pack_weight" if transposed else "kbn_upconv2x_pack_weight")
 
 
 @_on_tensor_device
@@ -563,9 +583,7 @@ def upconv2x(x: torch.Tensor, packed_weight: torch.Tensor, out_channels: int, ou
         executed = lambda: upconv2x_executed_flops(n, cin, out_channels, h, w)
     check(_launch("conv_up2x", work,
                   lambda: fwd(xptr, xbs, packed_weight.data_ptr(), optr, obs, n, cin,
-                              out_channels, h, w, 0 if negative_slope is None else 1,
-                              0.0 if negative_slope is None else float(negative_slope),
-                              _slot_ptr(out_absmax, n), _stream()),
+                              out_channels, h, w, *_act_args(negative_slope), _slot_ptr(out_absmax, n), _stream()),
                   executed=executed, pipe="fp32",
                   nbytes=4.0 * n * h * w * (cin + 4 * out_channels)), name)
     return out
@@ -634,8 +652,7 @@ def depth_head(x, weight, min_predict_depth: float, max_predict_depth: float, re
     lib = _lib.load()
     _require(x, "x", 4)
     x = x.contiguous()
-    w = weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(weight)
     n, c, h, wd = x.shape
     if tuple(w.shape) != (1, c, 3, 3):
         raise KbnError(f"depth head weight must be 1 x {c} x 3 x 3")
@@ -647,13 +664,7 @@ def depth_head(x, weight, min_predict_depth: float, max_predict_depth: float, re
         # (device ops only -- a fill and a pad: this runs under HIP-graph capture too)
         ident = torch.nn.functional.pad(torch.ones((1, 1, 1, 1), device=x.device, dtype=torch.float32), (1, 1, 1, 1))
         return depth_head(plane, ident, min_predict_depth, max_predict_depth, return_logits=return_logits, out=out)
-    if out is None:
-        depth = torch.empty((n, 1, h, wd), device=x.device, dtype=torch.float32)
-    else:
-        _require(out, "out", 4)
-        if tuple(out.shape) != (n, 1, h, wd) or not out.is_contiguous():
-            raise KbnError(f"out must be a contiguous {(n, 1, h, wd)} tensor")
-        depth = out
+    depth = _out_tensor(out, (n, 1, h, wd), x.device)
     logits = torch.empty_like(depth) if return_logits else None
     check(_launch("depth_head", 4.0 * n * h * wd * (c + 1),
                   lambda: lib.kbn_depth_head_forward(x.data_ptr(), w.data_ptr(), depth.data_ptr(),
@@ -671,35 +682,21 @@ def conv_head(x, w_conv, w_out, min_predict_depth: float, max_predict_depth: flo
     lib = _lib.load()
     xptr, xbs = _planes(x, "x")
     n, c, h, wd = x.shape
-    wc = w_conv.detach().contiguous()
-    wo = w_out.detach().contiguous()
-    _require(wc, "w_conv", 4)
-    _require(wo, "w_out", 4)
+    wc, wo = _weight(w_conv, "w_conv"), _weight(w_out, "w_out")
     if tuple(wc.shape) != (c, c, 3, 3) or tuple(wo.shape) != (1, c, 3, 3):
         raise KbnError(f"conv_head weights must be {c} x {c} x 3 x 3 and 1 x {c} x 3 x 3")
-    if out is None:
-        depth = torch.empty((n, 1, h, wd), device=x.device, dtype=torch.float32)
-    else:
-        _require(out, "out", 4)
-        if tuple(out.shape) != (n, 1, h, wd) or not out.is_contiguous():
-            raise KbnError(f"out must be a contiguous {(n, 1, h, wd)} tensor")
-        depth = out
+    depth = _out_tensor(out, (n, 1, h, wd), x.device)
     logits = torch.empty_like(depth) if return_logits else None
     flops = 2.0 * n * h * wd * c * 9 * c
-    status = _launch("conv_head", flops,
+    if not _launched("kbn_conv_head_forward", "conv_head", flops,
                      lambda: lib.kbn_conv_head_forward(xptr, xbs, wc.data_ptr(), wo.data_ptr(), depth.data_ptr(),
                                                        logits.data_ptr() if return_logits else None, n, c, h, wd,
-                                                       0 if negative_slope is None else 1,
-                                                       0.0 if negative_slope is None else float(negative_slope),
+                                                       *_act_args(negative_slope),
                                                        float(min_predict_depth), float(max_predict_depth), _stream()),
                      # 75 m-blocks of 16 positions per 64 x 16 tile, 16 filter columns, K = 9 c
                      executed=2.0 * n * (-(-h // 16)) * (-(-wd // 64)) * 75 * 16 * 16 * 9 * c, pipe="fp32",
-                     nbytes=4.0 * n * h * wd * (c + 1))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                     nbytes=4.0 * n * h * wd * (c + 1)):
         return None
-    check(status, "kbn_conv_head_forward")
     return (depth, logits) if return_logits else depth
 
 
@@ -708,17 +705,12 @@ def pack_conv_tail_weight(w_conv: torch.Tensor, out: Optional[torch.Tensor] = No
     """Blob of `conv_tail` from the raw C x C x 3 x 3 weight of deconv0's second conv (kbn_conv_tail_pack_weight); None when
     C is outside the kernel's range."""
     lib = _lib.load()
-    w = w_conv.detach().contiguous()
-    _require(w, "w_conv", 4)
+    w = _weight(w_conv, "w_conv")
     c = w.shape[0]
-    if tuple(w.shape) != (c, c, 3, 3):
-        return None
-    nbytes = lib.kbn_conv_tail_packed_weight_bytes(c)
+    nbytes = lib.kbn_conv_tail_packed_weight_bytes(c) if tuple(w.shape) == (c, c, 3, 3) else 0
     if nbytes == 0:
         return None
-    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    check(lib.kbn_conv_tail_pack_weight(w.data_ptr(), packed.data_ptr(), c, _stream()), "kbn_conv_tail_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv_tail_pack_weight(w.data_ptr(), p, c, _stream()), "kbn_conv_tail_pack_weight")
 
 
 @_on_tensor_device
@@ -728,8 +720,7 @@ def conv_tail(x, packed_w_conv, w_out, min_predict_depth: float, max_predict_dep
     `x`: N x C x H x W fp32, or the up-conv's PairTensor of 16 channels (kbn_conv_tail_forward_pair; C = w_out's channels).
     Returns None when the shape does not qualify: the caller runs conv_head / the two-launch path."""
     lib = _lib.load()
-    wo = w_out.detach().contiguous()
-    _require(wo, "w_out", 4)
+    wo = _weight(w_out, "w_out")
     pair = isinstance(x, PairTensor)
     if pair:
         n, cp, h, wd = x.shape
@@ -741,29 +732,18 @@ def conv_tail(x, packed_w_conv, w_out, min_predict_depth: float, max_predict_dep
         n, c, h, wd = x.shape
     if tuple(wo.shape) != (1, c, 3, 3):
         raise KbnError(f"conv_tail: w_out must be 1 x {c} x 3 x 3")
-    if out is None:
-        depth = torch.empty((n, 1, h, wd), device=x.device, dtype=torch.float32)
-    else:
-        _require(out, "out", 4)
-        if tuple(out.shape) != (n, 1, h, wd) or not out.is_contiguous():
-            raise KbnError(f"out must be a contiguous {(n, 1, h, wd)} tensor")
-        depth = out
+    depth = _out_tensor(out, (n, 1, h, wd), x.device)
     logits = torch.empty_like(depth) if return_logits else None
     flops = 2.0 * n * h * wd * c * 9 * c
     tiles = n * (-(-h // 16)) * (-(-wd // 32))
     tail_args = (packed_w_conv.data_ptr(), wo.data_ptr(), depth.data_ptr(), logits.data_ptr() if return_logits else None, n, c, h, wd,
-                 0 if negative_slope is None else 1, 0.0 if negative_slope is None else float(negative_slope),
-                 float(min_predict_depth), float(max_predict_depth))
-    status = _launch("conv_tail", flops,
+                 *_act_args(negative_slope), float(min_predict_depth), float(max_predict_depth))
+    if not _launched("kbn_conv_tail_forward", "conv_tail", flops,
                      (lambda: lib.kbn_conv_tail_forward_pair(x.data.data_ptr(), x.data.stride(0), x.scale.data_ptr(), *tail_args, _stream()))
                      if pair else (lambda: lib.kbn_conv_tail_forward(xptr, xbs, *tail_args, _stream())),
                      executed=tiles * 39 * 15 * 2.0 * 16 * 16 * 32,   # 39 pixel blocks x 15 MFMAs of 16 x 16 x 32 per tile
-                     pipe="fp16", nbytes=4.0 * n * h * wd * ((16 if pair else c) + 1))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                     pipe="fp16", nbytes=4.0 * n * h * wd * ((16 if pair else c) + 1)):
         return None
-    check(status, "kbn_conv_tail_forward")
     return (depth, logits) if return_logits else depth
 
 
@@ -778,15 +758,13 @@ def pack_conv3x3_split_weight(weight: torch.Tensor, out: Optional[torch.Tensor] 
     `conv3x3_split(up2x=True, folded_up2x=True, transposed=True)` reads (mode 4: the folded kernels, the layer's own taps)."""
     mode = 4 if transposed else (3 if folded_up2x else (2 if stride == 2 else 0))
     lib = _lib.load()
-    w = _deconv_weight(weight) if transposed else weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(_deconv_weight(weight) if transposed else weight)
     oc, cin, kh, kw = w.shape
     nbytes = lib.kbn_conv3x3_split_packed_weight_bytes(oc, cin, mode) if (kh, kw) == (3, 3) else 0
     if nbytes == 0:
         raise KbnError(f"conv3x3_split needs a 3x3 weight with in_channels % 16 == 0, got {tuple(w.shape)}")
-    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    check(lib.kbn_conv3x3_split_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, mode, _stream()), "kbn_conv3x3_split_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv3x3_split_pack_weight(w.data_ptr(), p, oc, cin, mode, _stream()),
+                      "kbn_conv3x3_split_pack_weight")
 
 
 def act_exponent_for(amax: float) -> int:
@@ -865,37 +843,25 @@ def conv3x3_split(srcs: List[ConvSrc], packed_weight: torch.Tensor, n: int, out_
         if pair or mode == 1:
             raise KbnError("conv3x3_split: ksplit goes with the plain / stride-2 / folded up-conv forms and an fp32 output")
         ws = torch.empty((ksplit, n, out_channels, height, width), device=out.device, dtype=torch.float32)
-        status = _launch(("conv_split", "", "conv_split_s2", "conv_split_upfold", "conv_split_upfold")[mode], flops,
+        done = _launched("kbn_conv3x3_split_forward_ksplit", ("conv_split", "", "conv_split_s2", "conv_split_upfold", "conv_split_upfold")[mode], flops,
                          lambda: lib.kbn_conv3x3_split_forward_ksplit(arr, len(srcs), packed_weight.data_ptr(), optr, obs, n, out_channels, height, width,
-                                                                      mode, max(-60, min(60, int(act_exponent))), 0 if negative_slope is None else 1,
-                                                                      0.0 if negative_slope is None else float(negative_slope),
+                                                                      mode, max(-60, min(60, int(act_exponent))), *_act_args(negative_slope),
                                                                       _slot_ptr(out_absmax, n), int(ksplit), ws.data_ptr(), _stream()),
                          executed=conv3x3_split_executed_flops(n, cin, out_channels, height, width, stride, up2x and folded_up2x),
                          pipe="fp16", nbytes=_src_bytes(srcs, n) + 4.0 * n * height * width * out_channels * (1 + 2 * ksplit))
-        if status == _lib.KBN_ERR_UNSUPPORTED:
-            if PROFILE is not None:
-                PROFILE.pop()
-            return None
-        check(status, "kbn_conv3x3_split_forward_ksplit")
-        return out
-    status = _launch(("conv_split", "conv_split_up", "conv_split_s2", "conv_split_upfold", "conv_split_upfold")[mode], flops,
+        return out if done else None
+    if not _launched("kbn_conv3x3_split_forward", ("conv_split", "conv_split_up", "conv_split_s2", "conv_split_upfold", "conv_split_upfold")[mode], flops,
                      lambda: lib.kbn_conv3x3_split_forward(arr, len(srcs), packed_weight.data_ptr(), optr, obs, n,
                                                            out_channels, height, width,
                                                            mode, max(-60, min(60, int(act_exponent))),
-                                                           0 if negative_slope is None else 1,
-                                                           0.0 if negative_slope is None else float(negative_slope),
-                                                           _slot_ptr(out_absmax, n),
+                                                           *_act_args(negative_slope), _slot_ptr(out_absmax, n),
                                                            out.data.data_ptr() if pair else None,
                                                            out.data.stride(0) if pair else 0,
                                                            out.scale.data_ptr() if pair else None, _stream()),
                      executed=conv3x3_split_executed_flops(n, cin, out_channels, height, width, stride, up2x and folded_up2x),
                      pipe="fp16", nbytes=_src_bytes(srcs, n) + 4.0 * n * height * width * want[1]
-                     + (4.0 * n * out_channels * out.sub.shape[2] * out.sub.shape[3] if (pair and out.sub is not None and stride == 2) else 0.0))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                     + (4.0 * n * out_channels * out.sub.shape[2] * out.sub.shape[3] if (pair and out.sub is not None and stride == 2) else 0.0)):
         return None
-    check(status, "kbn_conv3x3_split_forward")
     return out
 
 
@@ -926,17 +892,14 @@ def pack_conv1x1s2_split_weight(weight: torch.Tensor, xyz_offset: int = -1, out:
     channels in MFMA order (+ the fp32 weights of the three xyz channels that start at input channel `xyz_offset`,
     -1: the conv has none).  Tensor channels (in_channels, minus 3 with xyz) % 16 == 0."""
     lib = _lib.load()
-    w = weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(weight)
     oc, cin, kh, kw = w.shape
     has_xyz = xyz_offset >= 0
     nbytes = lib.kbn_conv1x1s2_split_packed_weight_bytes(oc, cin - (3 if has_xyz else 0), 1 if has_xyz else 0) if (kh, kw) == (1, 1) else 0
     if nbytes == 0:
         raise KbnError(f"conv1x1s2_split needs a 1x1 weight with tensor channels % 16 == 0, got {tuple(w.shape)}")
-    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    check(lib.kbn_conv1x1s2_split_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, int(xyz_offset), _stream()),
-          "kbn_conv1x1s2_split_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv1x1s2_split_pack_weight(w.data_ptr(), p, oc, cin, int(xyz_offset), _stream()),
+                      "kbn_conv1x1s2_split_pack_weight")
 
 
 @_on_tensor_device
@@ -955,9 +918,7 @@ def kb_xyz_s2(depth: torch.Tensor, proj_weight: torch.Tensor, kinv: torch.Tensor
         out = torch.empty((n, 3, oh, ow), device=depth.device, dtype=torch.float32)
     optr, obs = _planes(out, "xyz")
     check(_launch("kb_xyz", 2.0 * n * oh * ow * cd,
-                  lambda: lib.kbn_kb_xyz_s2_forward(dptr, dbs, cd, h, w, pw.data_ptr(), kinv.data_ptr(),
-                                                    0 if negative_slope is None else 1,
-                                                    0.0 if negative_slope is None else float(negative_slope),
+                  lambda: lib.kbn_kb_xyz_s2_forward(dptr, dbs, cd, h, w, pw.data_ptr(), kinv.data_ptr(), *_act_args(negative_slope),
                                                     optr, obs, n, _stream()), nbytes=4.0 * n * oh * ow * (cd + 3)), "kbn_kb_xyz_s2_forward")
     return out
 
@@ -982,19 +943,14 @@ def conv1x1s2_split(srcs: List[ConvSrc], packed_weight: torch.Tensor, xyz: Optio
     cin = sum(s.channels for s in srcs)
     flops = 2.0 * n * height * width * (cin + (3 if xyz is not None else 0)) * out_channels
     executed = 3 * 2.0 * n * (-(-height // 8) * 8) * (-(-width // 32) * 32) * cin * (-(-out_channels // 128) * 128)   # this kernel skips nothing
-    status = _launch("conv_split_1x1s2", flops,
+    if not _launched("kbn_conv1x1s2_split_forward", "conv_split_1x1s2", flops,
                      lambda: lib.kbn_conv1x1s2_split_forward(arr, len(srcs), packed_weight.data_ptr(), xptr, xbs, optr, obs, n,
                                                              out_channels, height, width, max(-60, min(60, int(act_exponent))),
-                                                             0 if negative_slope is None else 1,
-                                                             0.0 if negative_slope is None else float(negative_slope),
-                                                             _slot_ptr(out_absmax, n), _stream()), executed=executed, pipe="fp16",
+                                                             *_act_args(negative_slope), _slot_ptr(out_absmax, n), _stream()),
+                     executed=executed, pipe="fp16",
                      # a 1x1 stride-2 conv needs the even pixels of its sources only
-                     nbytes=4.0 * n * height * width * (cin + (3 if xyz is not None else 0) + out_channels))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                     nbytes=4.0 * n * height * width * (cin + (3 if xyz is not None else 0) + out_channels)):
         return None
-    check(status, "kbn_conv1x1s2_split_forward")
     return out
 
 
@@ -1006,9 +962,7 @@ def pack_kb1_front_weight(w_conv0: torch.Tensor, w_conv_image: torch.Tensor, w_c
     conv_image weight (FI x F0 x 3 x 3) and conv_fused weight (FI x (F0 + 3) x 1 x 1).  None when the shapes are outside
     the kernel's (F0 = FI = 48, C <= 4)."""
     lib = _lib.load()
-    w0, wi, wf = (w.detach().contiguous() for w in (w_conv0, w_conv_image, w_conv_fused))
-    for w, nm in ((w0, "w_conv0"), (wi, "w_conv_image"), (wf, "w_conv_fused")):
-        _require(w, nm, 4)
+    w0, wi, wf = _weight(w_conv0, "w_conv0"), _weight(w_conv_image, "w_conv_image"), _weight(w_conv_fused, "w_conv_fused")
     f0, c = w0.shape[0], w0.shape[1]
     fi = wi.shape[0]
     if tuple(w0.shape[2:]) != (3, 3) or tuple(wi.shape) != (fi, f0, 3, 3) or tuple(wf.shape) != (fi, f0 + 3, 1, 1):
@@ -1016,10 +970,8 @@ def pack_kb1_front_weight(w_conv0: torch.Tensor, w_conv_image: torch.Tensor, w_c
     nbytes = lib.kbn_kb1_front_packed_weight_bytes(c, f0, fi)
     if nbytes == 0:
         return None
-    packed = out if _reusable(out, nbytes // 4, w0) else torch.empty(nbytes // 4, device=w0.device, dtype=torch.float32)
-    check(lib.kbn_kb1_front_pack_weight(w0.data_ptr(), wi.data_ptr(), wf.data_ptr(), packed.data_ptr(), c, f0, fi, _stream()),
-          "kbn_kb1_front_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w0, lambda p: lib.kbn_kb1_front_pack_weight(w0.data_ptr(), wi.data_ptr(), wf.data_ptr(), p, c, f0, fi, _stream()),
+                      "kbn_kb1_front_pack_weight")
 
 
 def kb1_front_supported(image_channels: int, conv0_filters: int, kb_filters: int, height: int, width: int,
@@ -1035,8 +987,7 @@ def pack_kb1_front_next_weight(w_conv_fused: torch.Tensor, image_channels: int, 
     """Blob of kb1_front's `next` stage (kbn_kb1_front_next_pack_weight) from the NEXT KB block's conv_fused weight,
     F x (image_channels + 3 + fused_channels) x 1 x 1.  None when the widths are outside the kernel's (48 + 3 + 48 -> 96)."""
     lib = _lib.load()
-    wf = w_conv_fused.detach().contiguous()
-    _require(wf, "w_conv_fused", 4)
+    wf = _weight(w_conv_fused, "w_conv_fused")
     fo, cin = wf.shape[0], wf.shape[1]
     cf = cin - 3 - image_channels
     if tuple(wf.shape[2:]) != (1, 1) or cf < 0:
@@ -1044,10 +995,8 @@ def pack_kb1_front_next_weight(w_conv_fused: torch.Tensor, image_channels: int, 
     nbytes = lib.kbn_kb1_front_next_packed_weight_bytes(int(image_channels), int(cf), int(fo))
     if nbytes == 0:
         return None
-    packed = out if _reusable(out, nbytes // 4, wf) else torch.empty(nbytes // 4, device=wf.device, dtype=torch.float32)
-    check(lib.kbn_kb1_front_next_pack_weight(wf.data_ptr(), packed.data_ptr(), int(image_channels), int(cf), int(fo), _stream()),
-          "kbn_kb1_front_next_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, wf, lambda p: lib.kbn_kb1_front_next_pack_weight(wf.data_ptr(), p, int(image_channels), int(cf), int(fo), _stream()),
+                      "kbn_kb1_front_next_pack_weight")
 
 
 def kb1_front_next_supported(image_channels: int, conv0_filters: int, kb_filters: int, next_filters: int, height: int, width: int,
@@ -1107,12 +1056,8 @@ def kb1_front(image: torch.Tensor, packed_weight: torch.Tensor, xyz: Optional[to
                                                       _slot_ptr(out_image_absmax, n), _slot_ptr(out_fused_absmax, n),
                                                       packed_next.data_ptr(), xn, xnbs, on, onbs, fo, float(slope_next),
                                                       _slot_ptr(amax_next, n), _stream())
-    status = _launch("kb1_front", flops, call, executed=executed, pipe="fp16", nbytes=nbytes)
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+    if not _launched("kbn_kb1_front_forward", "kb1_front", flops, call, executed=executed, pipe="fp16", nbytes=nbytes):
         return None
-    check(status, "kbn_kb1_front_forward")
     return out_image, out_fused
 
 
@@ -1122,9 +1067,7 @@ def pack_kb1_depth_front_weight(w_conv0: torch.Tensor, w_conv_depth: torch.Tenso
     """Blob of `kb1_depth_front` from conv0_depth's weight (16 x C x 3 x 3), the level-0 KB block's conv_depth weight
     (16 x 19 x 3 x 3) and proj_depth weight (1 x 16 x 1 x 1).  None when the shapes are outside the kernel's."""
     lib = _lib.load()
-    w0, wc, wp = (w.detach().contiguous() for w in (w_conv0, w_conv_depth, w_proj))
-    for w, nm in ((w0, "w_conv0"), (wc, "w_conv_depth"), (wp, "w_proj")):
-        _require(w, nm, 4)
+    w0, wc, wp = _weight(w_conv0, "w_conv0"), _weight(w_conv_depth, "w_conv_depth"), _weight(w_proj, "w_proj")
     f0, c = w0.shape[0], w0.shape[1]
     fd = wc.shape[0]
     if tuple(w0.shape[2:]) != (3, 3) or tuple(wc.shape) != (fd, f0 + 3, 3, 3) or wp.numel() != f0:
@@ -1132,10 +1075,8 @@ def pack_kb1_depth_front_weight(w_conv0: torch.Tensor, w_conv_depth: torch.Tenso
     nbytes = lib.kbn_kb1_depth_front_packed_weight_bytes(c, f0, fd)
     if nbytes == 0:
         return None
-    packed = out if _reusable(out, nbytes // 4, w0) else torch.empty(nbytes // 4, device=w0.device, dtype=torch.float32)
-    check(lib.kbn_kb1_depth_front_pack_weight(w0.data_ptr(), wc.data_ptr(), wp.data_ptr(), packed.data_ptr(), c, f0, fd, _stream()),
-          "kbn_kb1_depth_front_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w0, lambda p: lib.kbn_kb1_depth_front_pack_weight(w0.data_ptr(), wc.data_ptr(), wp.data_ptr(), p, c, f0, fd, _stream()),
+                      "kbn_kb1_depth_front_pack_weight")
 
 
 @_on_tensor_device
@@ -1160,18 +1101,13 @@ def kb1_depth_front(depth: torch.Tensor, kinv: torch.Tensor, packed_weight: torc
     flops = 2.0 * n * (h * w * c * 9 * conv0_filters + oh * ow * ((conv0_filters + 3) * 9 * kb_filters + conv0_filters))
     tiles = n * (-(-oh // 8)) * (-(-ow // 16))
     executed = tiles * (36 * 9 + 8 * 15) * 2.0 * 16 * 16 * 32
-    status = _launch("kb1_depth_front", flops,
+    if not _launched("kbn_kb1_depth_front_forward", "kb1_depth_front", flops,
                      lambda: lib.kbn_kb1_depth_front_forward(dptr, dbs, kinv.data_ptr(), packed_weight.data_ptr(), optr, obs, xptr, xbs,
                                                              n, c, conv0_filters, kb_filters, h, w, float(conv0_negative_slope),
-                                                             float(kb_negative_slope), 0 if proj_negative_slope is None else 1,
-                                                             0.0 if proj_negative_slope is None else float(proj_negative_slope),
+                                                             float(kb_negative_slope), *_act_args(proj_negative_slope),
                                                              _slot_ptr(out_depth_absmax, n), _stream()),
-                     executed=executed, pipe="fp16", nbytes=4.0 * n * (h * w * c + oh * ow * (kb_filters + 3)))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                     executed=executed, pipe="fp16", nbytes=4.0 * n * (h * w * c + oh * ow * (kb_filters + 3))):
         return None
-    check(status, "kbn_kb1_depth_front_forward")
     return out_depth, xyz
 
 
@@ -1184,10 +1120,8 @@ def pack_s2d_depth_front_weight(w_pool_convs: List[torch.Tensor], w_conv: torch.
     lib = _lib.load()
     if len(w_pool_convs) != 3:
         return None
-    ws = [w.detach().contiguous() for w in w_pool_convs]
-    wc = w_conv.detach().contiguous()
-    for w in ws + [wc]:
-        _require(w, "weight", 4)
+    ws = [_weight(w) for w in w_pool_convs]
+    wc = _weight(w_conv)
     npool = ws[0].shape[1]
     if (tuple(ws[0].shape) != (8, npool, 1, 1) or tuple(ws[1].shape) != (8, 8, 1, 1) or tuple(ws[2].shape) != (8, 8, 1, 1)
             or tuple(wc.shape) != (8, 10, 3, 3)):
@@ -1195,10 +1129,8 @@ def pack_s2d_depth_front_weight(w_pool_convs: List[torch.Tensor], w_conv: torch.
     nbytes = lib.kbn_s2d_depth_front_packed_weight_bytes(npool)
     if nbytes == 0:
         return None
-    packed = out if _reusable(out, nbytes // 4, wc) else torch.empty(nbytes // 4, device=wc.device, dtype=torch.float32)
-    check(lib.kbn_s2d_depth_front_pack_weight(ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), wc.data_ptr(), packed.data_ptr(), npool,
-                                              _stream()), "kbn_s2d_depth_front_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, wc, lambda p: lib.kbn_s2d_depth_front_pack_weight(ws[0].data_ptr(), ws[1].data_ptr(), ws[2].data_ptr(), wc.data_ptr(),
+                                                                                     p, npool, _stream()), "kbn_s2d_depth_front_pack_weight")
 
 
 def s2d_depth_front_supported(input_channels: int, min_pool_sizes, max_pool_sizes, n_convolution: int, n_filter: int, conv0_filters: int,
@@ -1242,19 +1174,13 @@ def s2d_depth_front(x: torch.Tensor, kinv: torch.Tensor, packed_s2d: torch.Tenso
     tiles = n * (-(-oh // 8)) * (-(-ow // 16))
     executed = tiles * (27 * 6 + 22 * 12 + 36 * 9 + 8 * 15) * 2.0 * 16 * 16 * 32   # chain, 3x3 pairs, conv0, conv_depth: MFMAs of 16 x 16 x 32 per tile
     amin, amax = _int_array(mins), _int_array(maxs)
-    status = _launch("s2d_depth_front", flops,
+    if not _launched("kbn_s2d_depth_front_forward", "s2d_depth_front", flops,
                      lambda: lib.kbn_s2d_depth_front_forward(xptr, xbs, kinv.data_ptr(), packed_s2d.data_ptr(), packed_weight.data_ptr(), optr, obs,
                                                              zptr, zbs, n, c, amin, len(mins), amax, len(maxs), 3, nf, conv0_filters, kb_filters,
                                                              h, w, float(s2d_negative_slope), float(conv0_negative_slope), float(kb_negative_slope),
-                                                             0 if proj_negative_slope is None else 1,
-                                                             0.0 if proj_negative_slope is None else float(proj_negative_slope),
-                                                             _slot_ptr(out_depth_absmax, n), _stream()),
-                     executed=executed, pipe="fp16", nbytes=4.0 * n * (h * w * c + oh * ow * (kb_filters + 3)))
-    if status == _lib.KBN_ERR_UNSUPPORTED:
-        if PROFILE is not None:
-            PROFILE.pop()
+                                                             *_act_args(proj_negative_slope), _slot_ptr(out_depth_absmax, n), _stream()),
+                     executed=executed, pipe="fp16", nbytes=4.0 * n * (h * w * c + oh * ow * (kb_filters + 3))):
         return None
-    check(status, "kbn_s2d_depth_front_forward")
     return out_depth, xyz
 
 
@@ -1438,18 +1364,15 @@ def pack_conv2d_s2_affine_weight(weight: torch.Tensor, out: Optional[torch.Tenso
     """OIHW (k in {3, 5, 7}, any channel counts) -> the [filter tile][K chunk][16][filters] order conv2d_s2_affine reads
     (kbn_conv2d_s2_affine_pack_weight); `out`: an existing blob of the right size to re-pack into."""
     lib = _lib.load()
-    w = weight.detach().contiguous()
-    _require(w, "weight", 4)
+    w = _weight(weight)
     oc, cin, kh, kw = w.shape
     if kh != kw:
         raise KbnError("square kernels only")
     nbytes = lib.kbn_conv2d_s2_affine_packed_weight_bytes(oc, cin, kh)
     if nbytes == 0:
         raise KbnError(f"conv2d_s2_affine: unsupported weight shape {tuple(w.shape)} (kernel size 3, 5 or 7)")
-    packed = out if _reusable(out, nbytes // 4, w) else torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    check(lib.kbn_conv2d_s2_affine_pack_weight(w.data_ptr(), packed.data_ptr(), oc, cin, kh, _stream()),
-          "kbn_conv2d_s2_affine_pack_weight")
-    return packed
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_s2_affine_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
+                      "kbn_conv2d_s2_affine_pack_weight")
 
 
 @_on_tensor_device
@@ -1484,10 +1407,7 @@ def conv2d_s2_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor
         if t.numel() != out_channels or not t.is_contiguous():
             raise KbnError(f"conv2d_s2_affine: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
     oh, ow = (h + 1) // 2, (w + 1) // 2
-    if out is None:
-        out = torch.empty((n, out_channels, oh, ow), device=inputs[0].device, dtype=torch.float32)
-    elif tuple(out.shape) != (n, out_channels, oh, ow):
-        raise KbnError(f"out has shape {tuple(out.shape)}, expected {(n, out_channels, oh, ow)}")
+    out = _out_tensor(out, (n, out_channels, oh, ow), inputs[0].device, planes=True)
     optr, obs = _planes(out, "out")
     arr = (ConvSrc * len(srcs))(*srcs)
     k2 = kernel_size * kernel_size
@@ -1496,8 +1416,7 @@ def conv2d_s2_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor
     check(_launch(f"conv_s2_affine<{kernel_size},{nt // 16}>", 2.0 * n * oh * ow * cin * k2 * out_channels,
                   lambda: lib.kbn_conv2d_s2_affine_forward(arr, len(srcs), packed_weight.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                                                            optr, obs, n, out_channels, kernel_size, h, w,
-                                                           0 if negative_slope is None else 1,
-                                                           0.0 if negative_slope is None else float(negative_slope), _stream()),
+                                                           *_act_args(negative_slope), _stream()),
                   executed=2.0 * (-(-n * oh * ow // 128) * 128) * kpad * (-(-out_channels // nt) * nt), pipe="fp32",
                   nbytes=_src_bytes(srcs, n) + 4.0 * n * oh * ow * out_channels), "kbn_conv2d_s2_affine_forward")
     return out
@@ -1517,17 +1436,9 @@ def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = Fal
         raise KbnError(f"pose_head: weight must be a contiguous 6 x {c} (x 1 x 1) tensor, got {tuple(weight.shape)}")
     if n < 1 or c < 1 or h < 1 or w < 1:
         raise KbnError(f"pose_head: empty latent {tuple(latent.shape)}")
-    if out is None:
-        out = torch.empty((n, 4, 4), device=latent.device, dtype=torch.float32)
-    _require(out, "out", 3)
-    if tuple(out.shape) != (n, 4, 4) or not out.is_contiguous():
-        raise KbnError(f"pose_head: out must be a contiguous {(n, 4, 4)} tensor, got {tuple(out.shape)}")
+    out = _out_tensor(out, (n, 4, 4), latent.device, "pose_head: out")
     if return_dof or dof_out is not None:
-        if dof_out is None:
-            dof_out = torch.empty((n, 6), device=latent.device, dtype=torch.float32)
-        _require(dof_out, "dof_out", 2)
-        if tuple(dof_out.shape) != (n, 6) or not dof_out.is_contiguous():
-            raise KbnError(f"pose_head: dof_out must be a contiguous {(n, 6)} tensor, got {tuple(dof_out.shape)}")
+        dof_out = _out_tensor(dof_out, (n, 6), latent.device, "pose_head: dof_out")
     check(_launch("pose_head", 2.0 * n * h * w * c * 6,
                   lambda: lib.kbn_pose_head_forward(ptr, bs, weight.data_ptr(), out.data_ptr(),
                                                     dof_out.data_ptr() if dof_out is not None else None, n, c, h, w, _stream()),

@@ -61,8 +61,8 @@ class _BareConv(torch.nn.Module):
 
 class PoseConv2d(torch.nn.Module):
     """net_utils.Conv2d(stride=2, use_batch_norm=True) in eval mode: conv, BatchNorm2d on its running statistics, activation, in
-    one launch (ops.conv2d_s2_affine).  The packed weight and the scale / shift vectors are cached and rebuilt when a parameter
-    or buffer changes (in place, replaced or moved), like modules._PackedWeight."""
+    one launch (ops.conv2d_s2_affine).  The packed weight (a modules._PackedBlob) and the scale / shift vectors are cached and
+    rebuilt when a parameter or buffer changes (in place, replaced or moved)."""
 
     def __init__(self, in_channels, out_channels, kernel_size, weight_initializer, slope):
         super().__init__()
@@ -73,16 +73,12 @@ class PoseConv2d(torch.nn.Module):
         self.batch_norm = torch.nn.BatchNorm2d(out_channels)
         for p in self.batch_norm.parameters():
             p.requires_grad_(False)
-        self._wkey = self._akey = None
-        self._packed = self._scale = self._shift = None
+        from .modules import _PackedBlob   # (modules.py imports this file at its end: not at the top)
+        self._packed = _PackedBlob(ops.pack_conv2d_s2_affine_weight)
+        self._akey = self._scale = self._shift = None
 
     def packed(self):
-        w = self.conv.weight
-        key = _state(w)
-        if key != self._wkey:
-            self._packed = ops.pack_conv2d_s2_affine_weight(w, out=self._packed)
-            self._wkey = key
-        return self._packed
+        return self._packed.get(self.conv.weight)
 
     def affine(self):
         """scale = g * rsqrt(var + eps), shift = b - mean * scale (BatchNorm2d.eval()), fp32 on the weights' device."""
@@ -205,6 +201,12 @@ class PoseNetModel(object):
 
     def modules(self):
         return (self.encoder, self.decoder)
+
+    def refresh_packed(self):
+        """Re-packs (in place) the blobs of weights that changed since they were packed, as KBNetModel.refresh_packed."""
+        from .modules import packed_blobs
+        for blob in packed_blobs(self):
+            blob.refresh()
 
     def parameters(self):
         return list(self.encoder.parameters()) + list(self.decoder.parameters())

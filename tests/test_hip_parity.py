@@ -2282,6 +2282,44 @@ def test_graph_replay_follows_weight_updates(dev):
         replay(*a)
 
 
+@pytest.mark.parametrize("case", ["default", "s2d_front", "transpose"])
+def test_graph_replay_refreshes_every_packed_blob(dev, case):
+    """test_graph_replay_follows_weight_updates on the full-width KITTI preset, whose forward uses the blobs the narrow one
+    never builds: the encoder front's (image launch with the next level's conv_fused, depth launch; `s2d_front`: with the S2D
+    stage in it, opt-in), the split 1x1 stride-2 conv_fused's and the tail's; `transpose`: the transposed up-convs'.  A replay
+    after an in-place weight update must equal a fresh model's eager forward bit for bit: one blob left stale would show."""
+    import dataclasses
+    cfg = kb.kitti_config()
+    if case == "transpose":
+        cfg = dataclasses.replace(cfg, deconv_type="transpose")
+
+    def model(seed):
+        m = kb.modules.KBNetModel.from_config(cfg, dev)
+        m.encoder.fuse_s2d = case == "s2d_front"
+        m.load_state_dicts(*kb.synthetic.make_state_dicts(cfg, seed=seed, gain=1.3))
+        return m
+
+    m = model(0)
+    a = to(dev, *kb.synthetic.make_frames(2, 64, 96, "kitti", seed=1))
+    kb.ops.PROFILE = []
+    try:
+        m.forward(*a)
+        names = [r[0] for r in kb.ops.PROFILE]
+    finally:
+        kb.ops.PROFILE = None
+    assert "kb1_front" in names and "conv_tail" in names and "conv_split_1x1s2" in names, names
+    # level 1's conv_fused (96 filters: an fp32 1x1 stride-2 launch when it runs on its own) rode along in kb1_front
+    assert not any(nm.startswith(("conv_dma<1,2", "conv_igemm<1,2")) for nm in names), names
+    assert ("s2d_depth_front" if case == "s2d_front" else "kb1_depth_front") in names, names
+    assert "conv_split_upfold" in names, names
+    replay = m.capture(*a, tune=False)
+    before = replay(*a).clone()
+    m.load_state_dicts(*kb.synthetic.make_state_dicts(cfg, seed=9, gain=1.3))
+    after = replay(*a).clone()
+    assert not torch.equal(before, after)
+    assert torch.equal(after, model(9).forward(*a)), "replay after load_state_dicts must use the new weights everywhere"
+
+
 def test_channel_count_mismatch_raises(dev):
     """Public entry points validate channel counts (the packed blobs carry no size)."""
     act = torch.nn.LeakyReLU(0.2)

@@ -1496,3 +1496,5 @@ class KBNetModel(object):
 
 
 from .posenet import PoseDecoder, PoseEncoder, PoseNetModel  # noqa: E402,F401  (posenet.py: the pose network beside KBNetModel)
+from .posenet_resnet import (ResNetBlock, ResNetEncoder, ResNetPoseDecoder, ResNetPoseNetModel,  # noqa: E402,F401  (posenet_resnet.py:
+                             load_pose_model)                                                      # the ResNet-18 / 34 pose networks)

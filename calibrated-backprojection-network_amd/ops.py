@@ -1338,11 +1338,15 @@ def loss_terms(sums: torch.Tensor, height: int, width: int) -> torch.Tensor:
 def pose_matrix(v: torch.Tensor) -> torch.Tensor:
     """N x 6 -> N x 4 x 4 as the reference's net_utils.pose_matrix (src/net_utils.py:1493-1595): the FIRST three entries are the
     axis-angle rotation and the LAST three the translation (its docstring says the opposite; the code decides), axis = r / (|r| + 1e-7),
-    M = T(t) R.  Plain torch on the tensor's device and in its dtype: 16 numbers per frame."""
+    M = T(t) R.  Plain torch on the tensor's device and in its dtype: 16 numbers per frame.  |r| is written out (see below): at most 1 ulp
+    of the angle from the reference's torch.norm, whose rounding is torch's and the device's own."""
     if not isinstance(v, torch.Tensor) or v.dim() != 2 or v.shape[1] != 6:
         raise KbnError(f"pose_matrix: expected an N x 6 tensor, got {tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__}")
     r, t = v[:, :3], v[:, 3:]
-    angle = torch.linalg.vector_norm(r, dim=1, keepdim=True)
+    # sqrt((r0 r0 + r1 r1) + r2 r2), every product and sum an operation of its own -- what pose_from_dof (csrc/posenet.hip) evaluates.
+    # torch.norm / linalg.vector_norm round their sum another way, and not the same way on the CPU and on the device (1 ulp of the
+    # angle for about one vector in nine): with them this function had no fixed bits for the head kernel to reproduce.
+    angle = torch.sqrt((r[:, 0:1] * r[:, 0:1] + r[:, 1:2] * r[:, 1:2]) + r[:, 2:3] * r[:, 2:3])
     axis = r / (angle + 1e-7)
     ca, sa = torch.cos(angle[:, 0]), torch.sin(angle[:, 0])
     c = 1 - ca
@@ -1444,3 +1448,94 @@ def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = Fal
                                                     dof_out.data_ptr() if dof_out is not None else None, n, c, h, w, _stream()),
                   nbytes=4.0 * n * c * h * w), "kbn_pose_head_forward")
     return (out, dof_out) if return_dof else out
+
+
+# ------------------------------------------------------------------ ResNet pose networks (eval mode)
+@_on_tensor_device
+def pack_conv2d_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW (k in {1, 3, 7}, any channel counts) -> the [filter tile][K chunk][k][filters] order conv2d_affine reads
+    (kbn_conv2d_affine_pack_weight; not the blob of conv2d_s2_affine); `out`: an existing blob of the right size to re-pack into."""
+    lib = _lib.load()
+    w = _weight(weight)
+    oc, cin, kh, kw = w.shape
+    if kh != kw:
+        raise KbnError("square kernels only")
+    nbytes = lib.kbn_conv2d_affine_packed_weight_bytes(oc, cin, kh)
+    if nbytes == 0:
+        raise KbnError(f"conv2d_affine: unsupported weight shape {tuple(w.shape)} (kernel size 1, 3 or 7)")
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_affine_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
+                      "kbn_conv2d_affine_pack_weight")
+
+
+@_on_tensor_device
+def conv2d_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                  out_channels: int, kernel_size: int, stride: int = 1, negative_slope: Optional[float] = 0.2,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(act(conv_{k x k, stride, padding k // 2}(cat(inputs, 1)) * scale + shift) + residual) (kbn_conv2d_affine_forward): a
+    net_utils.Conv2d with eval-mode BatchNorm2d (reference src/net_utils.py:120-141) and, with `residual`, the add and the
+    second activation that end a ResNetBlock (src/net_utils.py:643-667), in one launch.  Without `residual`: one activation.
+    `inputs`: one or two N x C_i x H x W tensors read in place; k in {1, 3, 7}, stride in {1, 2}; `scale` / `shift`: out_channels
+    floats; `negative_slope` None: no activation at all; `residual` / `out`: N x out_channels x ceil(H / stride) x ceil(W / stride)
+    tensors or channel slices."""
+    lib = _lib.load()
+    inputs = list(inputs)
+    if not 1 <= len(inputs) <= 2:
+        raise KbnError(f"conv2d_affine: one or two inputs, got {len(inputs)}")
+    if kernel_size not in (1, 3, 7):
+        raise KbnError(f"conv2d_affine: kernel size 1, 3 or 7, got {kernel_size}")
+    if stride not in (1, 2):
+        raise KbnError(f"conv2d_affine: stride 1 or 2, got {stride}")
+    srcs = [tensor_src(t, f"inputs[{i}]") for i, t in enumerate(inputs)]
+    n, _, h, w = inputs[0].shape
+    for i, t in enumerate(inputs[1:], 1):
+        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
+            raise KbnError(f"conv2d_affine: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
+    if n < 1 or h < 1 or w < 1:
+        raise KbnError(f"conv2d_affine: empty input {tuple(inputs[0].shape)}")
+    cin = sum(s.channels for s in srcs)
+    _require(packed_weight, "packed_weight", 1)
+    want = lib.kbn_conv2d_affine_packed_weight_bytes(out_channels, cin, kernel_size) // 4
+    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
+        raise KbnError(f"conv2d_affine: packed_weight holds {packed_weight.numel()} floats, a {out_channels} x {cin} x "
+                       f"{kernel_size} x {kernel_size} weight packs into {want}")
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        _require(t, name, 1)
+        if t.numel() != out_channels or not t.is_contiguous():
+            raise KbnError(f"conv2d_affine: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
+    oh, ow = -(-h // stride), -(-w // stride)
+    rptr, rbs = None, 0
+    if residual is not None:
+        rptr, rbs = _planes(residual, "residual")
+        if tuple(residual.shape) != (n, out_channels, oh, ow):
+            raise KbnError(f"conv2d_affine: residual is {tuple(residual.shape)}, the output {(n, out_channels, oh, ow)}")
+    out = _out_tensor(out, (n, out_channels, oh, ow), inputs[0].device, planes=True)
+    optr, obs = _planes(out, "out")
+    arr = (ConvSrc * len(srcs))(*srcs)
+    k2 = kernel_size * kernel_size
+    # `want` = padded K x padded filter count, whatever the kernel's K chunk and filter tile are: no copy of its constants here
+    check(_launch(f"conv_affine<{kernel_size},{stride}>", 2.0 * n * oh * ow * cin * k2 * out_channels,
+                  lambda: lib.kbn_conv2d_affine_forward(arr, len(srcs), packed_weight.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                                        rptr, rbs, optr, obs, n, out_channels, kernel_size, stride, h, w,
+                                                        *_act_args(negative_slope), _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 128) * 128) * want, pipe="fp32",
+                  nbytes=_src_bytes(srcs, n) + 4.0 * n * oh * ow * out_channels * (2 if residual is not None else 1)),
+          "kbn_conv2d_affine_forward")
+    return out
+
+
+@_on_tensor_device
+def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.nn.MaxPool2d(3, stride=2, padding=1) (kbn_maxpool3x3s2_forward; reference src/networks.py:747): N x C x H x W ->
+    N x C x ceil(H / 2) x ceil(W / 2).  Padding never wins; a NaN in the window is the result.  `out`: a tensor or channel slice."""
+    lib = _lib.load()
+    ptr, bs = _planes(x, "x")
+    n, c, h, w = x.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"maxpool3x3s2: empty input {tuple(x.shape)}")
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    out = _out_tensor(out, (n, c, oh, ow), x.device, planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("maxpool3x3s2", 8.0 * n * c * oh * ow,
+                  lambda: lib.kbn_maxpool3x3s2_forward(ptr, bs, optr, obs, n, c, h, w, _stream()),
+                  nbytes=4.0 * n * c * (h * w + oh * ow)), "kbn_maxpool3x3s2_forward")
+    return out

@@ -169,35 +169,15 @@ class PoseDecoder(torch.nn.Module):
         return ops.pose_head(x, self.conv.conv.weight, return_dof=return_dof)
 
 
-class PoseNetModel(object):
-    """Inference counterpart of reference `PoseNetModel` (src/posenet_model.py:21-206): same constructor arguments and
-    `forward(image0, image1)` -> N x 4 x 4, the pose KBNetModel.compute_loss takes as pose01 / pose02."""
+class PoseModelBase(object):
+    """What the pose models share (PoseNetModel here, posenet_resnet.ResNetPoseNetModel): the device, checkpoint and re-pack
+    plumbing of reference `PoseNetModel` (src/posenet_model.py:114-206) over `self.encoder`, `self.decoder` and `self.device`,
+    which a subclass's constructor sets before it calls `_place(device)`."""
 
-    def __init__(self, encoder_type="posenet", rotation_parameterization="axis", weight_initializer="xavier_normal",
-                 activation_func="leaky_relu", device=torch.device("cuda"), n_filters=POSENET_FILTERS):
-        if encoder_type in ("resnet18", "resnet34"):
-            raise KbnError(f"PoseNetModel on the HIP path implements encoder_type='posenet' only, not {encoder_type!r} "
-                           "(the ResNet pose encoders are out of scope)")
-        if encoder_type != "posenet":
-            raise ValueError("Unsupported PoseNet encoder type: {}".format(encoder_type))
-        self.device = device
-        self.encoder = PoseEncoder(input_channels=6, n_filters=list(n_filters), weight_initializer=weight_initializer,
-                                   activation_func=activation_func, use_batch_norm=True)
-        self.decoder = PoseDecoder(rotation_parameterization=rotation_parameterization, weight_initializer=weight_initializer,
-                                   input_channels=list(n_filters)[-1])
+    def _place(self, device):
         self.data_parallel()
         self.to(device)
         self.eval()
-
-    @torch.no_grad()
-    def forward(self, image0, image1, return_all: bool = False):
-        """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone."""
-        if not isinstance(image0, torch.Tensor) or not isinstance(image1, torch.Tensor) or image0.dim() != 4 or \
-                image0.shape[1] != 3 or image0.shape != image1.shape:
-            raise KbnError("PoseNetModel.forward: image0 and image1 must be N x 3 x H x W tensors of one shape")
-        layers = self.encoder.encode([image0, image1], return_layers=True)
-        pose, dof = self.decoder(layers[-1], return_dof=True)
-        return (pose, dof, layers) if return_all else pose
 
     def modules(self):
         return (self.encoder, self.decoder)
@@ -247,3 +227,34 @@ class PoseNetModel(object):
                     "optimizer_state_dict": optimizer.state_dict() if optimizer is not None else {},
                     "encoder_state_dict": pref(self.encoder.state_dict()),
                     "decoder_state_dict": pref(self.decoder.state_dict())}, checkpoint_path)
+
+
+class PoseNetModel(PoseModelBase):
+    """Inference counterpart of reference `PoseNetModel` (src/posenet_model.py:21-206): same constructor arguments and
+    `forward(image0, image1)` -> N x 4 x 4, the pose KBNetModel.compute_loss takes as pose01 / pose02."""
+
+    def __init__(self, encoder_type="posenet", rotation_parameterization="axis", weight_initializer="xavier_normal",
+                 activation_func="leaky_relu", device=torch.device("cuda"), n_filters=POSENET_FILTERS):
+        if encoder_type in ("resnet18", "resnet34"):
+            raise KbnError(f"PoseNetModel on the HIP path implements encoder_type='posenet' only, not {encoder_type!r} "
+                           "(the ResNet pose networks are posenet_resnet.ResNetPoseNetModel; modules.load_pose_model picks the class "
+                           "from a checkpoint)")
+        if encoder_type != "posenet":
+            raise ValueError("Unsupported PoseNet encoder type: {}".format(encoder_type))
+        self.device = device
+        self.encoder_type = encoder_type      # 'posenet' here, 'resnet18' / 'resnet34' on the sibling: what load_pose_model found
+        self.encoder = PoseEncoder(input_channels=6, n_filters=list(n_filters), weight_initializer=weight_initializer,
+                                   activation_func=activation_func, use_batch_norm=True)
+        self.decoder = PoseDecoder(rotation_parameterization=rotation_parameterization, weight_initializer=weight_initializer,
+                                   input_channels=list(n_filters)[-1])
+        self._place(device)
+
+    @torch.no_grad()
+    def forward(self, image0, image1, return_all: bool = False):
+        """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone."""
+        if not isinstance(image0, torch.Tensor) or not isinstance(image1, torch.Tensor) or image0.dim() != 4 or \
+                image0.shape[1] != 3 or image0.shape != image1.shape:
+            raise KbnError("PoseNetModel.forward: image0 and image1 must be N x 3 x H x W tensors of one shape")
+        layers = self.encoder.encode([image0, image1], return_layers=True)
+        pose, dof = self.decoder(layers[-1], return_dof=True)
+        return (pose, dof, layers) if return_all else pose

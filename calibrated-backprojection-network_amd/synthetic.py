@@ -208,3 +208,50 @@ def make_image_pair(n: int, height: int, width: int, seed: int = 1, radius: int 
     image0 = scene[..., :, :width]
     image1 = 0.8 * scene[..., :, 2:] + 0.2 * own
     return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)) for a in (image0, image1))
+
+
+from .posenet_resnet import RESNET_BLOCKS  # noqa: E402  (the block counts of ResNet-18 / 34: one copy in the package)
+
+
+def make_resnet_pose_weights(n_layer: int = 18, filters=(16, 32, 64, 128, 256), decoder_filters=(256, 256), seed: int = 0,
+                             gain: float = 0.35):
+    """Two dicts (encoder, decoder) keyed like the state_dicts of the reference's ResNetEncoder(n_layer, use_batch_norm=True) /
+    PoseDecoder(n_filters=decoder_filters, use_batch_norm=True) (src/networks.py:674-996, 1992-2075; no `module.` prefix), every
+    block with its `projection.conv.weight`, used or not.  Conv weights: xavier normal (x gain).  BatchNorm2d as
+    make_posenet_weights: gamma in [0.5, 1.5], beta and running mean 0.2 N(0, 1), running variance in [0.25, 1.75], with
+    max(1, f // 32) channels of every f-channel layer at 1e-3 (eps = 1e-5 is 1 % of it: a forward that drops eps is 0.5 % off
+    there).  Such a channel amplifies 30-fold and a block ADDS its input to its output, so the activations' size is exponential
+    in the gain along 17 or 33 convs (gain 0.5 reaches 1e3 at 34 layers, 0.7 reaches 1e7): fewer such channels than the plain
+    network's two per layer, the second conv of every block and the projections at half the gain, and gain = 0.35 keep the
+    activations O(1) to O(100) and the pose vector between 1e-3 and a few radians / metres at both depths, full and narrow."""
+    if n_layer not in RESNET_BLOCKS or len(filters) != 5:
+        raise ValueError(f"make_resnet_pose_weights: n_layer 18 or 34 and five filter counts, got {n_layer}, {tuple(filters)}")
+    enc, dec = {}, {}
+
+    def conv_bn(sd, prefix, f, cin, k, scale=1.0):
+        sd[f"{prefix}.conv.weight"] = scale * gain * _xavier_normal(f"resnet{n_layer}/{prefix}.conv.weight", (f, cin, k, k), seed)
+        g = _rng((seed << 32) ^ zlib.crc32(f"resnet{n_layer}/{prefix}.batch_norm".encode()))
+        var = 0.25 + 1.5 * g.random(f)
+        var[g.choice(f, size=max(1, f // 32), replace=False)] = 1e-3
+        sd[f"{prefix}.batch_norm.weight"] = torch.from_numpy((0.5 + g.random(f)).astype(np.float32))
+        sd[f"{prefix}.batch_norm.bias"] = torch.from_numpy((0.2 * g.standard_normal(f)).astype(np.float32))
+        sd[f"{prefix}.batch_norm.running_mean"] = torch.from_numpy((0.2 * g.standard_normal(f)).astype(np.float32))
+        sd[f"{prefix}.batch_norm.running_var"] = torch.from_numpy(var.astype(np.float32))
+        sd[f"{prefix}.batch_norm.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    conv_bn(enc, "conv1", filters[0], 6, 7)
+    cin = filters[0]
+    for stage, (count, f) in enumerate(zip(RESNET_BLOCKS[n_layer], filters[1:]), 2):
+        for b in range(count):
+            prefix = f"blocks{stage}.{b}"
+            conv_bn(enc, prefix + ".conv1", f, cin, 3)
+            conv_bn(enc, prefix + ".conv2", f, f, 3, scale=0.5)
+            enc[prefix + ".projection.conv.weight"] = 0.5 * gain * _xavier_normal(f"resnet{n_layer}/{prefix}.projection.conv.weight",
+                                                                                  (f, cin, 1, 1), seed)
+            cin = f
+    for i, f in enumerate(decoder_filters):
+        conv_bn(dec, f"conv.{i}", f, cin, 3)
+        cin = f
+    dec[f"conv.{len(decoder_filters)}.conv.weight"] = gain * _xavier_normal(f"resnet{n_layer}/conv.{len(decoder_filters)}.conv.weight",
+                                                                            (6, cin, 1, 1), seed)
+    return enc, dec

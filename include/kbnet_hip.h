@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define KBN_ABI_VERSION 9
+#define KBN_ABI_VERSION 10
 
 typedef void* kbn_stream_t; /* hipStream_t */
 
@@ -606,6 +606,37 @@ int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src, const floa
  * atomics, and the mean is taken before the 6 x channels product (the conv of the mean is the mean of the conv). */
 int kbn_pose_head_forward(const float* latent, long long latent_batch_stride, const float* weight, float* pose,
                           float* dof, int n, int channels, int height, int width, kbn_stream_t stream);
+
+/* ------------------------------------------------- ResNet pose networks (eval mode) ----
+ * PoseNetModel(encoder_type='resnet18' | 'resnet34')   reference src/posenet_model.py:55-87 (what src/kbnet.py:221-226 trains)
+ *   networks.ResNetEncoder                             reference src/networks.py:674-996
+ *     conv1 7 x 7 stride 2, MaxPool2d(3, stride 2, padding 1), blocks2 .. blocks5 of net_utils.ResNetBlock
+ *   net_utils.ResNetBlock                              reference src/net_utils.py:572-667
+ *     act(act(bn(conv2(act(bn(conv1(x)))))) + X), X = x, or a 1 x 1 conv of x at the block's stride when the shape differs
+ *   networks.PoseDecoder, n_filters = [256, 256]       reference src/networks.py:1992-2075
+ *     two 3 x 3 stride-2 convs (BatchNorm2d, activation) before the 1 x 1 conv that kbn_pose_head_forward takes
+ *
+ * kbn_conv2d_affine_forward: v = (sum_c,ky,kx W[o, c, ky, kx] in[n, c, s oy + ky - k/2, s ox + kx - k/2]) * scale[o] + shift[o];
+ * v = act(v) when apply_activation; with `residual` (N x out_channels x OH x OW, frames residual_batch_stride elements apart,
+ * or NULL) v = v + residual, and v = act(v) once more when apply_activation; act = max(v, slope v).  kernel_size in {1, 3, 7},
+ * stride s in {1, 2}, padding k / 2, OH = ceil(in_h / s), OW = ceil(in_w / s); otherwise the contract of
+ * kbn_conv2d_s2_affine_forward: one or two KBN_SRC_TENSOR sources, any channel counts, taps outside the image zero, scale
+ * applied to the finished sum (the projection passes scale 1, shift 0), every output pixel a function of its frame and the
+ * weights alone.  The packed weight is this entry's own (another K chunk than kbn_conv2d_s2_affine_pack_weight's). */
+size_t kbn_conv2d_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
+int kbn_conv2d_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
+                                  int kernel_size, kbn_stream_t stream);
+int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, const float* packed_weight, const float* scale,
+                              const float* shift, const float* residual, long long residual_batch_stride, float* out,
+                              long long out_batch_stride, int n, int out_channels, int kernel_size, int stride,
+                              int in_height, int in_width, int apply_activation, float negative_slope,
+                              kbn_stream_t stream);
+
+/* torch.nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (reference src/networks.py:747): in N x channels x height x width ->
+ * out N x channels x ceil(height / 2) x ceil(width / 2), frames in_batch_stride / out_batch_stride elements apart.  Taps
+ * outside the image never win; a NaN in the window is the result, as in torch. */
+int kbn_maxpool3x3s2_forward(const float* in, long long in_batch_stride, float* out, long long out_batch_stride, int n,
+                             int channels, int height, int width, kbn_stream_t stream);
 
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:

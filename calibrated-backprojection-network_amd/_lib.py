@@ -22,7 +22,7 @@ KBN_SRC_TENSOR, KBN_SRC_COORDS, KBN_SRC_XYZ, KBN_SRC_PAIR = 0, 1, 2, 3
 KBN_ACT_ELU, KBN_ACT_SIGMOID = 1, 2
 KBN_RESIZE_NONE, KBN_RESIZE_NEAREST = 0, 1
 KBN_MAX_SRC = 3
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class KbnError(RuntimeError):
@@ -99,6 +99,7 @@ SIGNATURES = {
     "kbn_preprocess_forward": (_I, [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _F, _I, _P]),
     "kbn_eval_accumulate": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     "kbn_photometric_loss_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kbn_photometric_loss_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "kbn_conv2d_s2_affine_packed_weight_bytes": (C.c_size_t, [_I, _I, _I]),
     "kbn_conv2d_s2_affine_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "kbn_conv2d_s2_affine_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P]),

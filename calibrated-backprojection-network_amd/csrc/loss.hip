@@ -21,67 +21,12 @@
 // Addressing: a sample position comes from a division by z + 1e-7 and may be huge, negative, infinite or NaN.  It is
 // clamped as a float with comparisons that send NaN to 0, converted, and then clamped AGAIN as an integer into
 // [0, W-1] x [0, H-1]; every other address is a function of the tile index alone.
-#include <math.h>
-
-#include "kbn_common.h"
+#include "loss_common.h"   // K^-1, T and the sample position: shared with loss_backward.hip
 
 namespace kbn {
 
-constexpr int LS_TW = 64, LS_TH = 16, LS_ZW = LS_TW + 2, LS_ZH = LS_TH + 2, LS_ZN = LS_ZW * LS_ZH;
+constexpr int LS_ZW = LS_TW + 2, LS_ZH = LS_TH + 2, LS_ZN = LS_ZW * LS_ZH;   // the tile and a one-pixel halo
 constexpr int LS_ROWS = LS_TH / 4;   // SSIM: one thread takes a column strip of 4 output rows
-
-// how many pixels of the H-long (W-long) output axis torch's nearest interpolation maps to score `s` of the
-// (size - 2)-long SSIM axis: interpolate(scores, size, mode='nearest'), reference src/losses.py:58
-__device__ __forceinline__ int ssim_axis_weight(int s, int size) {
-    int cnt = 0;
-    for (int d = s; d <= s + 3 && d < size; ++d) cnt += nearest_src_index(d, size - 2, size) == s;
-    return cnt;
-}
-
-// K^-1 and the top three rows of (K | 0) * pose, in fp64 from the fp32 inputs, rounded once
-__device__ __forceinline__ void loss_kinv(const float* __restrict__ k, float* kinv) {
-    const double A = k[0], B = k[1], C = k[2], D = k[3], E = k[4], F = k[5], G = k[6], H = k[7], I = k[8];
-    const double c00 = E * I - F * H, c01 = -(D * I - F * G), c02 = D * H - E * G;
-    const double r = 1.0 / (A * c00 + B * c01 + C * c02);
-    kinv[0] = (float)(c00 * r);
-    kinv[1] = (float)(-(B * I - C * H) * r);
-    kinv[2] = (float)((B * F - C * E) * r);
-    kinv[3] = (float)(c01 * r);
-    kinv[4] = (float)((A * I - C * G) * r);
-    kinv[5] = (float)(-(A * F - C * D) * r);
-    kinv[6] = (float)(c02 * r);
-    kinv[7] = (float)(-(A * H - B * G) * r);
-    kinv[8] = (float)((A * E - B * D) * r);
-}
-__device__ __forceinline__ void loss_projection(const float* __restrict__ k, const float* __restrict__ pose, float* t) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            t[i * 4 + j] = (float)((double)k[i * 3] * pose[j] + (double)k[i * 3 + 1] * pose[4 + j] + (double)k[i * 3 + 2] * pose[8 + j]);
-}
-
-// pixel (x, y) at depth z -> the un-normalised, border-clamped sample position torch's grid_sample arrives at
-// (align_corners=True), in the reference's fp32 operation order: divide by size - 1, 2 (t - 0.5), ((g + 1) / 2) (size - 1)
-__device__ __forceinline__ void loss_sample_position(const float* kinv, const float* t, float x, float y, float z, float wm1, float hm1,
-                                                     float& ix, float& iy) {
-    const float px = fmaf(kinv[1], y, kinv[0] * x) + kinv[2];
-    const float py = fmaf(kinv[4], y, kinv[3] * x) + kinv[5];
-    const float pz = fmaf(kinv[7], y, kinv[6] * x) + kinv[8];
-    const float X = px * z, Y = py * z, Z = pz * z;
-    const float q0 = fmaf(t[2], Z, fmaf(t[1], Y, t[0] * X)) + t[3];
-    const float q1 = fmaf(t[6], Z, fmaf(t[5], Y, t[4] * X)) + t[7];
-    const float q2 = fmaf(t[10], Z, fmaf(t[9], Y, t[8] * X)) + t[11];
-    const float d = q2 + 1e-7f;
-    const float gx = 2.0f * (q0 / d / wm1 - 0.5f);
-    const float gy = 2.0f * (q1 / d / hm1 - 0.5f);
-    ix = ((gx + 1.0f) / 2.0f) * wm1;
-    iy = ((gy + 1.0f) / 2.0f) * hm1;
-    ix = ix >= 0.f ? ix : 0.f;       // false for NaN: NaN -> 0
-    iy = iy >= 0.f ? iy : 0.f;
-    ix = ix <= wm1 ? ix : wm1;
-    iy = iy <= hm1 ? iy : hm1;
-}
 
 // sums[n * 8 + k] += { sum |image01 - image0|, sum |image02 - image0|, sum ssim01, sum ssim02, sum v |sparse - depth|, sum v,
 //                      sum wx |dx depth|, sum wy |dy depth| }
@@ -149,16 +94,10 @@ __global__ __launch_bounds__(256) void photometric_loss_kernel(
             if (Y >= 0 && Y < H && X >= 0 && X < W) {
                 float ix, iy;
                 loss_sample_position(kinv, t, (float)X, (float)Y, s_depth[e], wm1, hm1, ix, iy);
-                const float fx0 = floorf(ix), fy0 = floorf(iy), fx1 = fx0 + 1.0f, fy1 = fy0 + 1.0f;
-                float wnw = (fx1 - ix) * (fy1 - iy), wne = (ix - fx0) * (fy1 - iy);
-                float wsw = (fx1 - ix) * (iy - fy0), wse = (ix - fx0) * (iy - fy0);
-                // ix, iy are finite and inside [0, W-1] x [0, H-1] here; the integer clamp makes the addresses safe whatever they are
-                int xa = (int)fx0, ya = (int)fy0;
-                xa = xa < 0 ? 0 : (xa > W - 1 ? W - 1 : xa);
-                ya = ya < 0 ? 0 : (ya > H - 1 ? H - 1 : ya);
-                int xb = xa + 1, yb = ya + 1;
-                if (xb > W - 1) { xb = W - 1; wne = 0.f; wse = 0.f; }   // torch skips taps outside the image
-                if (yb > H - 1) { yb = H - 1; wsw = 0.f; wse = 0.f; }
+                // ix, iy are finite and inside [0, W-1] x [0, H-1] here; loss_taps clamps the addresses again as integers
+                const LossTaps tp = loss_taps(ix, iy, W, H);
+                const int xa = tp.xa, xb = tp.xb, ya = tp.ya, yb = tp.yb;
+                const float wnw = tp.wnw, wne = tp.wne, wsw = tp.wsw, wse = tp.wse;
                 const long long oa = (long long)ya * W, ob = (long long)yb * W;
                 const float* s = src;
                 v0 = s[oa + xa] * wnw + s[oa + xb] * wne + s[ob + xa] * wsw + s[ob + xb] * wse; s += HW;

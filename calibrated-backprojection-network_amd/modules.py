@@ -1451,13 +1451,18 @@ class KBNetModel(object):
 
     def compute_loss(self, image0=None, image1=None, image2=None, output_depth0=None, sparse_depth0=None, validity_map_depth0=None,
                      intrinsics=None, pose01=None, pose02=None, w_color=0.15, w_structure=0.95, w_sparse_depth=0.60, w_smoothness=0.04):
-        """The FORWARD VALUE of the reference's objective (src/kbnet_model.py:188-304): warp image1 / image2 into image0's view with
-        the predicted depth and the relative poses, then colour L1 + SSIM + sparse-depth L1 + edge-aware smoothness -- a quality score
-        that needs no ground truth.  Returns (loss, loss_info) with the reference's keys (0-dim fp32 tensors and the two warped
-        images), plus loss_info['per_frame']: N x 4 fp64, the (colour, structure, sparse depth, smoothness) of each frame.  One
-        kernel launch (ops.photometric_loss) and a few scalar torch ops on its N x 8 sums; nothing synchronises with the host.
-        A frame without a valid sparse point makes the sparse-depth term (and the loss) NaN, as in the reference.  There is no
-        backward pass: the HIP path does not train."""
+        """The reference's objective (src/kbnet_model.py:188-304): warp image1 / image2 into image0's view with the predicted depth
+        and the relative poses, then colour L1 + SSIM + sparse-depth L1 + edge-aware smoothness -- a quality score that needs no
+        ground truth, and a loss to train against.  Returns (loss, loss_info) with the reference's keys (0-dim fp32 tensors and the
+        two warped images), plus loss_info['per_frame']: N x 4 fp64, the (colour, structure, sparse depth, smoothness) of each frame.
+        One kernel launch (ops.photometric_loss) and a few scalar torch ops on its N x 8 sums; nothing synchronises with the host.
+        A frame without a valid sparse point makes the sparse-depth term (and the loss) NaN, as in the reference.
+
+        Differentiable with respect to output_depth0, pose01 and pose02, what the reference trains through: `loss.backward()` is one
+        more launch (ops.photometric_loss_backward) and nothing image-sized is kept for it beyond the inputs themselves.  The
+        gradient reaches whatever torch graph produced the depth and the poses (ops.pose_matrix included).  The images, the sparse
+        depth, the validity map and the intrinsics are data: one that requires grad raises KbnError.  The warped images in loss_info
+        are for logging and carry no gradient (the reference's do; nothing trains through them).  No double backward."""
         given = {"image0": image0, "image1": image1, "image2": image2, "output_depth0": output_depth0, "sparse_depth0": sparse_depth0,
                  "validity_map_depth0": validity_map_depth0, "intrinsics": intrinsics, "pose01": pose01, "pose02": pose02}
         missing = [k for k, v in given.items() if v is None]

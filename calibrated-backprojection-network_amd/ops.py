@@ -1285,8 +1285,69 @@ def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate
     return torch.stack([mean[:, 0], mean[:, 1].sqrt(), mean[:, 2], mean[:, 3].sqrt()], dim=1)
 
 
-# ------------------------------------------------------------------ forward value of the objective
+# ------------------------------------------------------------------ the objective: its sums and their gradient
 _LOSS_ARGS = ("image0", "image1", "image2", "output_depth", "sparse_depth", "validity_map", "intrinsics", "pose01", "pose02")
+_LOSS_TRAINED = ("output_depth", "pose01", "pose02")   # what the reference trains through; everything else is data
+
+
+def _loss_inputs(fn: str, tensors):
+    """The argument checks `photometric_loss` and `photometric_loss_backward` share -> (n, h, w, the nine dense tensors)."""
+    for t, name in zip(tensors, _LOSS_ARGS):
+        if not isinstance(t, torch.Tensor):
+            raise KbnError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
+    image0 = tensors[0]
+    if image0.dim() != 4 or image0.shape[1] != 3:
+        raise KbnError(f"{fn}: image0 must be N x 3 x H x W, got {tuple(image0.shape)}")
+    n, _, h, w = image0.shape
+    if n < 1 or h < 3 or w < 3:
+        raise KbnError(f"{fn}: needs at least one frame of at least 3 x 3 pixels (SSIM pools 3 x 3 windows), got {tuple(image0.shape)}")
+    want = {"image1": (n, 3, h, w), "image2": (n, 3, h, w), "output_depth": (n, 1, h, w), "sparse_depth": (n, 1, h, w),
+            "validity_map": (n, 1, h, w), "intrinsics": (n, 3, 3), "pose01": (n, 4, 4), "pose02": (n, 4, 4)}
+    for t, name in zip(tensors, _LOSS_ARGS):
+        if name in want and tuple(t.shape) != want[name]:
+            raise KbnError(f"{fn}: {name} must be {want[name]} beside image0 {tuple(image0.shape)}, got {tuple(t.shape)}")
+    if torch.is_grad_enabled():
+        for t, name in zip(tensors, _LOSS_ARGS):
+            if name not in _LOSS_TRAINED and t.requires_grad:
+                raise KbnError(f"{fn}: {name} requires grad, but it is data and gets no gradient (gradients exist for "
+                               + ", ".join(_LOSS_TRAINED) + "); detach it")
+    for t, name in zip(tensors, _LOSS_ARGS):
+        _require(t, name)
+    return n, h, w, tuple(t.detach().contiguous() for t in tensors)
+
+
+def _photometric_loss_launch(n, h, w, dense, return_images):
+    lib = _lib.load()
+    i0, i1, i2, d, s, v, k, p1, p2 = dense
+    sums = torch.empty((n, 8), device=i0.device, dtype=torch.float64)   # the entry zeroes it on the stream
+    w1 = torch.empty_like(i0) if return_images else None
+    w2 = torch.empty_like(i0) if return_images else None
+    check(lib.kbn_photometric_loss_forward(i0.data_ptr(), i1.data_ptr(), i2.data_ptr(), d.data_ptr(), s.data_ptr(), v.data_ptr(),
+                                           k.data_ptr(), p1.data_ptr(), p2.data_ptr(), sums.data_ptr(),
+                                           w1.data_ptr() if return_images else None, w2.data_ptr() if return_images else None,
+                                           n, h, w, _stream()), "kbn_photometric_loss_forward")
+    return (sums, w1, w2) if return_images else sums
+
+
+class _PhotometricLoss(torch.autograd.Function):
+    """The N x 8 sums as a differentiable node: forward is the forward launch, backward one launch of
+    kbn_photometric_loss_backward.  Saved for backward: the nine inputs, nothing the forward computed."""
+
+    @staticmethod
+    def forward(ctx, shape, return_images, *tensors):
+        ctx.save_for_backward(*tensors)
+        out = _photometric_loss_launch(*shape, tuple(t.detach().contiguous() for t in tensors), return_images)
+        if return_images:
+            ctx.mark_non_differentiable(out[1], out[2])   # logging outputs: nothing trains through the warped images
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sums, *_):
+        grads = photometric_loss_backward(*ctx.saved_tensors, grad_sums)
+        need = ctx.needs_input_grad[2:]
+        by_name = dict(zip(_LOSS_TRAINED, grads))
+        return (None, None) + tuple(by_name[name] if name in by_name and need[i] else None for i, name in enumerate(_LOSS_ARGS))
 
 
 @_on_tensor_device
@@ -1296,33 +1357,54 @@ def photometric_loss(image0, image1, image2, output_depth, sparse_depth, validit
     {sum |image01 - image0|, sum |image02 - image0|, sum ssim01, sum ssim02, sum v |sparse - depth|, sum v, sum wx |dx depth|,
     sum wy |dy depth|} per frame (kbn_photometric_loss_forward), where image01 / image02 are image1 / image2 sampled where the
     depth and the relative poses put each pixel of image0.  `return_images`: also the two warped images (N x 3 x H x W), which the
-    reference hands back for logging; without it nothing image-sized is written."""
+    reference hands back for logging; without it nothing image-sized is written.
+
+    Differentiable with respect to output_depth, pose01 and pose02 (what the reference trains through): when grad mode is on and
+    one of them requires grad, the sums come from an autograd node whose backward is one launch (`photometric_loss_backward`) and
+    which saves its inputs only.  The warped images are outputs for logging and carry no gradient.  Any other argument that
+    requires grad is an error, not a silent None."""
+    tensors = (image0, image1, image2, output_depth, sparse_depth, validity_map, intrinsics, pose01, pose02)
+    n, h, w, dense = _loss_inputs("photometric_loss", tensors)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (output_depth, pose01, pose02)):
+        return _PhotometricLoss.apply((n, h, w), bool(return_images), *tensors)
+    return _photometric_loss_launch(n, h, w, dense, return_images)
+
+
+@_on_tensor_device
+def photometric_loss_backward(image0, image1, image2, output_depth, sparse_depth, validity_map, intrinsics, pose01, pose02, grad_sums,
+                              out=None):
+    """The gradient of `photometric_loss`'s sums, in one kernel (kbn_photometric_loss_backward): `grad_sums` (N x 8, the gradient
+    of the sums) -> (grad_depth N x 1 x H x W, grad_pose01, grad_pose02 N x 4 x 4), fp32.  The kernel reduces the gradient with
+    respect to T = rows 0-2 of (K | 0) pose in fp64 (N x 2 x 12); grad_pose[:3] = K^T grad_T is formed here in fp64 torch on those
+    24 numbers per frame and rounded once; row 3 of a pose gradient is zero.  `out`: (grad_depth, grad_T) buffers to write
+    into, an fp32 N x 1 x H x W and an fp64 N x 2 x 12 device tensor, both contiguous."""
     lib = _lib.load()
     tensors = (image0, image1, image2, output_depth, sparse_depth, validity_map, intrinsics, pose01, pose02)
-    for t, name in zip(tensors, _LOSS_ARGS):
-        if not isinstance(t, torch.Tensor):
-            raise KbnError(f"photometric_loss: {name} must be a tensor, got {type(t).__name__}")
-    if image0.dim() != 4 or image0.shape[1] != 3:
-        raise KbnError(f"photometric_loss: image0 must be N x 3 x H x W, got {tuple(image0.shape)}")
-    n, _, h, w = image0.shape
-    if n < 1 or h < 3 or w < 3:
-        raise KbnError(f"photometric_loss: needs at least one frame of at least 3 x 3 pixels (SSIM pools 3 x 3 windows), got {tuple(image0.shape)}")
-    want = {"image1": (n, 3, h, w), "image2": (n, 3, h, w), "output_depth": (n, 1, h, w), "sparse_depth": (n, 1, h, w),
-            "validity_map": (n, 1, h, w), "intrinsics": (n, 3, 3), "pose01": (n, 4, 4), "pose02": (n, 4, 4)}
-    for t, name in zip(tensors, _LOSS_ARGS):
-        if name in want and tuple(t.shape) != want[name]:
-            raise KbnError(f"photometric_loss: {name} must be {want[name]} beside image0 {tuple(image0.shape)}, got {tuple(t.shape)}")
-    for t, name in zip(tensors, _LOSS_ARGS):
-        _require(t, name)
-    i0, i1, i2, d, s, v, k, p1, p2 = (t.contiguous() for t in tensors)
-    sums = torch.empty((n, 8), device=i0.device, dtype=torch.float64)   # the entry zeroes it on the stream
-    w1 = torch.empty_like(i0) if return_images else None
-    w2 = torch.empty_like(i0) if return_images else None
-    check(lib.kbn_photometric_loss_forward(i0.data_ptr(), i1.data_ptr(), i2.data_ptr(), d.data_ptr(), s.data_ptr(), v.data_ptr(),
-                                           k.data_ptr(), p1.data_ptr(), p2.data_ptr(), sums.data_ptr(),
-                                           w1.data_ptr() if return_images else None, w2.data_ptr() if return_images else None,
-                                           n, h, w, _stream()), "kbn_photometric_loss_forward")
-    return (sums, w1, w2) if return_images else sums
+    n, h, w, dense = _loss_inputs("photometric_loss_backward", tensors)
+    if not isinstance(grad_sums, torch.Tensor) or not grad_sums.is_cuda or not grad_sums.is_floating_point() or tuple(grad_sums.shape) != (n, 8):
+        raise KbnError(f"photometric_loss_backward: grad_sums must be a floating-point CUDA/HIP tensor of shape {(n, 8)}, got "
+                       + (f"{tuple(grad_sums.shape)} {grad_sums.dtype} on {grad_sums.device}" if isinstance(grad_sums, torch.Tensor)
+                          else type(grad_sums).__name__))
+    i0, i1, i2, d, s, v, k, p1, p2 = dense
+    gs = grad_sums.detach().to(torch.float64).contiguous()
+    if out is None:
+        grad_depth = torch.empty_like(d)                                          # every element is written by the kernel
+        grad_t = torch.empty((n, 2, 12), device=d.device, dtype=torch.float64)    # the entry zeroes it on the stream
+    else:
+        grad_depth, grad_t = out
+        _require(grad_depth, "out[0]", 4)
+        if tuple(grad_depth.shape) != (n, 1, h, w) or not grad_depth.is_contiguous():
+            raise KbnError(f"photometric_loss_backward: out[0] must be a contiguous {(n, 1, h, w)} tensor, got {tuple(grad_depth.shape)}")
+        if not isinstance(grad_t, torch.Tensor) or not grad_t.is_cuda or grad_t.dtype != torch.float64 or tuple(grad_t.shape) != (n, 2, 12) \
+                or not grad_t.is_contiguous():
+            raise KbnError(f"photometric_loss_backward: out[1] must be a contiguous float64 CUDA/HIP tensor of shape {(n, 2, 12)}")
+    check(lib.kbn_photometric_loss_backward(i0.data_ptr(), i1.data_ptr(), i2.data_ptr(), d.data_ptr(), s.data_ptr(), v.data_ptr(),
+                                            k.data_ptr(), p1.data_ptr(), p2.data_ptr(), gs.data_ptr(), grad_depth.data_ptr(),
+                                            grad_t.data_ptr(), n, h, w, _stream()), "kbn_photometric_loss_backward")
+    grad_pose = torch.zeros((2, n, 4, 4), device=d.device, dtype=torch.float64)
+    grad_pose[:, :, :3] = torch.matmul(k.double().transpose(1, 2)[None], grad_t.reshape(n, 2, 3, 4).transpose(0, 1))
+    grad_pose = grad_pose.float()
+    return grad_depth, grad_pose[0], grad_pose[1]
 
 
 def loss_terms(sums: torch.Tensor, height: int, width: int) -> torch.Tensor:

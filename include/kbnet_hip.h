@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define KBN_ABI_VERSION 10
+#define KBN_ABI_VERSION 11
 
 typedef void* kbn_stream_t; /* hipStream_t */
 
@@ -575,6 +575,26 @@ int kbn_photometric_loss_forward(const float* image0, const float* image1, const
                                  const float* pose01, const float* pose02, double* sums,
                                  float* image01, float* image02, int n, int height, int width,
                                  kbn_stream_t stream);
+
+/* ------------------------------------------------- gradient of the objective ----
+ * torch.autograd's backward of KBNetModel.compute_loss  reference src/kbnet_model.py:188-304
+ *   project_to_pixel: d = q2 + 1e-7, u = q0 / d, v = q1 / d   reference src/net_utils.py:1676-1704
+ *   grid_sample (bilinear, border: no gradient for a position on or beyond the border)
+ *                                                       reference src/net_utils.py:1706-1739
+ *   the four terms (abs: sgn(0) = 0; clamp passes the gradient on [0, 1])   reference src/losses.py:23-158
+ * with respect to what the reference trains through: output_depth and the two poses.  Inputs as
+ * kbn_photometric_loss_forward; grad_sums: N x 8 fp64, the gradient of that entry's sums (column 5,
+ * sum v, depends on nothing differentiable).  WRITES every element of grad_depth (N x 1 x H x W) once
+ * and ADDS INTO grad_proj[(n*2 + pair)*12 + i*4 + j] (fp64; the entry zeroes the buffer on `stream`
+ * first) the gradient with respect to T[i][j], T = rows 0-2 of (K | 0) pose of pair 0 (pose01) and
+ * 1 (pose02): grad_pose[0:3, :] = K^T grad_T, row 3 is zero.  One launch; allocates nothing, does not
+ * synchronise.  Sample positions of any value read inside the planes, as in the forward. */
+int kbn_photometric_loss_backward(const float* image0, const float* image1, const float* image2,
+                                  const float* output_depth, const float* sparse_depth,
+                                  const float* validity_map, const float* intrinsics,
+                                  const float* pose01, const float* pose02, const double* grad_sums,
+                                  float* grad_depth, double* grad_proj, int n, int height, int width,
+                                  kbn_stream_t stream);
 
 /* ------------------------------------------------- pose network (eval mode) ----
  * PoseNetModel.forward                                 reference src/posenet_model.py:95-112

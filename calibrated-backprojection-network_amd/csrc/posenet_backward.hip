@@ -1,0 +1,696 @@
+// posenet_backward.hip -- the backward pass of a PoseEncoder layer, and BatchNorm2d on batch statistics.
+//
+//   net_utils.Conv2d           reference src/net_utils.py:51-141    bias-free conv (stride 2, padding k / 2), BatchNorm2d, LeakyReLU
+//   networks.PoseEncoder       reference src/networks.py:536-671    seven of them; src/kbnet.py:392-453 trains through them
+//
+// Everything is fp32 in and out; the two matrix products run on v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 sums), the
+// per-channel sums of BatchNorm in fp64.  NO floating-point atomics: every sum has a fixed order, two runs give the same bits.
+//
+// conv_s2_bwd_data_kernel<KS, NB>: the gradient with respect to the conv's input, in GATHER form: the structure of
+//   conv_s2_affine_kernel (posenet.hip) with the roles turned round.
+//   M = every INPUT pixel of the batch, m = (frame * H + iy) * W + ix, 128 per workgroup;
+//   N = input channels, 16 NB per workgroup;   K = (output channel, ky, kx), OC k k, zero-padded to a multiple of 16.
+//   A[m][k] = g[frame, oc, (iy + k/2 - ky) / 2, (ix + k/2 - kx) / 2] where both numerators are even, non-negative and inside the
+//   output map, else 0 BY PREDICATE (no address outside the planes is formed into a load).  This is the PREDICATED form: all k k
+//   taps run and about three quarters of them multiply zeros (only taps of the pixel's parity meet it).
+//   B = the weight in [n-tile][K chunk][16][16 NB] order with k = (oc, tap) and the column = input channel
+//   (conv_s2_bwd_data_pack_kernel).  The epilogue writes channel c of the gradient to the first tensor (c < C0) or the second.
+//
+// conv_s2_bwd_weight_kernel<KS, MB>: the gradient with respect to the OIHW weight.
+//   M = output channels, 16 MB per workgroup;  N = (input channel, ky, kx) = the weight's flat inner index, 64 per workgroup;
+//   K = every OUTPUT pixel of the batch, 32 per chunk.  A[k][m] = g[pixel, oc] (contiguous along pixels), B[k][n] = the input
+//   at the tap (zero outside by predicate).  A thread's 8 columns are the same in every chunk: decoded once, before the K loop.
+//   grid.z workgroups SPLIT K: split z sums chunks [z cps, (z + 1) cps) into plane z of a scratch buffer and
+//   sum_splits_kernel adds the planes in split order (the KSPLIT + ksplit_reduce_kernel pattern of conv_split.hip); one split
+//   writes the weight gradient directly.  Wave w owns columns 16 w .. 16 w + 15 times all MB row blocks.
+//   LDS pitches are = 17 mod 32: the staging stores (a lane per pixel = per row) fall on 32 distinct banks, the fragment reads
+//   (16 consecutive floats per row, two rows per half-wave) collide on one bank only.
+//
+// bn_stats_kernel, bn_bwd_sums_kernel: one workgroup per channel, fp64, a fixed tree.  bn_act_kernel, bn_bwd_apply_kernel: elementwise.
+#include "kbn_common.h"
+
+namespace kbn {
+namespace {
+
+// ---- fixed-order block sum of two doubles (256 threads) -----------------------------------------------------------------
+constexpr int RT = 256;
+
+__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds /* 2 * RT / 64 doubles */) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        a += __shfl_xor(a, o);
+        b += __shfl_xor(b, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();   // the previous use of `lds` is over
+    if (lane == 0) {
+        lds[wave] = a;
+        lds[RT / 64 + wave] = b;
+    }
+    __syncthreads();
+    a = 0.0;
+    b = 0.0;
+#pragma unroll
+    for (int w = 0; w < RT / 64; ++w) {
+        a += lds[w];
+        b += lds[RT / 64 + w];
+    }
+}
+
+// ---- data gradient ------------------------------------------------------------------------------------------------------
+constexpr int BD_BM = 128, BD_KC = 16, BD_AP = BD_BM + 16;
+
+__host__ __device__ inline int bd_nb(int c) { return c <= 16 ? 1 : (c <= 32 ? 2 : 4); }
+__host__ __device__ constexpr int bd_bp(int nb) { return nb == 1 ? 16 : 16 * nb + 16; }
+
+struct BdParams {
+    const float* g;
+    long long gbs;
+    const float* wp;
+    float* dst0;
+    float* dst1;
+    long long bs0, bs1;
+    int C0, Ctot;
+    int N, OC, H, W, OH, OW;
+    int M;        // N * H * W
+    int K, nchunks;
+};
+
+template <int KS, int NB>
+__global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p) {
+    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = bd_bp(NB);
+    __shared__ float As[2][BD_KC * BD_AP];
+    __shared__ float Bs[2][BD_KC * BP];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int mt = blockIdx.x, nt = blockIdx.y;
+    const int HW = p.H * p.W, OHW = p.OH * p.OW;
+
+    const int pm = tid & (BD_BM - 1);
+    const int khalf = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int m = mt * BD_BM + pm;
+    const bool mvalid = m < p.M;
+    int fn = 0, iyp = 0, ixp = 0;
+    if (mvalid) {
+        fn = m / HW;
+        const int rem = m - fn * HW;
+        const int iy = rem / p.W, ix = rem - iy * p.W;
+        iyp = iy + PAD;
+        ixp = ix + PAD;
+    }
+    const float* gf = p.g + (long long)fn * p.gbs;
+    const float* wtile = p.wp + (long long)nt * p.nchunks * (BD_KC * BN);
+
+    float va[8];
+    float vb[NB];
+    auto load_chunk = [&](int chunk) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = chunk * BD_KC + khalf + 2 * j;      // wave-uniform
+            const int oc = k / KK, t = k - oc * KK;
+            const int ky = t / KS, kx = t - ky * KS;
+            const int ty = iyp - ky, tx = ixp - kx;
+            float v = 0.f;
+            if (mvalid && k < p.K && ty >= 0 && tx >= 0 && ((ty | tx) & 1) == 0) {
+                const int oy = ty >> 1, ox = tx >> 1;
+                if (oy < p.OH && ox < p.OW) v = gf[(long long)oc * OHW + oy * p.OW + ox];
+            }
+            va[j] = v;
+        }
+        const float* wc = wtile + (long long)chunk * (BD_KC * BN);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) vb[j] = wc[tid + 256 * j];
+    };
+    auto store_chunk = [&](int buf) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) As[buf][(khalf + 2 * j) * BD_AP + pm] = va[j];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int e = tid + 256 * j;
+            Bs[buf][(e / BN) * BP + (e % BN)] = vb[j];
+        }
+    };
+
+    f32x4 acc[2][NB];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[mi][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    load_chunk(0);
+    store_chunk(0);
+    __syncthreads();
+    for (int chunk = 0; chunk < p.nchunks; ++chunk) {
+        const int buf = chunk & 1;
+        const bool more = chunk + 1 < p.nchunks;
+        if (more) load_chunk(chunk + 1);
+        const float* Ab = As[buf] + lk * BD_AP + wave * 32 + li;
+        const float* Bb = Bs[buf] + lk * BP + li;
+#pragma unroll
+        for (int k4 = 0; k4 < BD_KC / 4; ++k4) {
+            float a[2], b[NB];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * BD_AP + mi * 16];
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) b[nb] = Bb[k4 * 4 * BP + nb * 16];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb)
+                    acc[mi][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi], b[nb], acc[mi][nb], 0, 0, 0);
+        }
+        if (more) store_chunk(buf ^ 1);
+        __syncthreads();
+    }
+
+    // lane (li, lk) holds pixels 4 lk + r (r < 4) of each m-block for input channel li of each n-block
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        const int c = nt * BN + nb * 16 + li;
+        if (c >= p.Ctot) continue;
+        const bool first = c < p.C0;
+        float* base = first ? p.dst0 + (long long)c * HW : p.dst1 + (long long)(c - p.C0) * HW;
+        const long long bs = first ? p.bs0 : p.bs1;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int om = mt * BD_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
+                if (om >= p.M) continue;
+                const int n = om / HW, rem = om - n * HW;
+                base[(long long)n * bs + rem] = acc[mi][nb][r];
+            }
+        }
+    }
+}
+
+// OIHW -> [n-tile of input channels][k = (oc, tap), padded to chunks][16 NB input channels]
+__global__ void conv_s2_bwd_data_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int cin, int kk, int K,
+                                             int nchunks, int nb, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int bn = 16 * nb;
+    const int col = (int)(i % bn);
+    const long long row = i / bn;
+    const int k = (int)(row % ((long long)nchunks * BD_KC));
+    const int nt = (int)(row / ((long long)nchunks * BD_KC));
+    const int c = nt * bn + col;
+    float v = 0.f;
+    if (c < cin && k < K) {
+        const int oc = k / kk, t = k - oc * kk;
+        v = w[((long long)oc * cin + c) * kk + t];
+    }
+    packed[i] = v;
+}
+
+template <int KS>
+void bwd_data_launch_nb(const BdParams& p, int nb, dim3 grid, hipStream_t stream) {
+    switch (nb) {
+        case 1: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 1>), grid, dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 2>), grid, dim3(256), 0, stream, p); break;
+        default: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 4>), grid, dim3(256), 0, stream, p); break;
+    }
+}
+
+// ---- weight gradient ----------------------------------------------------------------------------------------------------
+constexpr int BW_BN = 64, BW_KC = 32, BW_BP = BW_BN + 17;
+constexpr int BW_TARGET_WORKGROUPS = 512;   // two per CU of a 256-CU device; a constant, so that the split (and the bits) do not follow the device
+constexpr int BW_MIN_CHUNKS = 4, BW_MAX_SPLITS = 1024;
+
+__host__ __device__ inline int bw_mb(int oc) { return oc <= 16 ? 1 : (oc <= 32 ? 2 : 4); }
+__host__ __device__ constexpr int bw_ap(int mb) { return mb == 1 ? 49 : 16 * mb + 17; }   // = 17 mod 32
+
+struct BwParams {
+    const float* g;
+    long long gbs;
+    const float* src0;
+    const float* src1;
+    long long bs0, bs1;
+    int C0, Ctot;
+    float* out;   // the weight gradient (one split) or the scratch planes
+    int N, OC, H, W, OH, OW;
+    int M;        // N * OH * OW
+    int CK;       // Ctot k k
+    int nchunks, cps;   // chunks of 32 pixels; chunks per split
+};
+
+template <int KS, int MB>
+__global__ __launch_bounds__(256) void conv_s2_bwd_weight_kernel(const BwParams p) {
+    constexpr int KK = KS * KS, PAD = KS / 2, BM = 16 * MB, AP = bw_ap(MB);
+    constexpr int AJ = BM / 8;    // rows of A a thread stages per chunk
+    __shared__ float As[2][BW_KC * AP];
+    __shared__ float Bs[2][BW_KC * BW_BP];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, lk = lane >> 4;
+    const int nt = blockIdx.x, mt = blockIdx.y, split = blockIdx.z;
+    const int HW = p.H * p.W, OHW = p.OH * p.OW;
+    const int px = tid & (BW_KC - 1), cr = tid >> 5;   // this thread's pixel of a chunk; its first row / column
+
+    // the 8 columns (input channel, tap) this thread gathers, fixed over the K loop: c << 6 | ky << 3 | kx, or -1
+    int cols[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int col = nt * BW_BN + cr + 8 * j;
+        if (col < p.CK) {
+            const int c = col / KK, t = col - c * KK;
+            const int ky = t / KS, kx = t - ky * KS;
+            cols[j] = (c << 6) | (ky << 3) | kx;
+        } else {
+            cols[j] = -1;
+        }
+    }
+
+    const int c_begin = split * p.cps;
+    const int c_end = min(p.nchunks, c_begin + p.cps);
+
+    float va[AJ], vb[8];
+    auto load_chunk = [&](int chunk) {
+        const int m = chunk * BW_KC + px;
+        const bool mvalid = m < p.M;
+        int fn = 0, rem = 0, iy0 = 0, ix0 = 0;
+        if (mvalid) {
+            fn = m / OHW;
+            rem = m - fn * OHW;
+            const int oy = rem / p.OW, ox = rem - oy * p.OW;
+            iy0 = 2 * oy - PAD;
+            ix0 = 2 * ox - PAD;
+        }
+        const float* gf = p.g + (long long)fn * p.gbs + rem;
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) {
+            const int oc = mt * BM + cr + 8 * j;
+            va[j] = (mvalid && oc < p.OC) ? gf[(long long)oc * OHW] : 0.f;
+        }
+        const float* f0 = p.src0 + (long long)fn * p.bs0;
+        const float* f1 = p.src1 ? p.src1 + (long long)fn * p.bs1 : nullptr;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e = cols[j];
+            const int c = e >> 6, iy = iy0 + ((e >> 3) & 7), ix = ix0 + (e & 7);
+            float v = 0.f;
+            if (mvalid && e >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
+                const float* plane = (c < p.C0) ? f0 + (long long)c * HW : f1 + (long long)(c - p.C0) * HW;
+                v = plane[iy * p.W + ix];
+            }
+            vb[j] = v;
+        }
+    };
+    auto store_chunk = [&](int buf) {
+#pragma unroll
+        for (int j = 0; j < AJ; ++j) As[buf][px * AP + cr + 8 * j] = va[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) Bs[buf][px * BW_BP + cr + 8 * j] = vb[j];
+    };
+
+    f32x4 acc[MB];
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi) acc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    if (c_begin < c_end) {
+        load_chunk(c_begin);
+        store_chunk(0);
+    }
+    __syncthreads();
+    for (int chunk = c_begin; chunk < c_end; ++chunk) {
+        const int buf = (chunk - c_begin) & 1;
+        const bool more = chunk + 1 < c_end;
+        if (more) load_chunk(chunk + 1);
+        const float* Ab = As[buf] + lk * AP + li;
+        const float* Bb = Bs[buf] + lk * BW_BP + wave * 16 + li;
+#pragma unroll
+        for (int k4 = 0; k4 < BW_KC / 4; ++k4) {
+            const float b = Bb[k4 * 4 * BW_BP];
+#pragma unroll
+            for (int mi = 0; mi < MB; ++mi)
+                acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ab[k4 * 4 * AP + mi * 16], b, acc[mi], 0, 0, 0);
+        }
+        if (more) store_chunk(buf ^ 1);
+        __syncthreads();
+    }
+
+    // lane (li, lk) holds output channels 4 lk + r of each row block for column li of this wave's 16
+    const int col = nt * BW_BN + wave * 16 + li;
+    if (col < p.CK) {
+        float* o = p.out + (long long)split * p.OC * p.CK + col;
+#pragma unroll
+        for (int mi = 0; mi < MB; ++mi) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int oc = mt * BM + mi * 16 + lk * 4 + r;
+                if (oc < p.OC) o[(long long)oc * p.CK] = acc[mi][r];
+            }
+        }
+    }
+}
+
+__global__ void sum_splits_kernel(const float* __restrict__ planes, float* __restrict__ out, long long total, int splits) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    float s = planes[i];
+    for (int z = 1; z < splits; ++z) s += planes[(long long)z * total + i];   // split order, always
+    out[i] = s;
+}
+
+template <int KS>
+void bwd_weight_launch_mb(const BwParams& p, int mb, dim3 grid, hipStream_t stream) {
+    switch (mb) {
+        case 1: hipLaunchKernelGGL((conv_s2_bwd_weight_kernel<KS, 1>), grid, dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((conv_s2_bwd_weight_kernel<KS, 2>), grid, dim3(256), 0, stream, p); break;
+        default: hipLaunchKernelGGL((conv_s2_bwd_weight_kernel<KS, 4>), grid, dim3(256), 0, stream, p); break;
+    }
+}
+
+struct BwPlan {
+    int ok, OH, OW, M, CK, nchunks, cps, splits, mb;
+    unsigned ntn, ntm;
+};
+
+bool ks_ok(int ks) { return ks == 3 || ks == 5 || ks == 7; }
+
+// `splits` <= 0: chosen here (enough workgroups for the chip, at least BW_MIN_CHUNKS chunks each); > 0: as asked, at most one per chunk
+BwPlan bwd_weight_plan(int n, int oc, int cin, int ks, int h, int w, int splits) {
+    BwPlan pl{};
+    if (n <= 0 || oc <= 0 || cin <= 0 || h <= 0 || w <= 0 || !ks_ok(ks)) return pl;
+    pl.OH = ceil_div(h, 2);
+    pl.OW = ceil_div(w, 2);
+    const long long M = (long long)n * pl.OH * pl.OW;
+    const long long CK = (long long)cin * ks * ks;
+    if (M > 0x7fffffffLL - BW_KC || CK > (1 << 24) || (long long)h * w > 0x7fffffffLL || (long long)oc * CK > 0x7fffffffLL) return pl;
+    pl.M = (int)M;
+    pl.CK = (int)CK;
+    pl.nchunks = ceil_div(pl.M, BW_KC);
+    pl.mb = bw_mb(oc);
+    pl.ntn = (unsigned)ceil_div(pl.CK, BW_BN);
+    pl.ntm = (unsigned)ceil_div(oc, 16 * pl.mb);
+    if (pl.ntm > 65535u) return pl;
+    if (splits <= 0) {
+        const long long tiles = (long long)pl.ntn * pl.ntm;
+        long long s = (BW_TARGET_WORKGROUPS + tiles - 1) / tiles;
+        s = s < pl.nchunks / BW_MIN_CHUNKS ? s : pl.nchunks / BW_MIN_CHUNKS;
+        splits = (int)(s < 1 ? 1 : s);
+    }
+    if (splits > BW_MAX_SPLITS) splits = BW_MAX_SPLITS;
+    if (splits > pl.nchunks) splits = pl.nchunks;
+    pl.cps = ceil_div(pl.nchunks, splits);
+    pl.splits = ceil_div(pl.nchunks, pl.cps);   // no empty split
+    pl.ok = 1;
+    return pl;
+}
+
+// ---- BatchNorm2d --------------------------------------------------------------------------------------------------------
+// mean and BIASED variance of channel blockIdx.x over N, H, W: two passes in fp64 (the mean, then the centred squares).
+__global__ __launch_bounds__(RT) void bn_stats_kernel(const float* __restrict__ x, long long bs, float* __restrict__ mean,
+                                                      float* __restrict__ var, int N, int HW) {
+    __shared__ double red[2 * RT / 64];
+    const int c = blockIdx.x;
+    const float* xc = x + (long long)c * HW;
+    double s = 0.0, unused = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const float* plane = xc + (long long)n * bs;
+        for (int i = threadIdx.x; i < HW; i += RT) s += (double)plane[i];
+    }
+    block_sum2(s, unused, red);
+    const double count = (double)N * (double)HW;
+    const double mu = s / count;
+    double q = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const float* plane = xc + (long long)n * bs;
+        for (int i = threadIdx.x; i < HW; i += RT) {
+            const double d = (double)plane[i] - mu;
+            q += d * d;
+        }
+    }
+    block_sum2(q, unused, red);
+    if (threadIdx.x == 0) {
+        mean[c] = (float)mu;
+        var[c] = (float)(q / count);
+    }
+}
+
+// y = act(u * scale[c] + shift[c])
+__global__ void bn_act_kernel(const float* __restrict__ u, long long ubs, const float* __restrict__ scale,
+                              const float* __restrict__ shift, float* __restrict__ y, long long ybs, int C, int HW, long long total,
+                              int act, float slope) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long plane = i / HW;
+    const int rem = (int)(i - plane * HW);
+    const int n = (int)(plane / C), c = (int)(plane - (long long)n * C);
+    float v = fmaf(u[(long long)n * ubs + (long long)c * HW + rem], scale[c], shift[c]);
+    if (act) v = leaky_relu(v, slope);
+    y[(long long)n * ybs + (long long)c * HW + rem] = v;
+}
+
+// g_z = g_y (z > 0 ? 1 : slope), z = u scale + shift exactly as bn_act_kernel forms it; xhat = (u - mean) rstd
+__device__ __forceinline__ float bn_gz(float u, float gy, float sc, float sh, int act, float slope) {
+    if (!act) return gy;
+    return fmaf(u, sc, sh) > 0.f ? gy : gy * slope;
+}
+
+// sums[c] = sum g_z, sums[C + c] = sum g_z xhat over N, H, W of channel c = blockIdx.x: fp64, a fixed tree
+__global__ __launch_bounds__(RT) void bn_bwd_sums_kernel(const float* __restrict__ u, long long ubs, const float* __restrict__ gy,
+                                                         long long gybs, const float* __restrict__ scale,
+                                                         const float* __restrict__ shift, const float* __restrict__ mean,
+                                                         const float* __restrict__ rstd, double* __restrict__ sums, int N, int C,
+                                                         int HW, int act, float slope) {
+    __shared__ double red[2 * RT / 64];
+    const int c = blockIdx.x;
+    const float sc = scale[c], sh = shift[c], mu = mean[c], rs = rstd[c];
+    double s1 = 0.0, s2 = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const float* up = u + (long long)n * ubs + (long long)c * HW;
+        const float* gp = gy + (long long)n * gybs + (long long)c * HW;
+        for (int i = threadIdx.x; i < HW; i += RT) {
+            const float uv = up[i];
+            const float gz = bn_gz(uv, gp[i], sc, sh, act, slope);
+            const float xh = (uv - mu) * rs;
+            s1 += (double)gz;
+            s2 += (double)gz * (double)xh;
+        }
+    }
+    block_sum2(s1, s2, red);
+    if (threadIdx.x == 0) {
+        sums[c] = s1;
+        sums[C + c] = s2;
+    }
+}
+
+// g_u = scale (g_z - (sum g_z + xhat sum g_z xhat) / count) on batch statistics; g_u = scale g_z on running ones
+__global__ void bn_bwd_apply_kernel(const float* __restrict__ u, long long ubs, const float* __restrict__ gy, long long gybs,
+                                    const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
+                                    const float* __restrict__ rstd, const double* __restrict__ sums, float* __restrict__ gu,
+                                    long long gubs, int C, int HW, long long total, double count, int act, float slope, int batch) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long plane = i / HW;
+    const int rem = (int)(i - plane * HW);
+    const int n = (int)(plane / C), c = (int)(plane - (long long)n * C);
+    const long long off = (long long)c * HW + rem;
+    const float uv = u[(long long)n * ubs + off];
+    const float sc = scale[c];
+    float gz = bn_gz(uv, gy[(long long)n * gybs + off], sc, shift[c], act, slope);
+    if (batch) {
+        const float m1 = (float)(sums[c] / count), m2 = (float)(sums[C + c] / count);
+        const float xh = (uv - mean[c]) * rstd[c];
+        gz = gz - fmaf(xh, m2, m1);
+    }
+    gu[(long long)n * gubs + off] = sc * gz;
+}
+
+bool elementwise_shape_ok(int n, int c, int h, int w, long long* total) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
+    const long long hw = (long long)h * w;
+    if (hw > 0x7fffffffLL || (long long)n * c > 0x7fffffffLL) return false;
+    *total = (long long)n * c * hw;
+    return *total <= 0x7fffffffLL * 256LL;
+}
+
+}  // namespace
+}  // namespace kbn
+
+using namespace kbn;
+
+extern "C" size_t kbn_conv2d_s2_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size) {
+    if (out_channels <= 0 || in_channels <= 0 || !ks_ok(kernel_size)) return 0;
+    const long long K = (long long)out_channels * kernel_size * kernel_size;
+    if (K > (1 << 24)) return 0;
+    const int nb = bd_nb(in_channels);
+    const long long floats = (long long)ceil_div(in_channels, 16 * nb) * round_up((int)K, BD_KC) * (16 * nb);
+    return (size_t)floats * sizeof(float);
+}
+
+extern "C" int kbn_conv2d_s2_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
+                                                       int kernel_size, kbn_stream_t stream) {
+    if (!weight || !packed) return KBN_ERR_INVALID_ARGUMENT;
+    if (out_channels <= 0 || in_channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
+    const size_t bytes = kbn_conv2d_s2_backward_data_packed_weight_bytes(out_channels, in_channels, kernel_size);
+    if (bytes == 0) return KBN_ERR_UNSUPPORTED;
+    const int kk = kernel_size * kernel_size, K = out_channels * kk;
+    const long long total = (long long)(bytes / sizeof(float));
+    hipLaunchKernelGGL(conv_s2_bwd_data_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       weight, packed, in_channels, kk, K, ceil_div(K, BD_KC), bd_nb(in_channels), total);
+    KBN_CHECK_LAUNCH();
+    return KBN_OK;
+}
+
+extern "C" int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad_out_batch_stride, const float* packed_weight,
+                                           float* grad_in0, long long grad_in0_batch_stride, int channels0, float* grad_in1,
+                                           long long grad_in1_batch_stride, int channels1, int n, int out_channels,
+                                           int kernel_size, int in_height, int in_width, kbn_stream_t stream) {
+    if (!grad_out || !packed_weight || !grad_in0) return KBN_ERR_INVALID_ARGUMENT;
+    if (n <= 0 || out_channels <= 0 || in_height <= 0 || in_width <= 0 || channels0 <= 0 || channels1 < 0) return KBN_ERR_INVALID_ARGUMENT;
+    if ((channels1 > 0) != (grad_in1 != nullptr)) return KBN_ERR_INVALID_ARGUMENT;
+    if (!ks_ok(kernel_size)) return KBN_ERR_UNSUPPORTED;
+    const long long HW = (long long)in_height * in_width;
+    const long long M = (long long)n * HW;
+    const long long K = (long long)out_channels * kernel_size * kernel_size;
+    if (M > 0x7fffffffLL - BD_BM || K > (1 << 24)) return KBN_ERR_UNSUPPORTED;
+    BdParams p{};
+    p.OH = ceil_div(in_height, 2);
+    p.OW = ceil_div(in_width, 2);
+    if (n > 1) {
+        if (grad_out_batch_stride < (long long)out_channels * p.OH * p.OW) return KBN_ERR_INVALID_ARGUMENT;
+        if (grad_in0_batch_stride < channels0 * HW) return KBN_ERR_INVALID_ARGUMENT;
+        if (channels1 > 0 && grad_in1_batch_stride < channels1 * HW) return KBN_ERR_INVALID_ARGUMENT;
+    }
+    p.g = grad_out;
+    p.gbs = grad_out_batch_stride;
+    p.wp = packed_weight;
+    p.dst0 = grad_in0;
+    p.dst1 = grad_in1;
+    p.bs0 = grad_in0_batch_stride;
+    p.bs1 = grad_in1_batch_stride;
+    p.C0 = channels0;
+    p.Ctot = channels0 + channels1;
+    p.N = n;
+    p.OC = out_channels;
+    p.H = in_height;
+    p.W = in_width;
+    p.M = (int)M;
+    p.K = (int)K;
+    p.nchunks = ceil_div((int)K, BD_KC);
+    const int nb = bd_nb(p.Ctot);
+    const unsigned ntn = (unsigned)ceil_div(p.Ctot, 16 * nb);
+    if (ntn > 65535u) return KBN_ERR_UNSUPPORTED;
+    const dim3 grid((unsigned)ceil_div((int)M, BD_BM), ntn);
+    switch (kernel_size) {
+        case 3: bwd_data_launch_nb<3>(p, nb, grid, (hipStream_t)stream); break;
+        case 5: bwd_data_launch_nb<5>(p, nb, grid, (hipStream_t)stream); break;
+        default: bwd_data_launch_nb<7>(p, nb, grid, (hipStream_t)stream); break;
+    }
+    KBN_CHECK_LAUNCH();
+    return KBN_OK;
+}
+
+extern "C" size_t kbn_conv2d_s2_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size,
+                                                              int in_height, int in_width, int splits) {
+    const BwPlan pl = bwd_weight_plan(n, out_channels, in_channels, kernel_size, in_height, in_width, splits);
+    if (!pl.ok || pl.splits <= 1) return 0;
+    return (size_t)pl.splits * out_channels * pl.CK * sizeof(float);
+}
+
+extern "C" int kbn_conv2d_s2_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out,
+                                             long long grad_out_batch_stride, float* grad_weight, int n, int out_channels,
+                                             int kernel_size, int in_height, int in_width, int splits, float* scratch,
+                                             size_t scratch_bytes, kbn_stream_t stream) {
+    if (!srcs || !grad_out || !grad_weight) return KBN_ERR_INVALID_ARGUMENT;
+    if (n_src < 1 || n_src > 2 || n <= 0 || out_channels <= 0 || in_height <= 0 || in_width <= 0) return KBN_ERR_INVALID_ARGUMENT;
+    if (!ks_ok(kernel_size)) return KBN_ERR_UNSUPPORTED;
+    BwParams p{};
+    int ctot = 0;
+    for (int s = 0; s < n_src; ++s) {
+        const kbn_conv_src& src = srcs[s];
+        if (src.kind != KBN_SRC_TENSOR) return KBN_ERR_UNSUPPORTED;
+        if (!src.data || src.channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
+        if (src.src_height != in_height || src.src_width != in_width) return KBN_ERR_INVALID_ARGUMENT;
+        if (src.batch_stride < (long long)src.channels * in_height * in_width && n > 1) return KBN_ERR_INVALID_ARGUMENT;
+        ctot += src.channels;
+    }
+    if (ctot >= (1 << 24)) return KBN_ERR_UNSUPPORTED;   // the column code keeps the channel above 6 bits of tap
+    const BwPlan pl = bwd_weight_plan(n, out_channels, ctot, kernel_size, in_height, in_width, splits);
+    if (!pl.ok) return KBN_ERR_UNSUPPORTED;
+    if (grad_out_batch_stride < (long long)out_channels * pl.OH * pl.OW && n > 1) return KBN_ERR_INVALID_ARGUMENT;
+    const long long total = (long long)out_channels * pl.CK;
+    if (pl.splits > 1 && (!scratch || scratch_bytes < (size_t)pl.splits * total * sizeof(float))) return KBN_ERR_INVALID_ARGUMENT;
+    p.g = grad_out;
+    p.gbs = grad_out_batch_stride;
+    p.src0 = srcs[0].data;
+    p.bs0 = srcs[0].batch_stride;
+    p.C0 = srcs[0].channels;
+    if (n_src == 2) { p.src1 = srcs[1].data; p.bs1 = srcs[1].batch_stride; }
+    p.Ctot = ctot;
+    p.out = pl.splits > 1 ? scratch : grad_weight;
+    p.N = n;
+    p.OC = out_channels;
+    p.H = in_height;
+    p.W = in_width;
+    p.OH = pl.OH;
+    p.OW = pl.OW;
+    p.M = pl.M;
+    p.CK = pl.CK;
+    p.nchunks = pl.nchunks;
+    p.cps = pl.cps;
+    const dim3 grid(pl.ntn, pl.ntm, (unsigned)pl.splits);
+    switch (kernel_size) {
+        case 3: bwd_weight_launch_mb<3>(p, pl.mb, grid, (hipStream_t)stream); break;
+        case 5: bwd_weight_launch_mb<5>(p, pl.mb, grid, (hipStream_t)stream); break;
+        default: bwd_weight_launch_mb<7>(p, pl.mb, grid, (hipStream_t)stream); break;
+    }
+    KBN_CHECK_LAUNCH();
+    if (pl.splits > 1) {
+        hipLaunchKernelGGL(sum_splits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch,
+                           grad_weight, total, pl.splits);
+        KBN_CHECK_LAUNCH();
+    }
+    return KBN_OK;
+}
+
+extern "C" int kbn_bn_stats_forward(const float* x, long long batch_stride, float* mean, float* var, int n, int channels,
+                                    int height, int width, kbn_stream_t stream) {
+    if (!x || !mean || !var) return KBN_ERR_INVALID_ARGUMENT;
+    long long total = 0;
+    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    const long long hw = (long long)height * width;
+    if (batch_stride < channels * hw && n > 1) return KBN_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)channels), dim3(RT), 0, (hipStream_t)stream, x, batch_stride, mean, var, n,
+                       (int)hw);
+    KBN_CHECK_LAUNCH();
+    return KBN_OK;
+}
+
+extern "C" int kbn_bn_act_forward(const float* u, long long u_batch_stride, const float* scale, const float* shift, float* y,
+                                  long long y_batch_stride, int n, int channels, int height, int width, int apply_activation,
+                                  float negative_slope, kbn_stream_t stream) {
+    if (!u || !scale || !shift || !y) return KBN_ERR_INVALID_ARGUMENT;
+    long long total = 0;
+    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    const long long hw = (long long)height * width;
+    if (n > 1 && (u_batch_stride < channels * hw || y_batch_stride < channels * hw)) return KBN_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(bn_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u, u_batch_stride,
+                       scale, shift, y, y_batch_stride, channels, (int)hw, total, apply_activation ? 1 : 0, negative_slope);
+    KBN_CHECK_LAUNCH();
+    return KBN_OK;
+}
+
+extern "C" int kbn_bn_act_backward(const float* u, long long u_batch_stride, const float* grad_y, long long grad_y_batch_stride,
+                                   const float* scale, const float* shift, const float* mean, const float* rstd, double* sums,
+                                   float* grad_u, long long grad_u_batch_stride, int n, int channels, int height, int width,
+                                   int apply_activation, float negative_slope, int batch_statistics, kbn_stream_t stream) {
+    if (!u || !grad_y || !scale || !shift || !mean || !rstd || !sums || !grad_u) return KBN_ERR_INVALID_ARGUMENT;
+    long long total = 0;
+    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    const long long hw = (long long)height * width;
+    if (n > 1 && (u_batch_stride < channels * hw || grad_y_batch_stride < channels * hw || grad_u_batch_stride < channels * hw))
+        return KBN_ERR_INVALID_ARGUMENT;
+    const int act = apply_activation ? 1 : 0;
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3((unsigned)channels), dim3(RT), 0, (hipStream_t)stream, u, u_batch_stride, grad_y,
+                       grad_y_batch_stride, scale, shift, mean, rstd, sums, n, channels, (int)hw, act, negative_slope);
+    KBN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u,
+                       u_batch_stride, grad_y, grad_y_batch_stride, scale, shift, mean, rstd, sums, grad_u, grad_u_batch_stride,
+                       channels, (int)hw, total, (double)n * (double)hw, act, negative_slope, batch_statistics ? 1 : 0);
+    KBN_CHECK_LAUNCH();
+    return KBN_OK;
+}

@@ -1532,6 +1532,318 @@ def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = Fal
     return (out, dof_out) if return_dof else out
 
 
+# ------------------------------------------------------------------ pose network (training: csrc/posenet_backward.hip)
+def _s2_inputs(fn: str, inputs):
+    """The one or two N x C_i x H x W tensors of a stride-2 conv -> (inputs, sources, n, h, w, total channels)."""
+    inputs = list(inputs)
+    if not 1 <= len(inputs) <= 2:
+        raise KbnError(f"{fn}: one or two inputs, got {len(inputs)}")
+    srcs = [tensor_src(t.detach() if isinstance(t, torch.Tensor) else t, f"inputs[{i}]") for i, t in enumerate(inputs)]
+    n, _, h, w = inputs[0].shape
+    for i, t in enumerate(inputs[1:], 1):
+        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
+            raise KbnError(f"{fn}: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
+    if n < 1 or h < 1 or w < 1 or any(s.channels < 1 for s in srcs):
+        raise KbnError(f"{fn}: empty input {tuple(inputs[0].shape)}")
+    return inputs, srcs, n, h, w, sum(s.channels for s in srcs)
+
+
+def _s2_kernel_size(fn: str, kernel_size):
+    if kernel_size not in (3, 5, 7):
+        raise KbnError(f"{fn}: kernel size 3, 5 or 7, got {kernel_size}")
+
+
+@_on_tensor_device
+def pack_conv2d_s2_backward_data_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW (k in {3, 5, 7}) -> the transposed order conv2d_s2_backward_data reads: [input-channel tile][(filter, tap) chunk][16]
+    [input channels] (kbn_conv2d_s2_backward_data_pack_weight; not the forward's blob).  `out`: a blob to re-pack into."""
+    lib = _lib.load()
+    w = _weight(weight)
+    oc, cin, kh, kw = w.shape
+    if kh != kw:
+        raise KbnError("square kernels only")
+    nbytes = lib.kbn_conv2d_s2_backward_data_packed_weight_bytes(oc, cin, kh)
+    if nbytes == 0:
+        raise KbnError(f"conv2d_s2_backward_data: unsupported weight shape {tuple(w.shape)} (kernel size 3, 5 or 7)")
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_s2_backward_data_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
+                      "kbn_conv2d_s2_backward_data_pack_weight")
+
+
+@_on_tensor_device
+def conv2d_s2_backward_data(grad_out: torch.Tensor, packed_weight: torch.Tensor, in_channels: Sequence[int], kernel_size: int,
+                            in_height: int, in_width: int, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """The gradient of conv_{k x k, stride 2, padding k // 2}(cat(inputs, 1)) with respect to its one or two inputs
+    (kbn_conv2d_s2_backward_data): grad_out N x F x ceil(H / 2) x ceil(W / 2) -> [N x C_i x H x W for C_i in in_channels], the
+    matching channel ranges of the concat's gradient.  `packed_weight`: pack_conv2d_s2_backward_data_weight of the F x sum(C_i) x k
+    x k weight.  `out`: tensors or channel slices to write into.  One launch, all k x k taps with three quarters of them
+    predicated to zero (an input pixel meets only the taps of its parity): `executed` in the launch record says so."""
+    lib = _lib.load()
+    _s2_kernel_size("conv2d_s2_backward_data", kernel_size)
+    in_channels = [int(c) for c in in_channels]
+    if not 1 <= len(in_channels) <= 2 or any(c < 1 for c in in_channels):
+        raise KbnError(f"conv2d_s2_backward_data: one or two positive channel counts, got {in_channels}")
+    if in_height < 1 or in_width < 1:
+        raise KbnError(f"conv2d_s2_backward_data: empty input {in_height} x {in_width}")
+    gptr, gbs = _planes(grad_out, "grad_out")
+    n, oc, oh, ow = grad_out.shape
+    if n < 1 or oc < 1 or (oh, ow) != ((in_height + 1) // 2, (in_width + 1) // 2):
+        raise KbnError(f"conv2d_s2_backward_data: grad_out is {tuple(grad_out.shape)}, the conv of a {in_height} x {in_width} input "
+                       f"has {(in_height + 1) // 2} x {(in_width + 1) // 2} maps")
+    cin = sum(in_channels)
+    _require(packed_weight, "packed_weight", 1)
+    want = lib.kbn_conv2d_s2_backward_data_packed_weight_bytes(oc, cin, kernel_size) // 4
+    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
+        raise KbnError(f"conv2d_s2_backward_data: packed_weight holds {packed_weight.numel()} floats, a {oc} x {cin} x "
+                       f"{kernel_size} x {kernel_size} weight packs into {want}")
+    if out is not None and len(out) != len(in_channels):
+        raise KbnError(f"conv2d_s2_backward_data: {len(out)} output tensors for {len(in_channels)} inputs")
+    grads = [_out_tensor(None if out is None else out[i], (n, c, in_height, in_width), grad_out.device, f"out[{i}]", planes=True)
+             for i, c in enumerate(in_channels)]
+    ptrs = [_planes(g, f"out[{i}]") for i, g in enumerate(grads)]
+    p1, bs1, c1 = (ptrs[1][0], ptrs[1][1], in_channels[1]) if len(grads) == 2 else (None, 0, 0)
+    k2 = kernel_size * kernel_size
+    nt = 16 if cin <= 16 else (32 if cin <= 32 else 64)
+    check(_launch(f"conv_s2_bwd_data<{kernel_size},{nt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
+                  lambda: lib.kbn_conv2d_s2_backward_data(gptr, gbs, packed_weight.data_ptr(), ptrs[0][0], ptrs[0][1], in_channels[0],
+                                                          p1, bs1, c1, n, oc, kernel_size, in_height, in_width, _stream()),
+                  executed=2.0 * (-(-n * in_height * in_width // 128) * 128) * (-(-oc * k2 // 16) * 16) * (-(-cin // nt) * nt),
+                  pipe="fp32", nbytes=4.0 * n * (oc * oh * ow + cin * in_height * in_width)), "kbn_conv2d_s2_backward_data")
+    return grads
+
+
+@_on_tensor_device
+def conv2d_s2_backward_weight(inputs: Sequence[torch.Tensor], grad_out: torch.Tensor, kernel_size: int,
+                              splits: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of conv_{k x k, stride 2, padding k // 2}(cat(inputs, 1)) with respect to its weight
+    (kbn_conv2d_s2_backward_weight): -> F x sum(C_i) x k x k, plain OIHW.  The sum over the batch's output pixels is split over
+    `splits` workgroups per tile (None: chosen from the shape) whose partial sums a second launch adds in split order: the bits
+    are a function of the arguments (and of `splits`) alone."""
+    lib = _lib.load()
+    _s2_kernel_size("conv2d_s2_backward_weight", kernel_size)
+    inputs, srcs, n, h, w, cin = _s2_inputs("conv2d_s2_backward_weight", inputs)
+    gptr, gbs = _planes(grad_out, "grad_out")
+    oc, oh, ow = grad_out.shape[1], (h + 1) // 2, (w + 1) // 2
+    if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
+        raise KbnError(f"conv2d_s2_backward_weight: grad_out is {tuple(grad_out.shape)}, the conv of inputs {tuple(inputs[0].shape)} "
+                       f"has {n} frames of {oh} x {ow} maps")
+    if splits is not None and (not isinstance(splits, int) or splits < 1):
+        raise KbnError(f"conv2d_s2_backward_weight: splits must be a positive integer or None, got {splits!r}")
+    splits = 0 if splits is None else splits
+    out = _out_tensor(out, (oc, cin, kernel_size, kernel_size), grad_out.device, "conv2d_s2_backward_weight: out")
+    nbytes = lib.kbn_conv2d_s2_backward_weight_scratch_bytes(n, oc, cin, kernel_size, h, w, splits)
+    scratch = torch.empty(nbytes // 4, device=grad_out.device, dtype=torch.float32) if nbytes else None
+    arr = (ConvSrc * len(srcs))(*srcs)
+    k2 = kernel_size * kernel_size
+    mt = 16 if oc <= 16 else (32 if oc <= 32 else 64)
+    check(_launch(f"conv_s2_bwd_weight<{kernel_size},{mt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
+                  lambda: lib.kbn_conv2d_s2_backward_weight(arr, len(srcs), gptr, gbs, out.data_ptr(), n, oc, kernel_size, h, w, splits,
+                                                            scratch.data_ptr() if scratch is not None else None, nbytes, _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 32) * 32) * (-(-cin * k2 // 64) * 64) * (-(-oc // mt) * mt), pipe="fp32",
+                  nbytes=_src_bytes(srcs, n) + 4.0 * (n * oc * oh * ow + oc * cin * k2)), "kbn_conv2d_s2_backward_weight")
+    return out
+
+
+def _channel_vector(fn: str, t, name: str, c: int) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise KbnError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
+    v = t.detach()
+    _require(v, name, 1)
+    if v.numel() != c:
+        raise KbnError(f"{fn}: {name} must hold {c} floats (one per channel), got {tuple(v.shape)}")
+    return v.contiguous()
+
+
+@_on_tensor_device
+def batch_norm_stats(x: torch.Tensor):
+    """(mean, biased variance) of an N x C x H x W tensor over N, H, W: C floats each (kbn_bn_stats_forward), what
+    torch.nn.BatchNorm2d normalises with in train mode.  Two passes accumulated in fp64: no E[x^2] - mean^2."""
+    lib = _lib.load()
+    ptr, bs = _planes(x, "x")
+    n, c, h, w = x.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"batch_norm_stats: empty input {tuple(x.shape)}")
+    mean = torch.empty(c, device=x.device, dtype=torch.float32)
+    var = torch.empty(c, device=x.device, dtype=torch.float32)
+    check(_launch("bn_stats", 0.0, lambda: lib.kbn_bn_stats_forward(ptr, bs, mean.data_ptr(), var.data_ptr(), n, c, h, w, _stream()),
+                  nbytes=8.0 * n * c * h * w), "kbn_bn_stats_forward")
+    return mean, var
+
+
+def _bn_affine(fn: str, c: int, gamma, beta, mean, var, eps: float):
+    """(scale = gamma rstd, shift = beta - mean scale, mean, rstd): C-length torch ops, as PoseConv2d.affine forms them."""
+    g, b, m, v = (_channel_vector(fn, t, name, c) for t, name in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")))
+    rstd = torch.rsqrt(v + eps)
+    scale = g * rstd
+    return scale, b - m * scale, m, rstd
+
+
+def _bn_act_launch(u, scale, shift, negative_slope, out=None):
+    lib = _lib.load()
+    uptr, ubs = _planes(u, "u")
+    n, c, h, w = u.shape
+    out = _out_tensor(out, (n, c, h, w), u.device, "batch_norm_act: out", planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("bn_act", 0.0, lambda: lib.kbn_bn_act_forward(uptr, ubs, scale.data_ptr(), shift.data_ptr(), optr, obs, n, c, h, w,
+                                                                *_act_args(negative_slope), _stream()),
+                  nbytes=8.0 * n * c * h * w), "kbn_bn_act_forward")
+    return out
+
+
+class _BatchNormAct(torch.autograd.Function):
+    """act(batch_norm(u)) as a differentiable node.  Saved: u, gamma, beta and the two statistics vectors -- the normalised
+    tensor and the activation's mask are recomputed from u in the backward (kbn_bn_act_backward)."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, beta, mean, var, eps, negative_slope, batch):
+        scale, shift, _, _ = _bn_affine("batch_norm_act", u.shape[1], gamma, beta, mean, var, eps)
+        ctx.save_for_backward(u, gamma, beta, mean, var)
+        ctx.args = (eps, negative_slope, batch)
+        return _bn_act_launch(u.detach(), scale, shift, negative_slope)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        u, gamma, beta, mean, var = ctx.saved_tensors
+        grad_u, grad_gamma, grad_beta = batch_norm_act_backward(u, grad_y, gamma, beta, mean, var, *ctx.args)
+        need = ctx.needs_input_grad
+        return (grad_u if need[0] else None, grad_gamma if need[1] else None, grad_beta if need[2] else None, None, None, None,
+                None, None)
+
+
+@_on_tensor_device
+def batch_norm_act(u: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
+                   eps: float = 1e-5, negative_slope: Optional[float] = 0.2, batch: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act((u - mean) / sqrt(var + eps) * gamma + beta) per channel, act = max(v, slope v) (`negative_slope` None: none), as
+    y = act(u * scale + shift) in one launch (kbn_bn_act_forward).  `mean` / `var`: the running statistics, or with `batch` the
+    statistics of u itself (batch_norm_stats) -- the flag only tells the backward whether they depend on u.  Differentiable
+    with respect to u, gamma and beta when grad mode is on and one of them requires grad (one node, no double backward); `mean`
+    and `var` are data: one that requires grad is an error.  `out` (a tensor or channel slice to write into) only without autograd."""
+    _require(u, "u", 4)
+    if u.shape[0] < 1 or u.shape[1] < 1 or u.shape[2] < 1 or u.shape[3] < 1:
+        raise KbnError(f"batch_norm_act: empty input {tuple(u.shape)}")
+    for t, name in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")):
+        _channel_vector("batch_norm_act", t, name, u.shape[1])
+    if torch.is_grad_enabled():
+        for t, name in ((mean, "mean"), (var, "var")):
+            if t.requires_grad:
+                raise KbnError(f"batch_norm_act: {name} requires grad, but it is data and gets no gradient (gradients exist for u, "
+                               "gamma, beta); detach it")
+        if any(t.requires_grad for t in (u, gamma, beta)):
+            if out is not None:
+                raise KbnError("batch_norm_act: `out` cannot be given when the call is recorded for autograd")
+            _planes(u, "u")
+            return _BatchNormAct.apply(u, gamma, beta, mean, var, float(eps), negative_slope, bool(batch))
+    scale, shift, _, _ = _bn_affine("batch_norm_act", u.shape[1], gamma, beta, mean, var, eps)
+    return _bn_act_launch(u.detach(), scale, shift, negative_slope, out)
+
+
+@_on_tensor_device
+def batch_norm_act_backward(u: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor,
+                            var: torch.Tensor, eps: float = 1e-5, negative_slope: Optional[float] = 0.2, batch: bool = False):
+    """The gradient of `batch_norm_act`: (grad_u N x C x H x W, grad_gamma, grad_beta C floats each), two launches
+    (kbn_bn_act_backward).  The first sums g_z and g_z xhat per channel in fp64 and a fixed order (g_z = grad_y where
+    z = u scale + shift > 0, slope grad_y elsewhere; xhat recomputed from u); the second is elementwise.  With `batch` the
+    statistics are functions of u (torch.nn.BatchNorm2d in train mode); without, constants."""
+    lib = _lib.load()
+    uptr, ubs = _planes(u.detach() if isinstance(u, torch.Tensor) else u, "u")
+    n, c, h, w = u.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"batch_norm_act_backward: empty input {tuple(u.shape)}")
+    if not isinstance(grad_y, torch.Tensor) or tuple(grad_y.shape) != (n, c, h, w):
+        raise KbnError(f"batch_norm_act_backward: grad_y must be {(n, c, h, w)} like u, got "
+                       f"{tuple(grad_y.shape) if isinstance(grad_y, torch.Tensor) else type(grad_y).__name__}")
+    gy = grad_y.detach()
+    _require(gy, "grad_y", 4)
+    gy = gy.contiguous()
+    scale, shift, m, rstd = _bn_affine("batch_norm_act_backward", c, gamma, beta, mean, var, eps)
+    sums = torch.empty(2 * c, device=u.device, dtype=torch.float64)
+    grad_u = torch.empty((n, c, h, w), device=u.device, dtype=torch.float32)
+    check(_launch("bn_act_backward", 0.0,
+                  lambda: lib.kbn_bn_act_backward(uptr, ubs, gy.data_ptr(), c * h * w, scale.data_ptr(), shift.data_ptr(), m.data_ptr(),
+                                                  rstd.data_ptr(), sums.data_ptr(), grad_u.data_ptr(), c * h * w, n, c, h, w,
+                                                  *_act_args(negative_slope), 1 if batch else 0, _stream()),
+                  nbytes=20.0 * n * c * h * w), "kbn_bn_act_backward")
+    return grad_u, sums[c:].float(), sums[:c].float()
+
+
+_UNIT_AFFINE = {}
+
+
+def _unit_affine(device, c: int):
+    key = (device, c)
+    if key not in _UNIT_AFFINE:
+        _UNIT_AFFINE[key] = (torch.ones(c, device=device, dtype=torch.float32), torch.zeros(c, device=device, dtype=torch.float32))
+    return _UNIT_AFFINE[key]
+
+
+def _conv2d_s2_launch(inputs, weight, packed):
+    oc, _, k, _ = weight.shape
+    if packed is None:
+        packed = pack_conv2d_s2_affine_weight(weight)
+    ones, zeros = _unit_affine(weight.device, oc)
+    return conv2d_s2_affine([t.detach() for t in inputs], packed, ones, zeros, oc, k, negative_slope=None)
+
+
+class _Conv2dS2(torch.autograd.Function):
+    """The bias-free stride-2 conv as a differentiable node.  Saved: the weight and the inputs, nothing the forward computed.
+    Backward: one weight-gradient call, and one data-gradient launch only when an input asks for its gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, packed, packed_t, *inputs):
+        ctx.save_for_backward(weight, *inputs)
+        ctx.packed_t = packed_t
+        return _conv2d_s2_launch(inputs, weight, packed)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_u):
+        weight, *inputs = ctx.saved_tensors
+        k = weight.shape[2]
+        need = ctx.needs_input_grad
+        g = grad_u.contiguous()
+        grad_w = conv2d_s2_backward_weight(inputs, g, k) if need[0] else None
+        grads = [None] * len(inputs)
+        if any(need[3:]):
+            packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
+            h, w = inputs[0].shape[2:]
+            got = conv2d_s2_backward_data(g, packed_t, [t.shape[1] for t in inputs], k, h, w)
+            grads = [gi if need[3 + i] else None for i, gi in enumerate(got)]
+        return (grad_w, None, None) + tuple(grads)
+
+
+@_on_tensor_device
+def conv2d_s2(inputs: Sequence[torch.Tensor], weight: torch.Tensor, packed: Optional[torch.Tensor] = None, packed_t=None) -> torch.Tensor:
+    """conv_{k x k, stride 2, padding k // 2}(cat(inputs, 1)), no bias (k in {3, 5, 7}): conv2d_s2_affine's kernel with unit
+    scale, zero shift and no activation.  Differentiable with respect to the weight and to every input that requires grad (one
+    node, no double backward).  `packed`: the weight's pack_conv2d_s2_affine_weight blob when the caller caches it; `packed_t`:
+    a callable weight -> its pack_conv2d_s2_backward_data_weight blob, asked only when a data gradient is needed."""
+    inputs = list(inputs)
+    w = _weight(weight)
+    if w.shape[2] != w.shape[3]:
+        raise KbnError("square kernels only")
+    _s2_kernel_size("conv2d_s2", w.shape[2])
+    _, _, _, _, _, cin = _s2_inputs("conv2d_s2", inputs)
+    if cin != w.shape[1]:
+        raise KbnError(f"conv2d_s2: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
+    if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
+        return _Conv2dS2.apply(weight, packed, packed_t, *inputs)
+    return _conv2d_s2_launch(inputs, w, packed)
+
+
+def pose_head_recorded(latent: torch.Tensor, weight: torch.Tensor):
+    """`pose_head` restated in torch operations that autograd records (N x C x a handful of pixels): (pose N x 4 x 4, dof N x 6)
+    = (pose_matrix(dof), 0.01 * mean_hw(latent) W^T), the mean before the product as the kernel takes it.  Used only when
+    gradients are on; the values agree with pose_head's within the dof gate, not bit for bit."""
+    _require(latent, "latent", 4)
+    _require(weight, "weight")
+    c = latent.shape[1]
+    if weight.numel() != 6 * c or weight.shape[0] != 6:
+        raise KbnError(f"pose_head_recorded: weight must be 6 x {c} (x 1 x 1), got {tuple(weight.shape)}")
+    dof = 0.01 * (latent.mean(dim=(2, 3)) @ weight.reshape(6, c).t())
+    return pose_matrix(dof), dof
+
+
 # ------------------------------------------------------------------ ResNet pose networks (eval mode)
 @_on_tensor_device
 def pack_conv2d_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

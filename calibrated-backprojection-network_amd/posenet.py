@@ -6,8 +6,12 @@
   posenet_model.PoseNetModel  src/posenet_model.py:21-206   PoseNetModel
 
 Same constructor arguments, `forward(image0, image1)` and `state_dict()` keys as the reference, so a `pose_model-*.pth`
-checkpoint loads with strict=True.  Inference only: BatchNorm2d uses its running statistics (a per-channel scale and shift in
-the conv's epilogue), there is no autograd and no CPU path.  Eight launches per forward: seven convs and the head.
+checkpoint loads with strict=True.  By default inference: BatchNorm2d uses its running statistics (a per-channel scale and shift
+in the conv's epilogue), nothing is recorded, eight launches per forward: seven convs and the head.  No CPU path.
+
+Training (reference src/kbnet.py:392-453) is switched on by PoseNetModel.requires_grad_(True) and, for the reference's train-mode
+BatchNorm, set_batch_norm('batch'): the forward then runs layer by layer on the kernels of csrc/posenet_backward.hip and records
+autograd (ops.conv2d_s2, ops.batch_norm_act); `train()` still raises and the torch modules stay in eval mode.
 """
 
 from __future__ import annotations
@@ -75,10 +79,21 @@ class PoseConv2d(torch.nn.Module):
             p.requires_grad_(False)
         from .modules import _PackedBlob   # (modules.py imports this file at its end: not at the top)
         self._packed = _PackedBlob(ops.pack_conv2d_s2_affine_weight)
+        self._tkey = self._tblob = None   # the data gradient's transposed blob (packed_t): built on first use
         self._akey = self._scale = self._shift = None
 
     def packed(self):
         return self._packed.get(self.conv.weight)
+
+    def packed_t(self, weight=None):
+        """The weight in the data gradient's order (ops.pack_conv2d_s2_backward_data_weight), re-packed when the weight changed.
+        Not a _PackedBlob: no graph of the eval-mode forward points into it, refresh_packed has nothing to do with it."""
+        weight = self.conv.weight if weight is None else weight
+        key = _state(weight)
+        if key != self._tkey:
+            self._tblob = ops.pack_conv2d_s2_backward_data_weight(weight, out=self._tblob)
+            self._tkey = key
+        return self._tblob
 
     def affine(self):
         """scale = g * rsqrt(var + eps), shift = b - mean * scale (BatchNorm2d.eval()), fp32 on the weights' device."""
@@ -103,6 +118,28 @@ class PoseConv2d(torch.nn.Module):
         scale, shift = self.affine()
         return ops.conv2d_s2_affine(inputs, self.packed(), scale, shift, self.out_channels, self.kernel_size,
                                     negative_slope=self.slope, out=out)
+
+    def run_unfused(self, inputs: List[torch.Tensor], batch: bool):
+        """The layer as conv, [batch statistics], BatchNorm + activation: what the fused launch of `run` cannot be when the
+        backward needs the conv's output or the statistics are the batch's own.  Recorded for autograd when grad mode is on and
+        a parameter requires grad.  `batch`: normalise with the statistics of this batch and update the running ones as
+        torch.nn.BatchNorm2d does in train mode (src/net_utils.py:103-104); the module's `training` flag stays False."""
+        bn = self.batch_norm
+        u = ops.conv2d_s2(inputs, self.conv.weight, packed=self.packed(), packed_t=self.packed_t)
+        if batch:
+            count = u.shape[0] * u.shape[2] * u.shape[3]
+            if count <= 1:
+                raise KbnError(f"set_batch_norm('batch'): a {tuple(u.shape)} map has one value per channel, no batch statistics "
+                               "(torch.nn.BatchNorm2d raises there too)")
+            mean, var = ops.batch_norm_stats(u.detach())
+            with torch.no_grad():
+                momentum = bn.momentum
+                bn.running_mean.mul_(1.0 - momentum).add_(mean, alpha=momentum)
+                bn.running_var.mul_(1.0 - momentum).add_(var, alpha=momentum * count / (count - 1.0))   # the UNBIASED variance
+                bn.num_batches_tracked.add_(1)
+        else:
+            mean, var = bn.running_mean, bn.running_var
+        return ops.batch_norm_act(u, bn.weight, bn.bias, mean, var, bn.eps, self.slope, batch)
 
     def forward(self, x):
         return self.run([x])
@@ -134,6 +171,15 @@ class PoseEncoder(torch.nn.Module):
         x = list(inputs)
         for layer in self.layers():
             outs.append(layer.run(x))
+            x = [outs[-1]]
+        return outs if return_layers else outs[-1]
+
+    def encode_unfused(self, inputs: List[torch.Tensor], batch: bool = False, return_layers: bool = False):
+        """`encode` through PoseConv2d.run_unfused: three launches a layer (four with batch statistics), recordable."""
+        outs = []
+        x = list(inputs)
+        for layer in self.layers():
+            outs.append(layer.run_unfused(x, batch))
             x = [outs[-1]]
         return outs if return_layers else outs[-1]
 
@@ -191,8 +237,19 @@ class PoseModelBase(object):
     def parameters(self):
         return list(self.encoder.parameters()) + list(self.decoder.parameters())
 
+    _has_backward = False   # PoseNetModel: True
+
+    def requires_grad_(self, flag: bool = True):
+        """Sets requires_grad on every parameter (conv weights, BatchNorm weights and biases, the head's weight)."""
+        if flag and not self._has_backward:
+            raise KbnError(f"{type(self).__name__}.requires_grad_: only encoder_type='posenet' (PoseNetModel) has a backward pass yet")
+        for p in self.parameters():
+            p.requires_grad_(bool(flag))
+        return self
+
     def train(self):
-        raise KbnError("the HIP path is inference only")
+        raise KbnError("the HIP path is inference only through train() / eval(): the modules stay in eval mode.  PoseNetModel "
+                       "trains through requires_grad_(True) and set_batch_norm('batch')")
 
     def eval(self):
         for m in self.modules():
@@ -247,14 +304,48 @@ class PoseNetModel(PoseModelBase):
                                    activation_func=activation_func, use_batch_norm=True)
         self.decoder = PoseDecoder(rotation_parameterization=rotation_parameterization, weight_initializer=weight_initializer,
                                    input_channels=list(n_filters)[-1])
+        self.batch_norm_mode = "running"
         self._place(device)
 
-    @torch.no_grad()
+    _has_backward = True
+
+    def set_batch_norm(self, mode: str = "running"):
+        """'running' (default): BatchNorm2d normalises with its running statistics, constants of the backward pass -- fine-tuning
+        on frozen statistics.  'batch': what the reference's pose_model.train() does (src/kbnet.py:392-453): every layer normalises
+        with the statistics of the batch, the gradient runs through them, and running_mean / running_var / num_batches_tracked are
+        updated as torch.nn.BatchNorm2d updates them (momentum 0.1, unbiased variance), with gradients on or off.  A layer whose
+        map holds one value per channel raises."""
+        if mode not in ("running", "batch"):
+            raise KbnError(f"PoseNetModel.set_batch_norm: 'running' or 'batch', got {mode!r}")
+        self.batch_norm_mode = mode
+        return self
+
     def forward(self, image0, image1, return_all: bool = False):
-        """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone."""
+        """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone.
+
+        With grad mode on and a parameter that requires grad (`requires_grad_(True)`) the pose carries a grad_fn: every layer
+        runs as conv, [batch statistics], BatchNorm + activation on the kernels of csrc/posenet_backward.hip's forward side, the
+        head in recorded torch operations.  Otherwise, on running statistics, this is the fused eval-mode forward: eight
+        launches, nothing recorded."""
         if not isinstance(image0, torch.Tensor) or not isinstance(image1, torch.Tensor) or image0.dim() != 4 or \
                 image0.shape[1] != 3 or image0.shape != image1.shape:
             raise KbnError("PoseNetModel.forward: image0 and image1 must be N x 3 x H x W tensors of one shape")
-        layers = self.encoder.encode([image0, image1], return_layers=True)
-        pose, dof = self.decoder(layers[-1], return_dof=True)
+        record = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        batch = self.batch_norm_mode == "batch"
+        if not record and not batch:
+            with torch.no_grad():
+                layers = self.encoder.encode([image0, image1], return_layers=True)
+                pose, dof = self.decoder(layers[-1], return_dof=True)
+            return (pose, dof, layers) if return_all else pose
+        if record:
+            for t, name in ((image0, "image0"), (image1, "image1")):
+                if t.requires_grad:
+                    raise KbnError(f"PoseNetModel.forward: {name} requires grad, but it is data and gets no gradient (gradients "
+                                   "exist for the parameters); detach it")
+        with torch.set_grad_enabled(record):
+            layers = self.encoder.encode_unfused([image0, image1], batch, return_layers=True)
+            if record:
+                pose, dof = ops.pose_head_recorded(layers[-1], self.decoder.conv.conv.weight)
+            else:
+                pose, dof = self.decoder(layers[-1], return_dof=True)
         return (pose, dof, layers) if return_all else pose

@@ -627,6 +627,57 @@ int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src, const floa
 int kbn_pose_head_forward(const float* latent, long long latent_batch_stride, const float* weight, float* pose,
                           float* dof, int n, int channels, int height, int width, kbn_stream_t stream);
 
+/* ------------------------------------------------- pose network (training: the backward of a PoseEncoder layer) ----
+ * What reference src/kbnet.py:392-453 (loss.backward() through pose_model in train mode) needs of net_utils.Conv2d
+ * (src/net_utils.py:51-141: bias-free conv stride 2 padding k / 2, torch.nn.BatchNorm2d, LeakyReLU) on the HIP path.  fp32 in and
+ * out; the matrix products on v_mfma_f32_16x16x4_f32; no floating-point atomics: every sum has a fixed order, a call's bits are a
+ * function of its arguments alone.
+ *
+ * kbn_conv2d_s2_backward_data (the conv of src/net_utils.py:120-126, differentiated by its input):
+ *   grad_in[n, c, iy, ix] = sum_o,ky,kx W[o, c, ky, kx] grad_out[n, o, (iy + k/2 - ky) / 2, (ix + k/2 - kx) / 2] over the taps
+ *   whose numerators are even and land inside the ceil(in_h / 2) x ceil(in_w / 2) output map.  The gradient of the channel concat
+ *   of one or two inputs: channels [0, channels0) go to grad_in0, the next channels1 to grad_in1 (NULL and 0 for one input), frames
+ *   *_batch_stride elements apart.  kernel_size in {3, 5, 7}, any channel counts.  packed_weight: the OIHW weight through
+ *   kbn_conv2d_s2_backward_data_pack_weight (its own, transposed order: not the forward's blob).
+ * kbn_conv2d_s2_backward_weight (the same conv, differentiated by its OIHW weight):
+ *   grad_weight[o, c, ky, kx] = sum_n,oy,ox grad_out[n, o, oy, ox] in[n, c, 2 oy + ky - k/2, 2 ox + kx - k/2], `in` the concat of
+ *   one or two KBN_SRC_TENSOR sources as kbn_conv2d_s2_affine_forward reads them, taps outside the image zero.  The sum over the
+ *   output pixels is split over `splits` workgroups per tile (<= 0: chosen from the shape alone, not from the device), whose
+ *   partial sums go to `scratch` (kbn_conv2d_s2_backward_weight_scratch_bytes(..., splits) bytes; 0 bytes, and scratch may be
+ *   NULL, when one split remains) and are added in split order by a second launch.  grad_weight is plain OIHW. */
+size_t kbn_conv2d_s2_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
+int kbn_conv2d_s2_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
+                                            int kernel_size, kbn_stream_t stream);
+int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad_out_batch_stride, const float* packed_weight,
+                                float* grad_in0, long long grad_in0_batch_stride, int channels0, float* grad_in1,
+                                long long grad_in1_batch_stride, int channels1, int n, int out_channels, int kernel_size,
+                                int in_height, int in_width, kbn_stream_t stream);
+size_t kbn_conv2d_s2_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size, int in_height,
+                                                   int in_width, int splits);
+int kbn_conv2d_s2_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out, long long grad_out_batch_stride,
+                                  float* grad_weight, int n, int out_channels, int kernel_size, int in_height, int in_width,
+                                  int splits, float* scratch, size_t scratch_bytes, kbn_stream_t stream);
+
+/* torch.nn.BatchNorm2d in train mode (src/net_utils.py:103-104, 128-129) with the activation behind it (:131-141).
+ * kbn_bn_stats_forward: mean[c] and the BIASED variance var[c] of x (N x channels x H x W, frames batch_stride apart) over N, H, W,
+ *   two passes accumulated in fp64 (the mean, then the centred squares), rounded to fp32 once.
+ * kbn_bn_act_forward: y = act(u * scale[c] + shift[c]) (one fused multiply-add), act = max(v, slope v) when apply_activation.
+ *   The caller forms scale = gamma rstd and shift = beta - mean scale from the running or the batch statistics.
+ * kbn_bn_act_backward: two launches.  (1) per channel, in fp64 and a fixed order: sums[c] = sum g_z (the gradient of beta) and
+ *   sums[channels + c] = sum g_z xhat (the gradient of gamma), g_z = grad_y (z > 0 ? 1 : slope) with z = u * scale[c] + shift[c]
+ *   formed as the forward forms it (z <= 0 takes the slope, as torch's leaky_relu at 0), xhat = (u - mean[c]) rstd[c].
+ *   (2) grad_u = scale[c] (g_z - (sums[c] + xhat sums[channels + c]) / (N H W)) with batch_statistics, scale[c] g_z without (the
+ *   statistics are constants then). */
+int kbn_bn_stats_forward(const float* x, long long batch_stride, float* mean, float* var, int n, int channels, int height,
+                         int width, kbn_stream_t stream);
+int kbn_bn_act_forward(const float* u, long long u_batch_stride, const float* scale, const float* shift, float* y,
+                       long long y_batch_stride, int n, int channels, int height, int width, int apply_activation,
+                       float negative_slope, kbn_stream_t stream);
+int kbn_bn_act_backward(const float* u, long long u_batch_stride, const float* grad_y, long long grad_y_batch_stride,
+                        const float* scale, const float* shift, const float* mean, const float* rstd, double* sums,
+                        float* grad_u, long long grad_u_batch_stride, int n, int channels, int height, int width,
+                        int apply_activation, float negative_slope, int batch_statistics, kbn_stream_t stream);
+
 /* ------------------------------------------------- ResNet pose networks (eval mode) ----
  * PoseNetModel(encoder_type='resnet18' | 'resnet34')   reference src/posenet_model.py:55-87 (what src/kbnet.py:221-226 trains)
  *   networks.ResNetEncoder                             reference src/networks.py:674-996

@@ -24,17 +24,13 @@
 // the weights: the conv itself then rounds as the reference's does.
 //
 // maxpool3x3s2_kernel: MaxPool2d(3, stride 2, padding 1), one thread per output, torch's update rule (v > m || isnan(v)).
-#include "kbn_common.h"
+#include "pose_igemm.h"
 
 namespace kbn {
 namespace {
 
-constexpr int CA_BM = 128, CA_KC = 32, CA_AP = CA_BM + 16;
-
-__host__ __device__ inline int conv_affine_nb(int oc) { return oc <= 16 ? 1 : (oc <= 32 ? 2 : 4); }
-__host__ __device__ constexpr int conv_affine_bp(int nb) { return nb == 1 ? 16 : 16 * nb + 16; }
-__host__ __device__ constexpr int conv_affine_lds_floats(int nb) { return 2 * CA_KC * (CA_AP + conv_affine_bp(nb)); }
-constexpr int CA_MAX_LDS = conv_affine_lds_floats(4) * (int)sizeof(float);
+constexpr int CA_KC = 32;
+constexpr int CA_MAX_LDS = pose_igemm_lds_floats(CA_KC, 4) * (int)sizeof(float);
 
 struct CAParams {
     const float* src0;
@@ -57,12 +53,12 @@ struct CAParams {
 
 template <int KS, int STRIDE, int NB>
 __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
-    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = conv_affine_bp(NB);
+    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = pose_igemm_bp(NB);
     constexpr int NA = CA_KC / 2;                 // gathered values per thread and chunk
     constexpr int NW = CA_KC * BN / 256;          // weights per thread and chunk
     extern __shared__ float ca_lds[];
-    float* const As = ca_lds;                     // [2][CA_KC * CA_AP]
-    float* const Bs = ca_lds + 2 * CA_KC * CA_AP; // [2][CA_KC * BP]
+    float* const As = ca_lds;                     // [2][CA_KC * PI_AP]
+    float* const Bs = ca_lds + 2 * CA_KC * PI_AP; // [2][CA_KC * BP]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
@@ -70,9 +66,9 @@ __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
     const int HW = p.H * p.W, OHW = p.OH * p.OW;
 
     // the pixel this thread gathers
-    const int pm = tid & (CA_BM - 1);
+    const int pm = tid & (PI_BM - 1);
     const int khalf = __builtin_amdgcn_readfirstlane(tid >> 7);   // 0 for waves 0, 1; 1 for waves 2, 3
-    const int m = mt * CA_BM + pm;
+    const int m = mt * PI_BM + pm;
     const bool mvalid = m < p.M;
     int fn = 0, iy0 = 0, ix0 = 0;
     if (mvalid) {
@@ -107,10 +103,10 @@ __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
         for (int j = 0; j < NW; ++j) vb[j] = wc[tid + 256 * j];
     };
     auto store_chunk = [&](int buf) {
-        float* Ab = As + buf * (CA_KC * CA_AP);
+        float* Ab = As + buf * (CA_KC * PI_AP);
         float* Bb = Bs + buf * (CA_KC * BP);
 #pragma unroll
-        for (int j = 0; j < NA; ++j) Ab[(khalf + 2 * j) * CA_AP + pm] = va[j];
+        for (int j = 0; j < NA; ++j) Ab[(khalf + 2 * j) * PI_AP + pm] = va[j];
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
             const int e = tid + 256 * j;
@@ -131,13 +127,13 @@ __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
         const int buf = chunk & 1;
         const bool more = chunk + 1 < p.nchunks;
         if (more) load_chunk(chunk + 1);
-        const float* Ab = As + buf * (CA_KC * CA_AP) + lk * CA_AP + wave * 32 + li;
+        const float* Ab = As + buf * (CA_KC * PI_AP) + lk * PI_AP + wave * 32 + li;
         const float* Bb = Bs + buf * (CA_KC * BP) + lk * BP + li;
 #pragma unroll
         for (int k4 = 0; k4 < CA_KC / 4; ++k4) {
             float a[2], b[NB];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * CA_AP + mi * 16];
+            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * PI_AP + mi * 16];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) b[nb] = Bb[k4 * 4 * BP + nb * 16];
 #pragma unroll
@@ -160,7 +156,7 @@ __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
         for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int om = mt * CA_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
+                const int om = mt * PI_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
                 if (om >= p.M) continue;
                 const int n = om / OHW, rem = om - n * OHW;
                 const long long plane = (long long)oc * OHW + rem;
@@ -176,39 +172,20 @@ __global__ __launch_bounds__(256) void conv_affine_kernel(const CAParams p) {
     }
 }
 
-__global__ void conv_affine_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int oc, int K, int nchunks,
-                                        int nb, long long total) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int bn = 16 * nb;
-    const int col = (int)(i % bn);
-    const long long row = i / bn;                       // n-tile * (nchunks * CA_KC) + k
-    const int k = (int)(row % ((long long)nchunks * CA_KC));
-    const int nt = (int)(row / ((long long)nchunks * CA_KC));
-    const int o = nt * bn + col;
-    packed[i] = (o < oc && k < K) ? w[(long long)o * K + k] : 0.f;   // OIHW: (c, ky, kx) is already the flat k
-}
-
-template <int KS, int STRIDE, int NB>
-int conv_affine_launch_one(const CAParams& p, dim3 grid, hipStream_t stream) {
-    constexpr auto kernel = conv_affine_kernel<KS, STRIDE, NB>;
-    if (int rc = set_max_dynamic_lds(lds_once<kernel>, reinterpret_cast<const void*>(kernel), CA_MAX_LDS)) return rc;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), (size_t)conv_affine_lds_floats(NB) * sizeof(float), stream, p);
-    return KBN_OK;
-}
-
 template <int KS, int STRIDE>
-int conv_affine_launch_nb(const CAParams& p, int nb, dim3 grid, hipStream_t stream) {
-    switch (nb) {
-        case 1: return conv_affine_launch_one<KS, STRIDE, 1>(p, grid, stream);
-        case 2: return conv_affine_launch_one<KS, STRIDE, 2>(p, grid, stream);
-        default: return conv_affine_launch_one<KS, STRIDE, 4>(p, grid, stream);
-    }
+int conv_affine_launch(const CAParams& p, int nb, dim3 grid, hipStream_t stream) {
+    return dispatch_nb(nb, [&](auto nbc) {
+        constexpr int NB = decltype(nbc)::value;
+        constexpr auto kernel = conv_affine_kernel<KS, STRIDE, NB>;
+        if (int rc = set_max_dynamic_lds(lds_once<kernel>, reinterpret_cast<const void*>(kernel), CA_MAX_LDS)) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), (size_t)pose_igemm_lds_floats(CA_KC, NB) * sizeof(float), stream, p);
+        return (int)KBN_OK;
+    });
 }
 
 template <int KS>
 int conv_affine_launch_stride(const CAParams& p, int stride, int nb, dim3 grid, hipStream_t stream) {
-    return stride == 1 ? conv_affine_launch_nb<KS, 1>(p, nb, grid, stream) : conv_affine_launch_nb<KS, 2>(p, nb, grid, stream);
+    return stride == 1 ? conv_affine_launch<KS, 1>(p, nb, grid, stream) : conv_affine_launch<KS, 2>(p, nb, grid, stream);
 }
 
 // ---- max pool ---------------------------------------------------------------------------------------------------------
@@ -252,25 +229,13 @@ static bool ca_kernel_size_ok(int ks) { return ks == 1 || ks == 3 || ks == 7; }
 
 extern "C" size_t kbn_conv2d_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size) {
     if (out_channels <= 0 || in_channels <= 0 || !ca_kernel_size_ok(kernel_size)) return 0;
-    const long long K = (long long)in_channels * kernel_size * kernel_size;
-    if (K > (1 << 24)) return 0;
-    const int nb = conv_affine_nb(out_channels);
-    const long long floats = (long long)ceil_div(out_channels, 16 * nb) * round_up((int)K, CA_KC) * (16 * nb);
-    return (size_t)floats * sizeof(float);
+    return pose_igemm_packed_bytes(out_channels, (long long)in_channels * kernel_size * kernel_size, CA_KC);
 }
 
 extern "C" int kbn_conv2d_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                                              int kernel_size, kbn_stream_t stream) {
-    if (!weight || !packed) return KBN_ERR_INVALID_ARGUMENT;
-    if (out_channels <= 0 || in_channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
-    const size_t bytes = kbn_conv2d_affine_packed_weight_bytes(out_channels, in_channels, kernel_size);
-    if (bytes == 0) return KBN_ERR_UNSUPPORTED;
-    const int K = in_channels * kernel_size * kernel_size;
-    const long long total = (long long)(bytes / sizeof(float));
-    hipLaunchKernelGGL(conv_affine_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       weight, packed, out_channels, K, ceil_div(K, CA_KC), conv_affine_nb(out_channels), total);
-    KBN_CHECK_LAUNCH();
-    return KBN_OK;
+    return pose_igemm_pack_weight(weight, packed, out_channels, in_channels, kernel_size, CA_KC,
+                                  kbn_conv2d_affine_packed_weight_bytes(out_channels, in_channels, kernel_size), (hipStream_t)stream);
 }
 
 extern "C" int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, const float* packed_weight, const float* scale,
@@ -283,14 +248,7 @@ extern "C" int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, co
     if (!ca_kernel_size_ok(kernel_size) || (stride != 1 && stride != 2)) return KBN_ERR_UNSUPPORTED;
     CAParams p{};
     int ctot = 0;
-    for (int s = 0; s < n_src; ++s) {
-        const kbn_conv_src& src = srcs[s];
-        if (src.kind != KBN_SRC_TENSOR) return KBN_ERR_UNSUPPORTED;
-        if (!src.data || src.channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.src_height != in_height || src.src_width != in_width) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.batch_stride < (long long)src.channels * in_height * in_width && n > 1) return KBN_ERR_INVALID_ARGUMENT;
-        ctot += src.channels;
-    }
+    if (int rc = check_tensor_srcs(srcs, n_src, n, in_height, in_width, &ctot)) return rc;
     p.src0 = srcs[0].data;
     p.bs0 = srcs[0].batch_stride;
     p.C0 = srcs[0].channels;
@@ -300,7 +258,7 @@ extern "C" int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, co
     p.OW = ceil_div(in_width, stride);
     const long long M = (long long)n * p.OH * p.OW;
     const long long K = (long long)ctot * kernel_size * kernel_size;
-    if (M > 0x7fffffffLL - CA_BM || K > (1 << 24) || (long long)in_height * in_width > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
+    if (M > 0x7fffffffLL - PI_BM || K > (1 << 24) || (long long)in_height * in_width > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
     const long long frame = (long long)out_channels * p.OH * p.OW;
     if (out_batch_stride < frame && n > 1) return KBN_ERR_INVALID_ARGUMENT;
     if (residual && residual_batch_stride < frame && n > 1) return KBN_ERR_INVALID_ARGUMENT;
@@ -320,10 +278,10 @@ extern "C" int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, co
     p.nchunks = ceil_div((int)K, CA_KC);
     p.act = apply_activation ? 1 : 0;
     p.slope = negative_slope;
-    const int nb = conv_affine_nb(out_channels);
+    const int nb = pose_igemm_nb(out_channels);
     const unsigned ntn = (unsigned)ceil_div(out_channels, 16 * nb);
     if (ntn > 65535u) return KBN_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)ceil_div((int)M, CA_BM), ntn);
+    const dim3 grid((unsigned)ceil_div((int)M, PI_BM), ntn);
     int rc;
     switch (kernel_size) {
         case 1: rc = conv_affine_launch_stride<1>(p, stride, nb, grid, (hipStream_t)stream); break;

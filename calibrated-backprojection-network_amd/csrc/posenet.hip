@@ -8,7 +8,7 @@
 // conv_s2_affine_kernel<KS, NB>: implicit GEMM on v_mfma_f32_16x16x4_f32 (exact fp32 products, as conv_igemm.hip).
 //   M = every output pixel of the BATCH in one index m = (frame * OH + oy) * OW + ox: a workgroup's 128-pixel tile may
 //       span rows and frames, so that the last maps (11 x 38 and below) fill workgroups with pixels of several frames;
-//   N = output channels, 16 NB per workgroup (NB in {1, 2, 4} from the channel count: conv_s2_affine_nb);
+//   N = output channels, 16 NB per workgroup (NB in {1, 2, 4} from the channel count: pose_igemm_nb, pose_igemm.h);
 //   K = (input channel, ky, kx) flattened, C k k, zero-padded to a multiple of 16 -- any channel count is legal.
 // 256 threads = 4 waves; wave w owns m-blocks 2 w, 2 w + 1 (16 pixels each) times all NB n-blocks.
 // K loop, 16 at a time: thread t gathers pixel t % 128 at k = t / 128 + 2 j (j < 8; k is wave-uniform, so the
@@ -22,15 +22,12 @@
 //
 // pose_head_kernel: one workgroup per frame.  The mean over H W of a 1 x 1 conv is the 1 x 1 conv of the per-channel
 // means: only another summation order (C h w products and sums either way), and it needs no 6-channel map.
-#include "kbn_common.h"
+#include "pose_igemm.h"
 
 namespace kbn {
 namespace {
 
-constexpr int S2_BM = 128, S2_KC = 16, S2_AP = S2_BM + 16;
-
-__host__ __device__ inline int conv_s2_affine_nb(int oc) { return oc <= 16 ? 1 : (oc <= 32 ? 2 : 4); }
-__host__ __device__ constexpr int conv_s2_affine_bp(int nb) { return nb == 1 ? 16 : 16 * nb + 16; }
+constexpr int S2_KC = 16;
 
 struct S2Params {
     const float* src0;
@@ -51,8 +48,8 @@ struct S2Params {
 
 template <int KS, int NB>
 __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
-    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = conv_s2_affine_bp(NB);
-    __shared__ float As[2][S2_KC * S2_AP];
+    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = pose_igemm_bp(NB);
+    __shared__ float As[2][S2_KC * PI_AP];
     __shared__ float Bs[2][S2_KC * BP];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -61,9 +58,9 @@ __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
     const int HW = p.H * p.W, OHW = p.OH * p.OW;
 
     // the pixel this thread gathers
-    const int pm = tid & (S2_BM - 1);
+    const int pm = tid & (PI_BM - 1);
     const int khalf = __builtin_amdgcn_readfirstlane(tid >> 7);   // 0 for waves 0, 1; 1 for waves 2, 3
-    const int m = mt * S2_BM + pm;
+    const int m = mt * PI_BM + pm;
     const bool mvalid = m < p.M;
     int fn = 0, iy0 = 0, ix0 = 0;
     if (mvalid) {
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
     };
     auto store_chunk = [&](int buf) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) As[buf][(khalf + 2 * j) * S2_AP + pm] = va[j];
+        for (int j = 0; j < 8; ++j) As[buf][(khalf + 2 * j) * PI_AP + pm] = va[j];
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const int e = tid + 256 * j;
@@ -120,13 +117,13 @@ __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
         const int buf = chunk & 1;
         const bool more = chunk + 1 < p.nchunks;
         if (more) load_chunk(chunk + 1);
-        const float* Ab = As[buf] + lk * S2_AP + wave * 32 + li;
+        const float* Ab = As[buf] + lk * PI_AP + wave * 32 + li;
         const float* Bb = Bs[buf] + lk * BP + li;
 #pragma unroll
         for (int k4 = 0; k4 < S2_KC / 4; ++k4) {
             float a[2], b[NB];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * S2_AP + mi * 16];
+            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * PI_AP + mi * 16];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) b[nb] = Bb[k4 * 4 * BP + nb * 16];
 #pragma unroll
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
         for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int om = mt * S2_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
+                const int om = mt * PI_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
                 if (om >= p.M) continue;
                 const int n = om / OHW, rem = om - n * OHW;
                 float v = acc[mi][nb][r] * sc + sh;
@@ -160,27 +157,12 @@ __global__ __launch_bounds__(256) void conv_s2_affine_kernel(const S2Params p) {
     }
 }
 
-__global__ void conv_s2_affine_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int oc, int K, int nchunks,
-                                           int nb, long long total) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int bn = 16 * nb;
-    const int col = (int)(i % bn);
-    const long long row = i / bn;                       // n-tile * (nchunks * 16) + k
-    const int k = (int)(row % ((long long)nchunks * S2_KC));
-    const int nt = (int)(row / ((long long)nchunks * S2_KC));
-    const int o = nt * bn + col;
-    packed[i] = (o < oc && k < K) ? w[(long long)o * K + k] : 0.f;   // OIHW: (c, ky, kx) is already the flat k
-}
-
 template <int KS>
-int conv_s2_affine_launch_nb(const S2Params& p, int nb, dim3 grid, hipStream_t stream) {
-    switch (nb) {
-        case 1: hipLaunchKernelGGL((conv_s2_affine_kernel<KS, 1>), grid, dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((conv_s2_affine_kernel<KS, 2>), grid, dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((conv_s2_affine_kernel<KS, 4>), grid, dim3(256), 0, stream, p); break;
-    }
-    return KBN_OK;
+int conv_s2_affine_launch(const S2Params& p, int nb, dim3 grid, hipStream_t stream) {
+    return dispatch_nb(nb, [&](auto nbc) {
+        hipLaunchKernelGGL((conv_s2_affine_kernel<KS, decltype(nbc)::value>), grid, dim3(256), 0, stream, p);
+        return KBN_OK;
+    });
 }
 
 // ---- pose head ------------------------------------------------------------------------------------------------------
@@ -250,25 +232,13 @@ static bool s2_kernel_size_ok(int ks) { return ks == 3 || ks == 5 || ks == 7; }
 
 extern "C" size_t kbn_conv2d_s2_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size) {
     if (out_channels <= 0 || in_channels <= 0 || !s2_kernel_size_ok(kernel_size)) return 0;
-    const long long K = (long long)in_channels * kernel_size * kernel_size;
-    if (K > (1 << 24)) return 0;
-    const int nb = conv_s2_affine_nb(out_channels);
-    const long long floats = (long long)ceil_div(out_channels, 16 * nb) * round_up((int)K, S2_KC) * (16 * nb);
-    return (size_t)floats * sizeof(float);
+    return pose_igemm_packed_bytes(out_channels, (long long)in_channels * kernel_size * kernel_size, S2_KC);
 }
 
 extern "C" int kbn_conv2d_s2_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                                                 int kernel_size, kbn_stream_t stream) {
-    if (!weight || !packed) return KBN_ERR_INVALID_ARGUMENT;
-    if (out_channels <= 0 || in_channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
-    const size_t bytes = kbn_conv2d_s2_affine_packed_weight_bytes(out_channels, in_channels, kernel_size);
-    if (bytes == 0) return KBN_ERR_UNSUPPORTED;
-    const int K = in_channels * kernel_size * kernel_size;
-    const long long total = (long long)(bytes / sizeof(float));
-    hipLaunchKernelGGL(conv_s2_affine_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       weight, packed, out_channels, K, ceil_div(K, S2_KC), conv_s2_affine_nb(out_channels), total);
-    KBN_CHECK_LAUNCH();
-    return KBN_OK;
+    return pose_igemm_pack_weight(weight, packed, out_channels, in_channels, kernel_size, S2_KC,
+                                  kbn_conv2d_s2_affine_packed_weight_bytes(out_channels, in_channels, kernel_size), (hipStream_t)stream);
 }
 
 extern "C" int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src, const float* packed_weight, const float* scale,
@@ -280,14 +250,7 @@ extern "C" int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src,
     if (!s2_kernel_size_ok(kernel_size)) return KBN_ERR_UNSUPPORTED;
     S2Params p{};
     int ctot = 0;
-    for (int s = 0; s < n_src; ++s) {
-        const kbn_conv_src& src = srcs[s];
-        if (src.kind != KBN_SRC_TENSOR) return KBN_ERR_UNSUPPORTED;
-        if (!src.data || src.channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.src_height != in_height || src.src_width != in_width) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.batch_stride < (long long)src.channels * in_height * in_width && n > 1) return KBN_ERR_INVALID_ARGUMENT;
-        ctot += src.channels;
-    }
+    if (int rc = check_tensor_srcs(srcs, n_src, n, in_height, in_width, &ctot)) return rc;
     p.src0 = srcs[0].data;
     p.bs0 = srcs[0].batch_stride;
     p.C0 = srcs[0].channels;
@@ -297,7 +260,7 @@ extern "C" int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src,
     p.OW = ceil_div(in_width, 2);
     const long long M = (long long)n * p.OH * p.OW;
     const long long K = (long long)ctot * kernel_size * kernel_size;
-    if (M > 0x7fffffffLL - S2_BM || K > (1 << 24) || (long long)in_height * in_width > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
+    if (M > 0x7fffffffLL - PI_BM || K > (1 << 24) || (long long)in_height * in_width > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
     if (out_batch_stride < (long long)out_channels * p.OH * p.OW && n > 1) return KBN_ERR_INVALID_ARGUMENT;
     p.wp = packed_weight;
     p.scale = scale;
@@ -313,14 +276,14 @@ extern "C" int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src,
     p.nchunks = ceil_div((int)K, S2_KC);
     p.act = apply_activation ? 1 : 0;
     p.slope = negative_slope;
-    const int nb = conv_s2_affine_nb(out_channels);
+    const int nb = pose_igemm_nb(out_channels);
     const unsigned ntn = (unsigned)ceil_div(out_channels, 16 * nb);
     if (ntn > 65535u) return KBN_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)ceil_div((int)M, S2_BM), ntn);
+    const dim3 grid((unsigned)ceil_div((int)M, PI_BM), ntn);
     switch (kernel_size) {
-        case 3: conv_s2_affine_launch_nb<3>(p, nb, grid, (hipStream_t)stream); break;
-        case 5: conv_s2_affine_launch_nb<5>(p, nb, grid, (hipStream_t)stream); break;
-        default: conv_s2_affine_launch_nb<7>(p, nb, grid, (hipStream_t)stream); break;
+        case 3: conv_s2_affine_launch<3>(p, nb, grid, (hipStream_t)stream); break;
+        case 5: conv_s2_affine_launch<5>(p, nb, grid, (hipStream_t)stream); break;
+        default: conv_s2_affine_launch<7>(p, nb, grid, (hipStream_t)stream); break;
     }
     KBN_CHECK_LAUNCH();
     return KBN_OK;

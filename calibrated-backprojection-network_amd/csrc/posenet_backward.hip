@@ -27,7 +27,7 @@
 //   (16 consecutive floats per row, two rows per half-wave) collide on one bank only.
 //
 // bn_stats_kernel, bn_bwd_sums_kernel: one workgroup per channel, fp64, a fixed tree.  bn_act_kernel, bn_bwd_apply_kernel: elementwise.
-#include "kbn_common.h"
+#include "pose_igemm.h"
 
 namespace kbn {
 namespace {
@@ -58,10 +58,7 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* lds /* 
 }
 
 // ---- data gradient ------------------------------------------------------------------------------------------------------
-constexpr int BD_BM = 128, BD_KC = 16, BD_AP = BD_BM + 16;
-
-__host__ __device__ inline int bd_nb(int c) { return c <= 16 ? 1 : (c <= 32 ? 2 : 4); }
-__host__ __device__ constexpr int bd_bp(int nb) { return nb == 1 ? 16 : 16 * nb + 16; }
+constexpr int BD_KC = 16;
 
 struct BdParams {
     const float* g;
@@ -78,8 +75,8 @@ struct BdParams {
 
 template <int KS, int NB>
 __global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p) {
-    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = bd_bp(NB);
-    __shared__ float As[2][BD_KC * BD_AP];
+    constexpr int KK = KS * KS, PAD = KS / 2, BN = 16 * NB, BP = pose_igemm_bp(NB);
+    __shared__ float As[2][BD_KC * PI_AP];
     __shared__ float Bs[2][BD_KC * BP];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -87,9 +84,9 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p)
     const int mt = blockIdx.x, nt = blockIdx.y;
     const int HW = p.H * p.W, OHW = p.OH * p.OW;
 
-    const int pm = tid & (BD_BM - 1);
+    const int pm = tid & (PI_BM - 1);
     const int khalf = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int m = mt * BD_BM + pm;
+    const int m = mt * PI_BM + pm;
     const bool mvalid = m < p.M;
     int fn = 0, iyp = 0, ixp = 0;
     if (mvalid) {
@@ -124,7 +121,7 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p)
     };
     auto store_chunk = [&](int buf) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) As[buf][(khalf + 2 * j) * BD_AP + pm] = va[j];
+        for (int j = 0; j < 8; ++j) As[buf][(khalf + 2 * j) * PI_AP + pm] = va[j];
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             const int e = tid + 256 * j;
@@ -145,13 +142,13 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p)
         const int buf = chunk & 1;
         const bool more = chunk + 1 < p.nchunks;
         if (more) load_chunk(chunk + 1);
-        const float* Ab = As[buf] + lk * BD_AP + wave * 32 + li;
+        const float* Ab = As[buf] + lk * PI_AP + wave * 32 + li;
         const float* Bb = Bs[buf] + lk * BP + li;
 #pragma unroll
         for (int k4 = 0; k4 < BD_KC / 4; ++k4) {
             float a[2], b[NB];
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * BD_AP + mi * 16];
+            for (int mi = 0; mi < 2; ++mi) a[mi] = Ab[k4 * 4 * PI_AP + mi * 16];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) b[nb] = Bb[k4 * 4 * BP + nb * 16];
 #pragma unroll
@@ -176,7 +173,7 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_data_kernel(const BdParams p)
         for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int om = mt * BD_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
+                const int om = mt * PI_BM + (wave * 2 + mi) * 16 + lk * 4 + r;
                 if (om >= p.M) continue;
                 const int n = om / HW, rem = om - n * HW;
                 base[(long long)n * bs + rem] = acc[mi][nb][r];
@@ -205,12 +202,11 @@ __global__ void conv_s2_bwd_data_pack_kernel(const float* __restrict__ w, float*
 }
 
 template <int KS>
-void bwd_data_launch_nb(const BdParams& p, int nb, dim3 grid, hipStream_t stream) {
-    switch (nb) {
-        case 1: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 1>), grid, dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 2>), grid, dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, 4>), grid, dim3(256), 0, stream, p); break;
-    }
+int bwd_data_launch(const BdParams& p, int nb, dim3 grid, hipStream_t stream) {
+    return dispatch_nb(nb, [&](auto nbc) {
+        hipLaunchKernelGGL((conv_s2_bwd_data_kernel<KS, decltype(nbc)::value>), grid, dim3(256), 0, stream, p);
+        return KBN_OK;
+    });
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------
@@ -514,11 +510,7 @@ using namespace kbn;
 
 extern "C" size_t kbn_conv2d_s2_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size) {
     if (out_channels <= 0 || in_channels <= 0 || !ks_ok(kernel_size)) return 0;
-    const long long K = (long long)out_channels * kernel_size * kernel_size;
-    if (K > (1 << 24)) return 0;
-    const int nb = bd_nb(in_channels);
-    const long long floats = (long long)ceil_div(in_channels, 16 * nb) * round_up((int)K, BD_KC) * (16 * nb);
-    return (size_t)floats * sizeof(float);
+    return pose_igemm_packed_bytes(in_channels, (long long)out_channels * kernel_size * kernel_size, BD_KC);
 }
 
 extern "C" int kbn_conv2d_s2_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
@@ -530,7 +522,7 @@ extern "C" int kbn_conv2d_s2_backward_data_pack_weight(const float* weight, floa
     const int kk = kernel_size * kernel_size, K = out_channels * kk;
     const long long total = (long long)(bytes / sizeof(float));
     hipLaunchKernelGGL(conv_s2_bwd_data_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       weight, packed, in_channels, kk, K, ceil_div(K, BD_KC), bd_nb(in_channels), total);
+                       weight, packed, in_channels, kk, K, ceil_div(K, BD_KC), pose_igemm_nb(in_channels), total);
     KBN_CHECK_LAUNCH();
     return KBN_OK;
 }
@@ -546,7 +538,7 @@ extern "C" int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad
     const long long HW = (long long)in_height * in_width;
     const long long M = (long long)n * HW;
     const long long K = (long long)out_channels * kernel_size * kernel_size;
-    if (M > 0x7fffffffLL - BD_BM || K > (1 << 24)) return KBN_ERR_UNSUPPORTED;
+    if (M > 0x7fffffffLL - PI_BM || K > (1 << 24)) return KBN_ERR_UNSUPPORTED;
     BdParams p{};
     p.OH = ceil_div(in_height, 2);
     p.OW = ceil_div(in_width, 2);
@@ -571,14 +563,14 @@ extern "C" int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad
     p.M = (int)M;
     p.K = (int)K;
     p.nchunks = ceil_div((int)K, BD_KC);
-    const int nb = bd_nb(p.Ctot);
+    const int nb = pose_igemm_nb(p.Ctot);
     const unsigned ntn = (unsigned)ceil_div(p.Ctot, 16 * nb);
     if (ntn > 65535u) return KBN_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)ceil_div((int)M, BD_BM), ntn);
+    const dim3 grid((unsigned)ceil_div((int)M, PI_BM), ntn);
     switch (kernel_size) {
-        case 3: bwd_data_launch_nb<3>(p, nb, grid, (hipStream_t)stream); break;
-        case 5: bwd_data_launch_nb<5>(p, nb, grid, (hipStream_t)stream); break;
-        default: bwd_data_launch_nb<7>(p, nb, grid, (hipStream_t)stream); break;
+        case 3: bwd_data_launch<3>(p, nb, grid, (hipStream_t)stream); break;
+        case 5: bwd_data_launch<5>(p, nb, grid, (hipStream_t)stream); break;
+        default: bwd_data_launch<7>(p, nb, grid, (hipStream_t)stream); break;
     }
     KBN_CHECK_LAUNCH();
     return KBN_OK;
@@ -600,14 +592,7 @@ extern "C" int kbn_conv2d_s2_backward_weight(const kbn_conv_src* srcs, int n_src
     if (!ks_ok(kernel_size)) return KBN_ERR_UNSUPPORTED;
     BwParams p{};
     int ctot = 0;
-    for (int s = 0; s < n_src; ++s) {
-        const kbn_conv_src& src = srcs[s];
-        if (src.kind != KBN_SRC_TENSOR) return KBN_ERR_UNSUPPORTED;
-        if (!src.data || src.channels <= 0) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.src_height != in_height || src.src_width != in_width) return KBN_ERR_INVALID_ARGUMENT;
-        if (src.batch_stride < (long long)src.channels * in_height * in_width && n > 1) return KBN_ERR_INVALID_ARGUMENT;
-        ctot += src.channels;
-    }
+    if (int rc = check_tensor_srcs(srcs, n_src, n, in_height, in_width, &ctot)) return rc;
     if (ctot >= (1 << 24)) return KBN_ERR_UNSUPPORTED;   // the column code keeps the channel above 6 bits of tap
     const BwPlan pl = bwd_weight_plan(n, out_channels, ctot, kernel_size, in_height, in_width, splits);
     if (!pl.ok) return KBN_ERR_UNSUPPORTED;

@@ -1445,20 +1445,56 @@ def pose_matrix(v: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ pose network (eval mode)
-@_on_tensor_device
-def pack_conv2d_s2_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """OIHW (k in {3, 5, 7}, any channel counts) -> the [filter tile][K chunk][16][filters] order conv2d_s2_affine reads
-    (kbn_conv2d_s2_affine_pack_weight); `out`: an existing blob of the right size to re-pack into."""
+def _pack_pose_weight(fn: str, family: str, sizes_text: str, weight: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """The three pose-network pack wrappers: OIHW -> the blob of kbn_<family>_pack_weight, sized by kbn_<family>_packed_weight_bytes."""
     lib = _lib.load()
     w = _weight(weight)
     oc, cin, kh, kw = w.shape
     if kh != kw:
         raise KbnError("square kernels only")
-    nbytes = lib.kbn_conv2d_s2_affine_packed_weight_bytes(oc, cin, kh)
+    nbytes = getattr(lib, f"kbn_{family}_packed_weight_bytes")(oc, cin, kh)
     if nbytes == 0:
-        raise KbnError(f"conv2d_s2_affine: unsupported weight shape {tuple(w.shape)} (kernel size 3, 5 or 7)")
-    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_s2_affine_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
-                      "kbn_conv2d_s2_affine_pack_weight")
+        raise KbnError(f"{fn}: unsupported weight shape {tuple(w.shape)} (kernel size {sizes_text})")
+    pack = getattr(lib, f"kbn_{family}_pack_weight")
+    return _pack_into(out, nbytes, w, lambda p: pack(w.data_ptr(), p, oc, cin, kh, _stream()), f"kbn_{family}_pack_weight")
+
+
+def _conv_inputs(fn: str, inputs):
+    """The one or two N x C_i x H x W tensors a pose conv reads in place -> (inputs, sources, n, h, w, total channels)."""
+    inputs = list(inputs)
+    if not 1 <= len(inputs) <= 2:
+        raise KbnError(f"{fn}: one or two inputs, got {len(inputs)}")
+    srcs = [tensor_src(t.detach() if isinstance(t, torch.Tensor) else t, f"inputs[{i}]") for i, t in enumerate(inputs)]
+    n, _, h, w = inputs[0].shape
+    for i, t in enumerate(inputs[1:], 1):
+        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
+            raise KbnError(f"{fn}: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
+    if n < 1 or h < 1 or w < 1 or any(s.channels < 1 for s in srcs):
+        raise KbnError(f"{fn}: empty input {tuple(inputs[0].shape)}")
+    return inputs, srcs, n, h, w, sum(s.channels for s in srcs)
+
+
+def _affine_conv_args(fn: str, bytes_fn, inputs, packed_weight, scale, shift, out_channels: int, kernel_size: int):
+    """What conv2d_s2_affine and conv2d_affine check alike: the inputs (_conv_inputs), the blob's size (`bytes_fn`: the family's
+    kbn_*_packed_weight_bytes) and scale / shift -> (inputs, sources, n, h, w, total channels, floats in the blob)."""
+    inputs, srcs, n, h, w, cin = _conv_inputs(fn, inputs)
+    _require(packed_weight, "packed_weight", 1)
+    want = bytes_fn(out_channels, cin, kernel_size) // 4
+    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
+        raise KbnError(f"{fn}: packed_weight holds {packed_weight.numel()} floats, a {out_channels} x {cin} x "
+                       f"{kernel_size} x {kernel_size} weight packs into {want}")
+    for t, name in ((scale, "scale"), (shift, "shift")):
+        _require(t, name, 1)
+        if t.numel() != out_channels or not t.is_contiguous():
+            raise KbnError(f"{fn}: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
+    return inputs, srcs, n, h, w, cin, want
+
+
+@_on_tensor_device
+def pack_conv2d_s2_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW (k in {3, 5, 7}, any channel counts) -> the [filter tile][K chunk][16][filters] order conv2d_s2_affine reads
+    (kbn_conv2d_s2_affine_pack_weight); `out`: an existing blob of the right size to re-pack into."""
+    return _pack_pose_weight("conv2d_s2_affine", "conv2d_s2_affine", "3, 5 or 7", weight, out)
 
 
 @_on_tensor_device
@@ -1470,28 +1506,10 @@ def conv2d_s2_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor
     or two N x C_i x H x W tensors read in place (no concat); `scale` / `shift`: out_channels floats; `negative_slope` None: no
     activation; `out`: an N x out_channels x ceil(H / 2) x ceil(W / 2) tensor or channel slice to write into."""
     lib = _lib.load()
-    inputs = list(inputs)
-    if not 1 <= len(inputs) <= 2:
-        raise KbnError(f"conv2d_s2_affine: one or two inputs, got {len(inputs)}")
     if kernel_size not in (3, 5, 7):
         raise KbnError(f"conv2d_s2_affine: kernel size 3, 5 or 7, got {kernel_size}")
-    srcs = [tensor_src(t, f"inputs[{i}]") for i, t in enumerate(inputs)]
-    n, _, h, w = inputs[0].shape
-    for i, t in enumerate(inputs[1:], 1):
-        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
-            raise KbnError(f"conv2d_s2_affine: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
-    if n < 1 or h < 1 or w < 1:
-        raise KbnError(f"conv2d_s2_affine: empty input {tuple(inputs[0].shape)}")
-    cin = sum(s.channels for s in srcs)
-    _require(packed_weight, "packed_weight", 1)
-    want = lib.kbn_conv2d_s2_affine_packed_weight_bytes(out_channels, cin, kernel_size) // 4
-    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
-        raise KbnError(f"conv2d_s2_affine: packed_weight holds {packed_weight.numel()} floats, a {out_channels} x {cin} x "
-                       f"{kernel_size} x {kernel_size} weight packs into {want}")
-    for t, name in ((scale, "scale"), (shift, "shift")):
-        _require(t, name, 1)
-        if t.numel() != out_channels or not t.is_contiguous():
-            raise KbnError(f"conv2d_s2_affine: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
+    inputs, srcs, n, h, w, cin, _ = _affine_conv_args("conv2d_s2_affine", lib.kbn_conv2d_s2_affine_packed_weight_bytes, inputs,
+                                                      packed_weight, scale, shift, out_channels, kernel_size)
     oh, ow = (h + 1) // 2, (w + 1) // 2
     out = _out_tensor(out, (n, out_channels, oh, ow), inputs[0].device, planes=True)
     optr, obs = _planes(out, "out")
@@ -1533,21 +1551,6 @@ def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = Fal
 
 
 # ------------------------------------------------------------------ pose network (training: csrc/posenet_backward.hip)
-def _s2_inputs(fn: str, inputs):
-    """The one or two N x C_i x H x W tensors of a stride-2 conv -> (inputs, sources, n, h, w, total channels)."""
-    inputs = list(inputs)
-    if not 1 <= len(inputs) <= 2:
-        raise KbnError(f"{fn}: one or two inputs, got {len(inputs)}")
-    srcs = [tensor_src(t.detach() if isinstance(t, torch.Tensor) else t, f"inputs[{i}]") for i, t in enumerate(inputs)]
-    n, _, h, w = inputs[0].shape
-    for i, t in enumerate(inputs[1:], 1):
-        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
-            raise KbnError(f"{fn}: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
-    if n < 1 or h < 1 or w < 1 or any(s.channels < 1 for s in srcs):
-        raise KbnError(f"{fn}: empty input {tuple(inputs[0].shape)}")
-    return inputs, srcs, n, h, w, sum(s.channels for s in srcs)
-
-
 def _s2_kernel_size(fn: str, kernel_size):
     if kernel_size not in (3, 5, 7):
         raise KbnError(f"{fn}: kernel size 3, 5 or 7, got {kernel_size}")
@@ -1557,16 +1560,7 @@ def _s2_kernel_size(fn: str, kernel_size):
 def pack_conv2d_s2_backward_data_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """OIHW (k in {3, 5, 7}) -> the transposed order conv2d_s2_backward_data reads: [input-channel tile][(filter, tap) chunk][16]
     [input channels] (kbn_conv2d_s2_backward_data_pack_weight; not the forward's blob).  `out`: a blob to re-pack into."""
-    lib = _lib.load()
-    w = _weight(weight)
-    oc, cin, kh, kw = w.shape
-    if kh != kw:
-        raise KbnError("square kernels only")
-    nbytes = lib.kbn_conv2d_s2_backward_data_packed_weight_bytes(oc, cin, kh)
-    if nbytes == 0:
-        raise KbnError(f"conv2d_s2_backward_data: unsupported weight shape {tuple(w.shape)} (kernel size 3, 5 or 7)")
-    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_s2_backward_data_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
-                      "kbn_conv2d_s2_backward_data_pack_weight")
+    return _pack_pose_weight("conv2d_s2_backward_data", "conv2d_s2_backward_data", "3, 5 or 7", weight, out)
 
 
 @_on_tensor_device
@@ -1620,7 +1614,7 @@ def conv2d_s2_backward_weight(inputs: Sequence[torch.Tensor], grad_out: torch.Te
     are a function of the arguments (and of `splits`) alone."""
     lib = _lib.load()
     _s2_kernel_size("conv2d_s2_backward_weight", kernel_size)
-    inputs, srcs, n, h, w, cin = _s2_inputs("conv2d_s2_backward_weight", inputs)
+    inputs, srcs, n, h, w, cin = _conv_inputs("conv2d_s2_backward_weight", inputs)
     gptr, gbs = _planes(grad_out, "grad_out")
     oc, oh, ow = grad_out.shape[1], (h + 1) // 2, (w + 1) // 2
     if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
@@ -1823,7 +1817,7 @@ def conv2d_s2(inputs: Sequence[torch.Tensor], weight: torch.Tensor, packed: Opti
     if w.shape[2] != w.shape[3]:
         raise KbnError("square kernels only")
     _s2_kernel_size("conv2d_s2", w.shape[2])
-    _, _, _, _, _, cin = _s2_inputs("conv2d_s2", inputs)
+    _, _, _, _, _, cin = _conv_inputs("conv2d_s2", inputs)
     if cin != w.shape[1]:
         raise KbnError(f"conv2d_s2: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
     if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
@@ -1849,16 +1843,7 @@ def pose_head_recorded(latent: torch.Tensor, weight: torch.Tensor):
 def pack_conv2d_affine_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """OIHW (k in {1, 3, 7}, any channel counts) -> the [filter tile][K chunk][k][filters] order conv2d_affine reads
     (kbn_conv2d_affine_pack_weight; not the blob of conv2d_s2_affine); `out`: an existing blob of the right size to re-pack into."""
-    lib = _lib.load()
-    w = _weight(weight)
-    oc, cin, kh, kw = w.shape
-    if kh != kw:
-        raise KbnError("square kernels only")
-    nbytes = lib.kbn_conv2d_affine_packed_weight_bytes(oc, cin, kh)
-    if nbytes == 0:
-        raise KbnError(f"conv2d_affine: unsupported weight shape {tuple(w.shape)} (kernel size 1, 3 or 7)")
-    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_affine_pack_weight(w.data_ptr(), p, oc, cin, kh, _stream()),
-                      "kbn_conv2d_affine_pack_weight")
+    return _pack_pose_weight("conv2d_affine", "conv2d_affine", "1, 3 or 7", weight, out)
 
 
 @_on_tensor_device
@@ -1872,30 +1857,12 @@ def conv2d_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor, s
     floats; `negative_slope` None: no activation at all; `residual` / `out`: N x out_channels x ceil(H / stride) x ceil(W / stride)
     tensors or channel slices."""
     lib = _lib.load()
-    inputs = list(inputs)
-    if not 1 <= len(inputs) <= 2:
-        raise KbnError(f"conv2d_affine: one or two inputs, got {len(inputs)}")
     if kernel_size not in (1, 3, 7):
         raise KbnError(f"conv2d_affine: kernel size 1, 3 or 7, got {kernel_size}")
     if stride not in (1, 2):
         raise KbnError(f"conv2d_affine: stride 1 or 2, got {stride}")
-    srcs = [tensor_src(t, f"inputs[{i}]") for i, t in enumerate(inputs)]
-    n, _, h, w = inputs[0].shape
-    for i, t in enumerate(inputs[1:], 1):
-        if t.shape[0] != n or tuple(t.shape[2:]) != (h, w):
-            raise KbnError(f"conv2d_affine: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
-    if n < 1 or h < 1 or w < 1:
-        raise KbnError(f"conv2d_affine: empty input {tuple(inputs[0].shape)}")
-    cin = sum(s.channels for s in srcs)
-    _require(packed_weight, "packed_weight", 1)
-    want = lib.kbn_conv2d_affine_packed_weight_bytes(out_channels, cin, kernel_size) // 4
-    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
-        raise KbnError(f"conv2d_affine: packed_weight holds {packed_weight.numel()} floats, a {out_channels} x {cin} x "
-                       f"{kernel_size} x {kernel_size} weight packs into {want}")
-    for t, name in ((scale, "scale"), (shift, "shift")):
-        _require(t, name, 1)
-        if t.numel() != out_channels or not t.is_contiguous():
-            raise KbnError(f"conv2d_affine: {name} must be {out_channels} contiguous floats, got {tuple(t.shape)}")
+    inputs, srcs, n, h, w, cin, want = _affine_conv_args("conv2d_affine", lib.kbn_conv2d_affine_packed_weight_bytes, inputs,
+                                                         packed_weight, scale, shift, out_channels, kernel_size)
     oh, ow = -(-h // stride), -(-w // stride)
     rptr, rbs = None, 0
     if residual is not None:

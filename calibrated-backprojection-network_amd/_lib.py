@@ -116,6 +116,14 @@ SIGNATURES = {
     "kbn_conv2d_affine_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "kbn_conv2d_affine_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _P]),
     "kbn_maxpool3x3s2_forward": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _P]),
+    "kbn_conv2d_backward_weight_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "kbn_conv2d_backward_weight": (_I, [C.POINTER(ConvSrc), _I, _P, _L, _P, _I, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
+    "kbn_conv2d_backward_data_packed_weight_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "kbn_conv2d_backward_data_pack_weight": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "kbn_conv2d_backward_data": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "kbn_maxpool3x3s2_backward": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
+    "kbn_add_act_forward": (_I, [_P, _P, _P, _L, _I, _F, _P]),
+    "kbn_add_act_backward": (_I, [_P, _P, _P, _L, _I, _F, _P]),
     "kbn_depth_head_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "kbn_conv_head_forward": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
     "kbn_conv_tail_packed_weight_bytes": (C.c_size_t, [_I]),

@@ -27,7 +27,7 @@
 //   (16 consecutive floats per row, two rows per half-wave) collide on one bank only.
 //
 // bn_stats_kernel, bn_bwd_sums_kernel: one workgroup per channel, fp64, a fixed tree.  bn_act_kernel, bn_bwd_apply_kernel: elementwise.
-#include "pose_igemm.h"
+#include "conv_bwd_weight.h"
 
 namespace kbn {
 namespace {
@@ -210,27 +210,7 @@ int bwd_data_launch(const BdParams& p, int nb, dim3 grid, hipStream_t stream) {
 }
 
 // ---- weight gradient ----------------------------------------------------------------------------------------------------
-constexpr int BW_BN = 64, BW_KC = 32, BW_BP = BW_BN + 17;
-constexpr int BW_TARGET_WORKGROUPS = 512;   // two per CU of a 256-CU device; a constant, so that the split (and the bits) do not follow the device
-constexpr int BW_MIN_CHUNKS = 4, BW_MAX_SPLITS = 1024;
-
-__host__ __device__ inline int bw_mb(int oc) { return oc <= 16 ? 1 : (oc <= 32 ? 2 : 4); }
-__host__ __device__ constexpr int bw_ap(int mb) { return mb == 1 ? 49 : 16 * mb + 17; }   // = 17 mod 32
-
-struct BwParams {
-    const float* g;
-    long long gbs;
-    const float* src0;
-    const float* src1;
-    long long bs0, bs1;
-    int C0, Ctot;
-    float* out;   // the weight gradient (one split) or the scratch planes
-    int N, OC, H, W, OH, OW;
-    int M;        // N * OH * OW
-    int CK;       // Ctot k k
-    int nchunks, cps;   // chunks of 32 pixels; chunks per split
-};
-
+// the tile constants, BwParams, bwd_weight_plan and sum_splits_kernel: conv_bwd_weight.h (shared with conv_affine_backward.hip)
 template <int KS, int MB>
 __global__ __launch_bounds__(256) void conv_s2_bwd_weight_kernel(const BwParams p) {
     constexpr int KK = KS * KS, PAD = KS / 2, BM = 16 * MB, AP = bw_ap(MB);
@@ -341,14 +321,6 @@ __global__ __launch_bounds__(256) void conv_s2_bwd_weight_kernel(const BwParams 
     }
 }
 
-__global__ void sum_splits_kernel(const float* __restrict__ planes, float* __restrict__ out, long long total, int splits) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    float s = planes[i];
-    for (int z = 1; z < splits; ++z) s += planes[(long long)z * total + i];   // split order, always
-    out[i] = s;
-}
-
 template <int KS>
 void bwd_weight_launch_mb(const BwParams& p, int mb, dim3 grid, hipStream_t stream) {
     switch (mb) {
@@ -358,42 +330,7 @@ void bwd_weight_launch_mb(const BwParams& p, int mb, dim3 grid, hipStream_t stre
     }
 }
 
-struct BwPlan {
-    int ok, OH, OW, M, CK, nchunks, cps, splits, mb;
-    unsigned ntn, ntm;
-};
-
 bool ks_ok(int ks) { return ks == 3 || ks == 5 || ks == 7; }
-
-// `splits` <= 0: chosen here (enough workgroups for the chip, at least BW_MIN_CHUNKS chunks each); > 0: as asked, at most one per chunk
-BwPlan bwd_weight_plan(int n, int oc, int cin, int ks, int h, int w, int splits) {
-    BwPlan pl{};
-    if (n <= 0 || oc <= 0 || cin <= 0 || h <= 0 || w <= 0 || !ks_ok(ks)) return pl;
-    pl.OH = ceil_div(h, 2);
-    pl.OW = ceil_div(w, 2);
-    const long long M = (long long)n * pl.OH * pl.OW;
-    const long long CK = (long long)cin * ks * ks;
-    if (M > 0x7fffffffLL - BW_KC || CK > (1 << 24) || (long long)h * w > 0x7fffffffLL || (long long)oc * CK > 0x7fffffffLL) return pl;
-    pl.M = (int)M;
-    pl.CK = (int)CK;
-    pl.nchunks = ceil_div(pl.M, BW_KC);
-    pl.mb = bw_mb(oc);
-    pl.ntn = (unsigned)ceil_div(pl.CK, BW_BN);
-    pl.ntm = (unsigned)ceil_div(oc, 16 * pl.mb);
-    if (pl.ntm > 65535u) return pl;
-    if (splits <= 0) {
-        const long long tiles = (long long)pl.ntn * pl.ntm;
-        long long s = (BW_TARGET_WORKGROUPS + tiles - 1) / tiles;
-        s = s < pl.nchunks / BW_MIN_CHUNKS ? s : pl.nchunks / BW_MIN_CHUNKS;
-        splits = (int)(s < 1 ? 1 : s);
-    }
-    if (splits > BW_MAX_SPLITS) splits = BW_MAX_SPLITS;
-    if (splits > pl.nchunks) splits = pl.nchunks;
-    pl.cps = ceil_div(pl.nchunks, splits);
-    pl.splits = ceil_div(pl.nchunks, pl.cps);   // no empty split
-    pl.ok = 1;
-    return pl;
-}
 
 // ---- BatchNorm2d --------------------------------------------------------------------------------------------------------
 // mean and BIASED variance of channel blockIdx.x over N, H, W: two passes in fp64 (the mean, then the centred squares).
@@ -578,7 +515,8 @@ extern "C" int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad
 
 extern "C" size_t kbn_conv2d_s2_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size,
                                                               int in_height, int in_width, int splits) {
-    const BwPlan pl = bwd_weight_plan(n, out_channels, in_channels, kernel_size, in_height, in_width, splits);
+    if (!ks_ok(kernel_size)) return 0;
+    const BwPlan pl = bwd_weight_plan(n, out_channels, in_channels, kernel_size, 2, in_height, in_width, splits);
     if (!pl.ok || pl.splits <= 1) return 0;
     return (size_t)pl.splits * out_channels * pl.CK * sizeof(float);
 }
@@ -594,7 +532,7 @@ extern "C" int kbn_conv2d_s2_backward_weight(const kbn_conv_src* srcs, int n_src
     int ctot = 0;
     if (int rc = check_tensor_srcs(srcs, n_src, n, in_height, in_width, &ctot)) return rc;
     if (ctot >= (1 << 24)) return KBN_ERR_UNSUPPORTED;   // the column code keeps the channel above 6 bits of tap
-    const BwPlan pl = bwd_weight_plan(n, out_channels, ctot, kernel_size, in_height, in_width, splits);
+    const BwPlan pl = bwd_weight_plan(n, out_channels, ctot, kernel_size, 2, in_height, in_width, splits);
     if (!pl.ok) return KBN_ERR_UNSUPPORTED;
     if (grad_out_batch_stride < (long long)out_channels * pl.OH * pl.OW && n > 1) return KBN_ERR_INVALID_ARGUMENT;
     const long long total = (long long)out_channels * pl.CK;

@@ -1884,10 +1884,7 @@ def conv2d_affine(inputs: Sequence[torch.Tensor], packed_weight: torch.Tensor, s
     return out
 
 
-@_on_tensor_device
-def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """torch.nn.MaxPool2d(3, stride=2, padding=1) (kbn_maxpool3x3s2_forward; reference src/networks.py:747): N x C x H x W ->
-    N x C x ceil(H / 2) x ceil(W / 2).  Padding never wins; a NaN in the window is the result.  `out`: a tensor or channel slice."""
+def _maxpool3x3s2_launch(x, out):
     lib = _lib.load()
     ptr, bs = _planes(x, "x")
     n, c, h, w = x.shape
@@ -1900,3 +1897,287 @@ def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
                   lambda: lib.kbn_maxpool3x3s2_forward(ptr, bs, optr, obs, n, c, h, w, _stream()),
                   nbytes=4.0 * n * c * (h * w + oh * ow)), "kbn_maxpool3x3s2_forward")
     return out
+
+
+@_on_tensor_device
+def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.nn.MaxPool2d(3, stride=2, padding=1) (kbn_maxpool3x3s2_forward; reference src/networks.py:747): N x C x H x W ->
+    N x C x ceil(H / 2) x ceil(W / 2).  Padding never wins; a NaN in the window is the result.  `out`: a tensor or channel slice,
+    only without autograd.  Differentiable with respect to x when grad mode is on and x requires grad (maxpool3x3s2_backward)."""
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        if out is not None:
+            raise KbnError("maxpool3x3s2: `out` cannot be given when the call is recorded for autograd")
+        _planes(x, "x")
+        return _MaxPool3x3S2.apply(x)
+    return _maxpool3x3s2_launch(x, out)
+
+
+# ------------------------------------------------------------------ ResNet pose networks (training: csrc/conv_affine_backward.hip)
+_BACKWARD_CASES = ((3, 1), (1, 1), (1, 2))   # (kernel size, stride) of the new gradients; (3, 2) and (7, 2) are conv2d_s2_backward_*'s
+
+
+def _backward_case(fn: str, kernel_size, stride):
+    if (kernel_size, stride) not in _BACKWARD_CASES:
+        raise KbnError(f"{fn}: (kernel size, stride) one of {_BACKWARD_CASES}, got ({kernel_size}, {stride}); the 3 x 3 and 7 x 7 convs "
+                       "at stride 2 have conv2d_s2_backward_data / conv2d_s2_backward_weight")
+
+
+@_on_tensor_device
+def conv2d_backward_weight(inputs: Sequence[torch.Tensor], grad_out: torch.Tensor, kernel_size: int, stride: int,
+                           splits: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of conv_{k x k, stride, padding k // 2}(cat(inputs, 1)) with respect to its weight for (k, stride) in
+    {(3, 1), (1, 1), (1, 2)} (kbn_conv2d_backward_weight): -> F x sum(C_i) x k x k, plain OIHW.  The contract of
+    conv2d_s2_backward_weight: the sum over the batch's output pixels is split over `splits` workgroups per tile (None: chosen
+    from the shape) whose partial sums a second launch adds in split order; the bits are a function of the arguments (and of
+    `splits`) alone."""
+    lib = _lib.load()
+    _backward_case("conv2d_backward_weight", kernel_size, stride)
+    inputs, srcs, n, h, w, cin = _conv_inputs("conv2d_backward_weight", inputs)
+    gptr, gbs = _planes(grad_out, "grad_out")
+    oc, oh, ow = grad_out.shape[1], -(-h // stride), -(-w // stride)
+    if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
+        raise KbnError(f"conv2d_backward_weight: grad_out is {tuple(grad_out.shape)}, the conv of inputs {tuple(inputs[0].shape)} "
+                       f"has {n} frames of {oh} x {ow} maps")
+    if splits is not None and (not isinstance(splits, int) or splits < 1):
+        raise KbnError(f"conv2d_backward_weight: splits must be a positive integer or None, got {splits!r}")
+    splits = 0 if splits is None else splits
+    out = _out_tensor(out, (oc, cin, kernel_size, kernel_size), grad_out.device, "conv2d_backward_weight: out")
+    nbytes = lib.kbn_conv2d_backward_weight_scratch_bytes(n, oc, cin, kernel_size, stride, h, w, splits)
+    scratch = torch.empty(nbytes // 4, device=grad_out.device, dtype=torch.float32) if nbytes else None
+    arr = (ConvSrc * len(srcs))(*srcs)
+    k2 = kernel_size * kernel_size
+    mt = 16 if oc <= 16 else (32 if oc <= 32 else 64)
+    check(_launch(f"conv_bwd_weight<{kernel_size},{stride},{mt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
+                  lambda: lib.kbn_conv2d_backward_weight(arr, len(srcs), gptr, gbs, out.data_ptr(), n, oc, kernel_size, stride, h, w,
+                                                         splits, scratch.data_ptr() if scratch is not None else None, nbytes,
+                                                         _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 32) * 32) * (-(-cin * k2 // 64) * 64) * (-(-oc // mt) * mt), pipe="fp32",
+                  nbytes=_src_bytes(srcs, n) + 4.0 * (n * oc * oh * ow + oc * cin * k2)), "kbn_conv2d_backward_weight")
+    return out
+
+
+@_on_tensor_device
+def pack_conv2d_backward_data_weight(weight: torch.Tensor, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW -> the blob conv2d_backward_data reads at this stride (kbn_conv2d_backward_data_pack_weight).  Stride 1 (k 1 or 3): the
+    weight transposed (O <-> I) with both tap axes flipped, in conv2d_affine's packed order, and a unit scale and zero shift
+    behind it -- the data gradient is then that forward conv of grad_out.  (1, 2): the weight as it is.  `out`: a blob to re-pack into."""
+    lib = _lib.load()
+    w = _weight(weight)
+    oc, cin, kh, kw = w.shape
+    if kh != kw:
+        raise KbnError("square kernels only")
+    _backward_case("pack_conv2d_backward_data_weight", kh, stride)
+    nbytes = lib.kbn_conv2d_backward_data_packed_weight_bytes(oc, cin, kh, stride)
+    if nbytes == 0:
+        raise KbnError(f"pack_conv2d_backward_data_weight: unsupported weight shape {tuple(w.shape)}")
+    return _pack_into(out, nbytes, w, lambda p: lib.kbn_conv2d_backward_data_pack_weight(w.data_ptr(), p, oc, cin, kh, stride, _stream()),
+                      "kbn_conv2d_backward_data_pack_weight")
+
+
+@_on_tensor_device
+def conv2d_backward_data(grad_out: torch.Tensor, packed_weight: torch.Tensor, in_channels: int, kernel_size: int, stride: int,
+                         in_height: int, in_width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of conv_{k x k, stride, padding k // 2}(x) with respect to its one input for (k, stride) in {(3, 1), (1, 1),
+    (1, 2)} (kbn_conv2d_backward_data): grad_out N x F x ceil(H / stride) x ceil(W / stride) -> N x in_channels x H x W, every
+    element written by the one launch (at (1, 2): zeros at the pixels the conv never read).  `packed_weight`:
+    pack_conv2d_backward_data_weight of the F x in_channels x k x k weight at this stride.  `out`: a tensor or channel slice."""
+    lib = _lib.load()
+    _backward_case("conv2d_backward_data", kernel_size, stride)
+    in_channels = int(in_channels)
+    if in_channels < 1 or in_height < 1 or in_width < 1:
+        raise KbnError(f"conv2d_backward_data: empty input {in_channels} x {in_height} x {in_width}")
+    gptr, gbs = _planes(grad_out, "grad_out")
+    n, oc, oh, ow = grad_out.shape
+    if n < 1 or oc < 1 or (oh, ow) != (-(-in_height // stride), -(-in_width // stride)):
+        raise KbnError(f"conv2d_backward_data: grad_out is {tuple(grad_out.shape)}, the conv of a {in_height} x {in_width} input at "
+                       f"stride {stride} has {-(-in_height // stride)} x {-(-in_width // stride)} maps")
+    _require(packed_weight, "packed_weight", 1)
+    want = lib.kbn_conv2d_backward_data_packed_weight_bytes(oc, in_channels, kernel_size, stride) // 4
+    if want == 0 or packed_weight.numel() != want or not packed_weight.is_contiguous():
+        raise KbnError(f"conv2d_backward_data: packed_weight holds {packed_weight.numel()} floats, a {oc} x {in_channels} x "
+                       f"{kernel_size} x {kernel_size} weight packs into {want} at stride {stride}")
+    out = _out_tensor(out, (n, in_channels, in_height, in_width), grad_out.device, planes=True)
+    optr, obs = _planes(out, "out")
+    k2 = kernel_size * kernel_size
+    name = f"conv_affine<{kernel_size},1> (data gradient)" if stride == 1 else "conv1x1s2_bwd_data"
+    check(_launch(name, 2.0 * n * oh * ow * in_channels * k2 * oc,
+                  lambda: lib.kbn_conv2d_backward_data(gptr, gbs, packed_weight.data_ptr(), optr, obs, n, oc, in_channels, kernel_size,
+                                                       stride, in_height, in_width, _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 128) * 128) * (want - 2 * in_channels) if stride == 1 else None,
+                  pipe="fp32" if stride == 1 else None, nbytes=4.0 * n * (oc * oh * ow + in_channels * in_height * in_width)),
+          "kbn_conv2d_backward_data")
+    return out
+
+
+def _conv2d_pose_launch(inputs, weight, stride, packed):
+    oc, _, k, _ = weight.shape
+    if packed is None:
+        packed = pack_conv2d_affine_weight(weight)
+    ones, zeros = _unit_affine(weight.device, oc)
+    return conv2d_affine([t.detach() for t in inputs], packed, ones, zeros, oc, k, stride=stride, negative_slope=None)
+
+
+class _Conv2dPose(torch.autograd.Function):
+    """The bias-free conv of the ResNet pose networks as a differentiable node.  Saved: the weight and the inputs.  Backward by
+    (k, stride): (3, 2) and (7, 2) on conv2d_s2_backward_*, the rest on conv2d_backward_*; a data-gradient launch only when an
+    input asks for its gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, stride, packed, packed_t, *inputs):
+        ctx.save_for_backward(weight, *inputs)
+        ctx.stride, ctx.packed_t = stride, packed_t
+        return _conv2d_pose_launch(inputs, weight, stride, packed)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_u):
+        weight, *inputs = ctx.saved_tensors
+        k, stride = weight.shape[2], ctx.stride
+        need = ctx.needs_input_grad
+        g = grad_u.contiguous()
+        s2 = (k, stride) not in _BACKWARD_CASES
+        grad_w = None
+        if need[0]:
+            grad_w = conv2d_s2_backward_weight(inputs, g, k) if s2 else conv2d_backward_weight(inputs, g, k, stride)
+        grads = [None] * len(inputs)
+        if any(need[4:]):
+            h, w = inputs[0].shape[2:]
+            if s2:
+                packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
+                got = conv2d_s2_backward_data(g, packed_t, [t.shape[1] for t in inputs], k, h, w)
+            else:
+                packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_backward_data_weight(weight, stride)
+                got = [conv2d_backward_data(g, packed_t, inputs[0].shape[1], k, stride, h, w)]
+            grads = [gi if need[4 + i] else None for i, gi in enumerate(got)]
+        return (grad_w, None, None, None) + tuple(grads)
+
+
+@_on_tensor_device
+def conv2d_pose(inputs: Sequence[torch.Tensor], weight: torch.Tensor, stride: int, packed: Optional[torch.Tensor] = None,
+                packed_t=None) -> torch.Tensor:
+    """conv_{k x k, stride, padding k // 2}(cat(inputs, 1)), no bias, k in {1, 3, 7} at stride 1 or 2: conv2d_affine's kernel with
+    unit scale, zero shift and no activation.  Differentiable with respect to the weight and to every input that requires grad
+    (one node, no double backward); a data gradient at (k, stride) outside (3, 2) and (7, 2) takes ONE input.  `packed`: the
+    weight's pack_conv2d_affine_weight blob when the caller caches it; `packed_t`: a callable weight -> the data gradient's blob
+    (pack_conv2d_s2_backward_data_weight at (3, 2) and (7, 2), pack_conv2d_backward_data_weight(weight, stride) elsewhere), asked
+    only when a data gradient is needed."""
+    inputs = list(inputs)
+    w = _weight(weight)
+    if w.shape[2] != w.shape[3]:
+        raise KbnError("square kernels only")
+    k = w.shape[2]
+    if k not in (1, 3, 7) or stride not in (1, 2):
+        raise KbnError(f"conv2d_pose: kernel size 1, 3 or 7 at stride 1 or 2, got {k} at {stride}")
+    _, _, _, _, _, cin = _conv_inputs("conv2d_pose", inputs)
+    if cin != w.shape[1]:
+        raise KbnError(f"conv2d_pose: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
+    if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
+        if (k, stride) not in _BACKWARD_CASES + ((3, 2), (7, 2)):
+            raise KbnError(f"conv2d_pose: no backward pass for kernel size {k} at stride {stride}")
+        if any(t.requires_grad for t in inputs) and len(inputs) > 1 and (k, stride) in _BACKWARD_CASES:
+            raise KbnError(f"conv2d_pose: the data gradient at kernel size {k}, stride {stride} takes one input, got {len(inputs)}")
+        return _Conv2dPose.apply(weight, stride, packed, packed_t, *inputs)
+    return _conv2d_pose_launch(inputs, w, stride, packed)
+
+
+@_on_tensor_device
+def maxpool3x3s2_backward(x: torch.Tensor, grad_out: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of maxpool3x3s2 (kbn_maxpool3x3s2_backward): x N x C x H x W (the pool's input), grad_out N x C x ceil(H / 2) x
+    ceil(W / 2) -> N x C x H x W.  Every window's gradient goes to its FIRST maximum in row-major order (the forward's own scan;
+    ties are the rule behind a relu); a pixel sums the at most four windows that chose it in (oy, ox) order.  One launch, no atomics."""
+    lib = _lib.load()
+    xptr, xbs = _planes(x.detach() if isinstance(x, torch.Tensor) else x, "x")
+    n, c, h, w = x.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"maxpool3x3s2_backward: empty input {tuple(x.shape)}")
+    oh, ow = (h + 1) // 2, (w + 1) // 2
+    gptr, gbs = _planes(grad_out, "grad_out")
+    if tuple(grad_out.shape) != (n, c, oh, ow):
+        raise KbnError(f"maxpool3x3s2_backward: grad_out is {tuple(grad_out.shape)}, the pool of {tuple(x.shape)} is {(n, c, oh, ow)}")
+    out = _out_tensor(out, (n, c, h, w), x.device, planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("maxpool3x3s2_bwd", 0.0,
+                  lambda: lib.kbn_maxpool3x3s2_backward(xptr, xbs, gptr, gbs, optr, obs, n, c, h, w, _stream()),
+                  nbytes=4.0 * n * c * (2 * h * w + oh * ow)), "kbn_maxpool3x3s2_backward")
+    return out
+
+
+class _MaxPool3x3S2(torch.autograd.Function):
+    """maxpool3x3s2 as a differentiable node.  Saved: x -- the backward rescans the windows, no index tensor is kept."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return _maxpool3x3s2_launch(x.detach(), None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (x,) = ctx.saved_tensors
+        return maxpool3x3s2_backward(x, grad_out.contiguous())
+
+
+def _add_act_args(fn: str, a, b, names):
+    for t, name in zip((a, b), names):
+        _require(t, name)
+    if a.shape != b.shape or a.numel() < 1:
+        raise KbnError(f"{fn}: {names[0]} {tuple(a.shape)} and {names[1]} {tuple(b.shape)} must be one non-empty shape")
+    if not a.is_contiguous() or not b.is_contiguous():
+        raise KbnError(f"{fn}: {names[0]} and {names[1]} must be contiguous")
+
+
+def _add_act_launch(a, b, negative_slope):
+    lib = _lib.load()
+    y = torch.empty_like(a)
+    check(_launch("add_act", 0.0, lambda: lib.kbn_add_act_forward(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(),
+                                                                 *_act_args(negative_slope), _stream()),
+                  nbytes=12.0 * a.numel()), "kbn_add_act_forward")
+    return y
+
+
+@_on_tensor_device
+def add_act_backward(y: torch.Tensor, grad_y: torch.Tensor, negative_slope: Optional[float] = 0.2) -> torch.Tensor:
+    """The gradient of add_act with respect to EITHER addend (kbn_add_act_backward): grad_y where y > 0, negative_slope grad_y
+    elsewhere -- y <= 0 takes the slope, so slope 0 puts exact zeros there, as torch.nn.functional.leaky_relu does.
+    `negative_slope` None: grad_y itself, no launch."""
+    _add_act_args("add_act_backward", y, grad_y, ("y", "grad_y"))
+    if negative_slope is None:
+        return grad_y
+    lib = _lib.load()
+    g = torch.empty_like(y)
+    check(_launch("add_act_bwd", 0.0, lambda: lib.kbn_add_act_backward(y.data_ptr(), grad_y.data_ptr(), g.data_ptr(), y.numel(),
+                                                                      *_act_args(negative_slope), _stream()),
+                  nbytes=12.0 * y.numel()), "kbn_add_act_backward")
+    return g
+
+
+class _AddAct(torch.autograd.Function):
+    """act(a + b) as a differentiable node.  Saved: y only (its sign is the sign of a + b for a slope >= 0)."""
+
+    @staticmethod
+    def forward(ctx, a, b, negative_slope):
+        y = _add_act_launch(a.detach(), b.detach(), negative_slope)
+        ctx.save_for_backward(y)
+        ctx.slope = negative_slope
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        (y,) = ctx.saved_tensors
+        g = add_act_backward(y, grad_y.contiguous(), ctx.slope)
+        need = ctx.needs_input_grad
+        return g if need[0] else None, g if need[1] else None, None
+
+
+@_on_tensor_device
+def add_act(a: torch.Tensor, b: torch.Tensor, negative_slope: Optional[float] = 0.2) -> torch.Tensor:
+    """act(a + b) in one launch (kbn_add_act_forward), act = max(v, slope v), `negative_slope` None: the sum alone: the add and
+    second activation that end a ResNetBlock (reference src/net_utils.py:666-667).  Two contiguous fp32 tensors of one shape.
+    Differentiable with respect to both (one node, no double backward)."""
+    _add_act_args("add_act", a, b, ("a", "b"))
+    if negative_slope is not None and negative_slope < 0:
+        raise KbnError(f"add_act: negative_slope must be >= 0 (the backward reads the branch from y's sign), got {negative_slope}")
+    if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+        return _AddAct.apply(a, b, negative_slope)
+    return _add_act_launch(a.detach(), b.detach(), negative_slope)

@@ -119,13 +119,19 @@ class PoseConv2d(torch.nn.Module):
         return ops.conv2d_s2_affine(inputs, self.packed(), scale, shift, self.out_channels, self.kernel_size,
                                     negative_slope=self.slope, out=out)
 
+    def conv_recorded(self, inputs: List[torch.Tensor]):
+        """The bias-free conv alone, as a differentiable node."""
+        return ops.conv2d_s2(inputs, self.conv.weight, packed=self.packed(), packed_t=self.packed_t)
+
     def run_unfused(self, inputs: List[torch.Tensor], batch: bool):
         """The layer as conv, [batch statistics], BatchNorm + activation: what the fused launch of `run` cannot be when the
         backward needs the conv's output or the statistics are the batch's own.  Recorded for autograd when grad mode is on and
         a parameter requires grad.  `batch`: normalise with the statistics of this batch and update the running ones as
         torch.nn.BatchNorm2d does in train mode (src/net_utils.py:103-104); the module's `training` flag stays False."""
-        bn = self.batch_norm
-        u = ops.conv2d_s2(inputs, self.conv.weight, packed=self.packed(), packed_t=self.packed_t)
+        u = self.conv_recorded(inputs)
+        bn = getattr(self, "batch_norm", None)
+        if bn is None:       # (posenet_resnet.ResNetConv2d without batch norm: the projection)
+            return u
         if batch:
             count = u.shape[0] * u.shape[2] * u.shape[3]
             if count <= 1:
@@ -237,19 +243,35 @@ class PoseModelBase(object):
     def parameters(self):
         return list(self.encoder.parameters()) + list(self.decoder.parameters())
 
-    _has_backward = False   # PoseNetModel: True
+    _has_backward = False   # PoseNetModel: True; ResNetPoseNetModel: its `trainable` argument
+    batch_norm_mode = "running"
 
     def requires_grad_(self, flag: bool = True):
         """Sets requires_grad on every parameter (conv weights, BatchNorm weights and biases, the head's weight)."""
         if flag and not self._has_backward:
-            raise KbnError(f"{type(self).__name__}.requires_grad_: only encoder_type='posenet' (PoseNetModel) has a backward pass yet")
+            raise KbnError(f"{type(self).__name__}.requires_grad_: this model was built without a backward pass: encoder_type='posenet' "
+                           "(PoseNetModel) always has one, ResNetPoseNetModel with trainable=True")
         for p in self.parameters():
             p.requires_grad_(bool(flag))
         return self
 
+    def set_batch_norm(self, mode: str = "running"):
+        """'running' (default): BatchNorm2d normalises with its running statistics, constants of the backward pass -- fine-tuning
+        on frozen statistics.  'batch': what the reference's pose_model.train() does (src/kbnet.py:392-453): every layer normalises
+        with the statistics of the batch, the gradient runs through them, and running_mean / running_var / num_batches_tracked are
+        updated as torch.nn.BatchNorm2d updates them (momentum 0.1, unbiased variance), with gradients on or off.  A layer whose
+        map holds one value per channel raises."""
+        if not self._has_backward:
+            raise KbnError(f"{type(self).__name__}.set_batch_norm: this model has no backward pass (ResNetPoseNetModel: build it with "
+                           "trainable=True)")
+        if mode not in ("running", "batch"):
+            raise KbnError(f"{type(self).__name__}.set_batch_norm: 'running' or 'batch', got {mode!r}")
+        self.batch_norm_mode = mode
+        return self
+
     def train(self):
-        raise KbnError("the HIP path is inference only through train() / eval(): the modules stay in eval mode.  PoseNetModel "
-                       "trains through requires_grad_(True) and set_batch_norm('batch')")
+        raise KbnError("the HIP path is inference only through train() / eval(): the modules stay in eval mode.  PoseNetModel and "
+                       "ResNetPoseNetModel(trainable=True) train through requires_grad_(True) and set_batch_norm('batch')")
 
     def eval(self):
         for m in self.modules():
@@ -308,17 +330,6 @@ class PoseNetModel(PoseModelBase):
         self._place(device)
 
     _has_backward = True
-
-    def set_batch_norm(self, mode: str = "running"):
-        """'running' (default): BatchNorm2d normalises with its running statistics, constants of the backward pass -- fine-tuning
-        on frozen statistics.  'batch': what the reference's pose_model.train() does (src/kbnet.py:392-453): every layer normalises
-        with the statistics of the batch, the gradient runs through them, and running_mean / running_var / num_batches_tracked are
-        updated as torch.nn.BatchNorm2d updates them (momentum 0.1, unbiased variance), with gradients on or off.  A layer whose
-        map holds one value per channel raises."""
-        if mode not in ("running", "batch"):
-            raise KbnError(f"PoseNetModel.set_batch_norm: 'running' or 'batch', got {mode!r}")
-        self.batch_norm_mode = mode
-        return self
 
     def forward(self, image0, image1, return_all: bool = False):
         """`return_all` (extension): (pose, dof N x 6, the seven layer outputs) instead of the pose alone.

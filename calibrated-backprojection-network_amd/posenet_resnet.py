@@ -9,7 +9,11 @@ forward, on the HIP kernels of csrc/conv_affine.hip and the head of csrc/posenet
 
 Same constructor arguments and `state_dict()` keys as the reference, so `posenet-kitti.pth`, `posenet-void1500.pth` and every
 `pose_model-*.pth` its training writes load with strict=True; `load_pose_model(path)` picks the class from the checkpoint's keys.
-Inference only: BatchNorm2d uses its running statistics, there is no autograd and no CPU path.
+By default inference: BatchNorm2d uses its running statistics, nothing is recorded; no CPU path.
+
+Training (reference src/kbnet.py:392-453) is an opt-in at construction, ResNetPoseNetModel(..., trainable=True): requires_grad_(True)
+and set_batch_norm('batch') then work as on PoseNetModel and the forward runs layer by layer on the kernels of
+csrc/posenet_backward.hip and csrc/conv_affine_backward.hip, recording autograd; `train()` still raises.
 
 Launches per forward: conv1, the pool, per block conv1 and conv2 (conv2's epilogue adds the skip and applies the second
 activation) plus a 1 x 1 projection launch in the four blocks whose input changes shape, two decoder convs and the head:
@@ -24,7 +28,7 @@ import torch
 
 from . import ops
 from ._lib import KbnError
-from .posenet import PoseConv2d, PoseModelBase, PoseNetModel, _DecoderConv, _fused_slope
+from .posenet import PoseConv2d, PoseModelBase, PoseNetModel, _DecoderConv, _fused_slope, _state
 
 RESNET_BLOCKS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
 RESNET_FILTERS = (16, 32, 64, 128, 256)
@@ -51,6 +55,23 @@ class ResNetConv2d(PoseConv2d):
             self._scale = torch.ones(self.out_channels, device=w.device)
             self._shift = torch.zeros(self.out_channels, device=w.device)
         return self._scale, self._shift
+
+    def packed_t(self, weight=None):
+        """The weight as the data gradient of this (k, stride) reads it, re-packed when the weight changed: PoseConv2d.packed_t's
+        blob at (3, 2) and (7, 2), ops.pack_conv2d_backward_data_weight's elsewhere."""
+        if self.stride == 2 and self.kernel_size != 1:
+            return super().packed_t(weight)
+        weight = self.conv.weight if weight is None else weight
+        key = _state(weight)
+        if key != self._tkey:
+            self._tblob = ops.pack_conv2d_backward_data_weight(weight, self.stride, out=self._tblob)
+            self._tkey = key
+        return self._tblob
+
+    def conv_recorded(self, inputs: List[torch.Tensor]):
+        """`run_unfused` (PoseConv2d's: conv, [batch statistics], BatchNorm + activation; the conv alone without batch norm)
+        starts from this conv."""
+        return ops.conv2d_pose(inputs, self.conv.weight, self.stride, packed=self.packed(), packed_t=self.packed_t)
 
     @torch.no_grad()
     def run(self, inputs: List[torch.Tensor], residual: Optional[torch.Tensor] = None, out=None):
@@ -86,6 +107,17 @@ class ResNetBlock(torch.nn.Module):
         h = self.conv1.run([x])
         skip = self.projection.run([x]) if self.projects(x) else x
         return self.conv2.run([h], residual=skip, out=out)
+
+    def run_unfused(self, x, batch: bool, inner: Optional[dict] = None, name: str = ""):
+        """`run` layer by layer (reference src/net_utils.py:643-667), recordable: conv1 and conv2 as conv, [batch statistics],
+        BatchNorm + activation, the projection's conv where the block projects, then ops.add_act.  An identity skip never touches
+        `projection`.  `inner`: a dict that receives the outputs of conv1 and conv2 under `name`.conv1 / `name`.conv2."""
+        h = self.conv1.run_unfused([x], batch)
+        a = self.conv2.run_unfused([h], batch)
+        skip = self.projection.run_unfused([x], batch) if self.projects(x) else x
+        if inner is not None:
+            inner[name + ".conv1"], inner[name + ".conv2"] = h, a
+        return ops.add_act(a, skip, self.conv2.slope)
 
     def forward(self, x):
         return self.run(x)
@@ -132,6 +164,16 @@ class ResNetEncoder(torch.nn.Module):
         for block in self.blocks():
             outs.append(block.run(outs[-1]))
         return outs if return_layers else outs[-1]
+
+    def encode_unfused(self, inputs: List[torch.Tensor], batch: bool = False, inner: Optional[dict] = None):
+        """`encode(..., return_layers=True)` layer by layer, recordable.  conv1 reads the images, which are data: its node
+        launches no data gradient.  The pool is recorded when its input carries a gradient."""
+        outs = [self.conv1.run_unfused(list(inputs), batch)]
+        outs.append(ops.maxpool3x3s2(outs[-1]))
+        for name in self.stages:
+            for b, block in enumerate(getattr(self, name)):
+                outs.append(block.run_unfused(outs[-1], batch, inner, f"{name}.{b}"))
+        return outs
 
     def forward(self, x):
         outs = self.encode([x], return_layers=True)
@@ -186,7 +228,7 @@ class ResNetPoseNetModel(PoseModelBase):
 
     def __init__(self, n_layer=18, rotation_parameterization="axis", weight_initializer="xavier_normal",
                  activation_func="leaky_relu", device=torch.device("cuda"), n_filters=RESNET_FILTERS,
-                 decoder_filters=RESNET_DECODER_FILTERS):
+                 decoder_filters=RESNET_DECODER_FILTERS, trainable: bool = False):
         self.device = device
         self.n_layer = n_layer
         self.encoder = ResNetEncoder(n_layer, input_channels=6, n_filters=list(n_filters), weight_initializer=weight_initializer,
@@ -195,17 +237,51 @@ class ResNetPoseNetModel(PoseModelBase):
                                          n_filters=list(decoder_filters), weight_initializer=weight_initializer,
                                          activation_func=activation_func, use_batch_norm=True)
         self.encoder_type = f"resnet{n_layer}"
+        self._has_backward = bool(trainable)     # requires_grad_(True) and set_batch_norm refuse without it
+        self.batch_norm_mode = "running"
         self._place(device)
 
-    @torch.no_grad()
-    def forward(self, image0, image1, return_all: bool = False):
-        """`return_all` (extension): (pose, dof N x 6, layer outputs: conv1, the pool, every block, the decoder's hidden layers)."""
+    def forward(self, image0, image1, return_all: bool = False, return_inner: bool = False):
+        """`return_all` (extension): (pose, dof N x 6, layer outputs: conv1, the pool, every block, the decoder's hidden layers).
+
+        Built with trainable=True, with grad mode on and a parameter that requires grad the pose carries a grad_fn: the network
+        runs layer by layer (ResNetBlock.run_unfused, the kernels of csrc/posenet_backward.hip and csrc/conv_affine_backward.hip),
+        the head in recorded torch operations; so it does under set_batch_norm('batch'), recorded or not.  Otherwise this is the
+        fused eval-mode forward, nothing recorded.  `return_inner` (layer-by-layer path only): a fourth element, the dict
+        blocks{s}.{b}.conv1 / .conv2 -> the outputs of every block's two convs (conv2's before the skip is added)."""
         if not isinstance(image0, torch.Tensor) or not isinstance(image1, torch.Tensor) or image0.dim() != 4 or \
                 image0.shape[1] != 3 or image0.shape != image1.shape:
             raise KbnError("ResNetPoseNetModel.forward: image0 and image1 must be N x 3 x H x W tensors of one shape")
-        layers = self.encoder.encode([image0, image1], return_layers=True)
-        (pose, dof), hidden = self.decoder(layers[-1], return_dof=True, return_layers=True)
-        return (pose, dof, layers + hidden) if return_all else pose
+        record = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        batch = self.batch_norm_mode == "batch"
+        if not record and not batch:
+            if return_inner:
+                raise KbnError("ResNetPoseNetModel.forward: return_inner exists on the layer-by-layer path only (a recorded forward or "
+                               "set_batch_norm('batch')): the fused forward never materialises a block's inner activations")
+            with torch.no_grad():
+                layers = self.encoder.encode([image0, image1], return_layers=True)
+                (pose, dof), hidden = self.decoder(layers[-1], return_dof=True, return_layers=True)
+            return (pose, dof, layers + hidden) if return_all else pose
+        if record:
+            for t, name in ((image0, "image0"), (image1, "image1")):
+                if t.requires_grad:
+                    raise KbnError(f"ResNetPoseNetModel.forward: {name} requires grad, but it is data and gets no gradient (gradients "
+                                   "exist for the parameters); detach it")
+        inner = {}
+        with torch.set_grad_enabled(record):
+            layers = self.encoder.encode_unfused([image0, image1], batch, inner)
+            x = layers[-1]
+            for layer in self.decoder.hidden():
+                x = layer.run_unfused([x], batch)
+                layers.append(x)
+            weight = self.decoder.conv[-1].conv.weight
+            if record:
+                pose, dof = ops.pose_head_recorded(x, weight)
+            else:
+                pose, dof = ops.pose_head(x, weight, return_dof=True)
+        if return_inner:
+            return pose, dof, layers, inner
+        return (pose, dof, layers) if return_all else pose
 
 
 def _strip(sd):
@@ -237,10 +313,11 @@ def _pose_layout(enc, dec):
     return None
 
 
-def load_pose_model(checkpoint_path, device=torch.device("cuda"), activation_func="leaky_relu"):
+def load_pose_model(checkpoint_path, device=torch.device("cuda"), activation_func="leaky_relu", trainable: bool = False):
     """The restored pose model of a reference checkpoint (src/posenet_model.py:150-198), of the class its keys call for: a
     PoseNetModel for the seven-conv encoder, a ResNetPoseNetModel for ResNet-18 / 34 (told apart by the block counts of blocks2 ..
-    blocks5); the widths come from the weight shapes.  A checkpoint does not record the activation: `activation_func`."""
+    blocks5); the widths come from the weight shapes.  A checkpoint does not record the activation: `activation_func`.
+    `trainable`: ResNetPoseNetModel's argument (PoseNetModel always has its backward pass)."""
     ckpt = torch.load(checkpoint_path, map_location=device)
     if not isinstance(ckpt, dict) or "encoder_state_dict" not in ckpt or "decoder_state_dict" not in ckpt:
         raise KbnError(f"load_pose_model: {checkpoint_path} is no pose checkpoint (encoder_state_dict / decoder_state_dict); it holds "
@@ -255,6 +332,6 @@ def load_pose_model(checkpoint_path, device=torch.device("cuda"), activation_fun
         model = PoseNetModel(device=device, activation_func=activation_func, n_filters=filters)
     else:
         model = ResNetPoseNetModel(int(kind[6:]), device=device, activation_func=activation_func, n_filters=filters,
-                                   decoder_filters=decoder_filters)
+                                   decoder_filters=decoder_filters, trainable=trainable)
     model.load_state_dicts(enc, dec)
     return model

@@ -709,6 +709,44 @@ int kbn_conv2d_affine_forward(const kbn_conv_src* srcs, int n_src, const float* 
 int kbn_maxpool3x3s2_forward(const float* in, long long in_batch_stride, float* out, long long out_batch_stride, int n,
                              int channels, int height, int width, kbn_stream_t stream);
 
+/* ------------------------------------------------- ResNet pose networks (training: the backward of their layers) ----
+ * What the layers above need beside the stride-2 gradients and the BatchNorm2d entries of the section before them.  fp32 in and
+ * out, no floating-point atomics: a call's bits are a function of its arguments alone.  (kernel_size, stride) is one of (3, 1),
+ * (1, 1), (1, 2), padding kernel_size / 2, OH = ceil(in_h / stride), OW = ceil(in_w / stride); anything else KBN_ERR_UNSUPPORTED.
+ *
+ * kbn_conv2d_backward_weight: grad_weight[o, c, ky, kx] = sum_n,oy,ox grad_out[n, o, oy, ox] in[n, c, s oy + ky - k/2, s ox + kx - k/2]
+ *   with the sources, the split, the scratch planes and the fixed-order sum of kbn_conv2d_s2_backward_weight.
+ * kbn_conv2d_backward_data: grad_in[n, c, iy, ix] = sum_o,ky,kx W[o, c, ky, kx] grad_out[n, o, (iy + k/2 - ky) / s, (ix + k/2 - kx) / s]
+ *   over the taps that land on an output pixel; EVERY element of grad_in (N x in_channels x in_h x in_w, one tensor) is written.
+ *   At stride 1 this is kbn_conv2d_affine_forward over grad_out with the weight transposed and its taps flipped -- what
+ *   kbn_conv2d_backward_data_pack_weight writes, with the unit scale and zero shift behind it; at (1, 2) one launch of its own
+ *   writes W^T grad_out to the even-even pixels and zeros to the rest (the blob is the weight itself). */
+size_t kbn_conv2d_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size, int stride, int in_height,
+                                                int in_width, int splits);
+int kbn_conv2d_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out, long long grad_out_batch_stride,
+                               float* grad_weight, int n, int out_channels, int kernel_size, int stride, int in_height,
+                               int in_width, int splits, float* scratch, size_t scratch_bytes, kbn_stream_t stream);
+size_t kbn_conv2d_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size, int stride);
+int kbn_conv2d_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels, int kernel_size,
+                                         int stride, kbn_stream_t stream);
+int kbn_conv2d_backward_data(const float* grad_out, long long grad_out_batch_stride, const float* packed_weight, float* grad_in,
+                             long long grad_in_batch_stride, int n, int out_channels, int in_channels, int kernel_size, int stride,
+                             int in_height, int in_width, kbn_stream_t stream);
+
+/* The gradient of kbn_maxpool3x3s2_forward: grad_in[n, c, iy, ix] = the sum of grad_out over the windows whose FIRST maximum (the
+ * forward's scan: row-major, v > m or v is NaN) is this pixel, the at most four windows taken in (oy, ox) order.  x: the forward's input. */
+int kbn_maxpool3x3s2_backward(const float* x, long long x_batch_stride, const float* grad_out, long long grad_out_batch_stride,
+                              float* grad_in, long long grad_in_batch_stride, int n, int channels, int height, int width,
+                              kbn_stream_t stream);
+
+/* The add that ends a ResNetBlock (src/net_utils.py:666-667) over `count` contiguous floats: y = act(a + b), act = max(v, slope v)
+ * when apply_activation.  Backward: grad = grad_y where y > 0, negative_slope grad_y elsewhere (y <= 0 takes the slope, as torch's
+ * leaky_relu at 0) -- the gradient of both addends; without activation a copy. */
+int kbn_add_act_forward(const float* a, const float* b, float* y, long long count, int apply_activation, float negative_slope,
+                        kbn_stream_t stream);
+int kbn_add_act_backward(const float* y, const float* grad_y, float* grad, long long count, int apply_activation,
+                         float negative_slope, kbn_stream_t stream);
+
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:
  *   data_utils.load_image   Image.open(path).convert('RGB') -> float32   reference src/data_utils.py:58-85

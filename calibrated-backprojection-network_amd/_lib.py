@@ -124,6 +124,10 @@ SIGNATURES = {
     "kbn_maxpool3x3s2_backward": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _P]),
     "kbn_add_act_forward": (_I, [_P, _P, _P, _L, _I, _F, _P]),
     "kbn_add_act_backward": (_I, [_P, _P, _P, _L, _I, _F, _P]),
+    "kbn_resize_nearest_forward": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "kbn_resize_nearest_backward": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
+    "kbn_kb_xyz_backward": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
+    "kbn_depth_map_backward": (_I, [_P, _P, _P, _P, _L, _F, _P]),
     "kbn_depth_head_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     "kbn_conv_head_forward": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
     "kbn_conv_tail_packed_weight_bytes": (C.c_size_t, [_I]),

@@ -3,7 +3,8 @@
 Same class names, constructor arguments, `forward()` signatures and `state_dict()`
 keys as the reference (so its checkpoints load and `kbnet_model.py` can use these as
 drop-ins), but every `forward` is a sequence of HIP launches through the C ABI
-(ops.py).  Inference only: there is no autograd and no CPU path.
+(ops.py).  Inference by default: nothing is recorded for autograd (KBNetModel(trainable=True) is the opt-in, kbnet_train.py) and there
+is no CPU path.
 
   reference class                              here
   net_utils.Conv2d            src/net_utils.py:51-141      Conv2d
@@ -1331,7 +1332,12 @@ class KBNetModel(object):
                  n_filter_sparse_to_dense_pool, n_filters_encoder_image, n_filters_encoder_depth,
                  resolutions_backprojection, n_filters_decoder, deconv_type="up",
                  weight_initializer="xavier_normal", activation_func="leaky_relu",
-                 min_predict_depth=1.5, max_predict_depth=100.0, device=torch.device("cuda")):
+                 min_predict_depth=1.5, max_predict_depth=100.0, device=torch.device("cuda"), trainable: bool = False):
+        # `trainable` (extension): the model gets its backward pass -- with grad mode on and a parameter that requires grad, forward
+        # runs layer by layer and records autograd (kbnet_train.py); what that path does not differentiate is refused here
+        self._has_backward = bool(trainable)
+        if trainable:
+            kbnet_train.check(deconv_type, activation_func)
         self.min_predict_depth = min_predict_depth
         self.max_predict_depth = max_predict_depth
         self.device = device
@@ -1355,19 +1361,34 @@ class KBNetModel(object):
         self.eval()
 
     @classmethod
-    def from_config(cls, cfg: KBNetConfig, device=torch.device("cuda")):
+    def from_config(cls, cfg: KBNetConfig, device=torch.device("cuda"), trainable: bool = False):
         return cls(cfg.input_channels_image, cfg.input_channels_depth,
                    list(cfg.min_pool_sizes_sparse_to_dense_pool), list(cfg.max_pool_sizes_sparse_to_dense_pool),
                    cfg.n_convolution_sparse_to_dense_pool, cfg.n_filter_sparse_to_dense_pool,
                    list(cfg.n_filters_encoder_image), list(cfg.n_filters_encoder_depth),
                    list(cfg.resolutions_backprojection), list(cfg.n_filters_decoder), cfg.deconv_type,
                    cfg.weight_initializer, cfg.activation_func, cfg.min_predict_depth, cfg.max_predict_depth,
-                   device)
+                   device, trainable)
 
     # -- forward ---------------------------------------------------------------
+    def forward(self, image, sparse_depth, validity_map_depth, intrinsics, return_logits=False, out=None, return_inner=False):
+        """`out` (extension): write the N x 1 x H x W depth map into this tensor instead of a new one.
+
+        Built with trainable=True, with grad mode on and a parameter that requires grad the depth carries a grad_fn: the network
+        runs layer by layer and records autograd (kbnet_train.forward_recorded); `out` and `return_logits` are refused there and
+        `return_inner` adds the dict name -> activation of every layer.  Otherwise this is the fused forward, nothing recorded."""
+        if self._has_backward and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if out is not None or return_logits:
+                raise KbnError("KBNetModel.forward: out= and return_logits exist on the fused forward only; this call is recorded for "
+                               "autograd (run it under torch.no_grad(), or requires_grad_(False))")
+            return kbnet_train.forward_recorded(self, image, sparse_depth, validity_map_depth, intrinsics, return_inner=return_inner)
+        if return_inner:
+            raise KbnError("KBNetModel.forward: return_inner exists on the recorded path only (trainable=True, grad mode on, a parameter "
+                           "that requires grad): the fused forward never materialises most activations")
+        return self._forward_fused(image, sparse_depth, validity_map_depth, intrinsics, return_logits, out)
+
     @torch.no_grad()
-    def forward(self, image, sparse_depth, validity_map_depth, intrinsics, return_logits=False, out=None):
-        """`out` (extension): write the N x 1 x H x W depth map into this tensor instead of a new one."""
+    def _forward_fused(self, image, sparse_depth, validity_map_depth, intrinsics, return_logits=False, out=None):
         if out is not None and return_logits:
             raise KbnError("out= and return_logits are mutually exclusive")
         input_depth = paired_planes(sparse_depth, validity_map_depth)   # the two planes of one N x 2 x H x W buffer: no copy
@@ -1429,6 +1450,14 @@ class KBNetModel(object):
 
     def parameters(self):
         return [p for m in self.modules() for p in m.parameters()]
+
+    def requires_grad_(self, flag: bool = True):
+        """Sets requires_grad on every parameter; True needs a model built with trainable=True."""
+        if flag and not self._has_backward:
+            raise KbnError("KBNetModel.requires_grad_: this model was built without a backward pass (trainable=True builds one)")
+        for p in self.parameters():
+            p.requires_grad_(bool(flag))
+        return self
 
     def train(self):
         raise KbnError("the HIP path is inference only")
@@ -1500,6 +1529,7 @@ class KBNetModel(object):
                     "decoder_state_dict": pref(self.decoder.state_dict())}, checkpoint_path)
 
 
+from . import kbnet_train  # noqa: E402  (kbnet_train.py: the recorded forward of KBNetModel(trainable=True))
 from .posenet import PoseDecoder, PoseEncoder, PoseNetModel  # noqa: E402,F401  (posenet.py: the pose network beside KBNetModel)
 from .posenet_resnet import (ResNetBlock, ResNetEncoder, ResNetPoseDecoder, ResNetPoseNetModel,  # noqa: E402,F401  (posenet_resnet.py:
                              load_pose_model)                                                      # the ResNet-18 / 34 pose networks)

@@ -2181,3 +2181,289 @@ def add_act(a: torch.Tensor, b: torch.Tensor, negative_slope: Optional[float] = 
     if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
         return _AddAct.apply(a, b, negative_slope)
     return _add_act_launch(a.detach(), b.detach(), negative_slope)
+
+
+# ------------------------------------------------------------------ depth network (training: csrc/kbnet_backward.hip)
+def _resize_args(fn: str, t: torch.Tensor, name: str, small, large):
+    ptr, bs = _planes(t, name)
+    (h, w), (H, W) = small, large
+    if min(t.shape) < 1 or h < 1 or w < 1:
+        raise KbnError(f"{fn}: empty {name} {tuple(t.shape)}")
+    if H < h or W < w:
+        raise KbnError(f"{fn}: the resized map {H} x {W} must be at least the source's {h} x {w}")
+    return ptr, bs
+
+
+@_on_tensor_device
+def resize_nearest_forward(x: torch.Tensor, height: int, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torch.nn.functional.interpolate(x, size=(height, width), mode='nearest') for height >= H, width >= W
+    (kbn_resize_nearest_forward): the index rule the forward convs resize by, as a tensor of its own.  x: N x C x H x W dense planes."""
+    lib = _lib.load()
+    n, c, h, w = x.shape if isinstance(x, torch.Tensor) and x.dim() == 4 else (0, 0, 0, 0)
+    height, width = int(height), int(width)
+    xptr, xbs = _resize_args("resize_nearest_forward", x, "x", (h, w), (height, width))
+    out = _out_tensor(out, (n, c, height, width), x.device, "resize_nearest_forward: out", planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("resize_nearest", 0.0, lambda: lib.kbn_resize_nearest_forward(xptr, xbs, optr, obs, n, c, h, w, height, width, _stream()),
+                  nbytes=4.0 * n * c * (h * w + height * width)), "kbn_resize_nearest_forward")
+    return out
+
+
+@_on_tensor_device
+def resize_nearest_backward(grad_out: torch.Tensor, height: int, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of resize_nearest_forward (kbn_resize_nearest_backward): grad_out N x C x H' x W' -> N x C x height x width, the
+    SOURCE size.  A gather: every source pixel sums, in row-major order, the destination pixels the index rule maps to it."""
+    lib = _lib.load()
+    n, c, H, W = grad_out.shape if isinstance(grad_out, torch.Tensor) and grad_out.dim() == 4 else (0, 0, 0, 0)
+    height, width = int(height), int(width)
+    gptr, gbs = _resize_args("resize_nearest_backward", grad_out, "grad_out", (height, width), (H, W))
+    out = _out_tensor(out, (n, c, height, width), grad_out.device, "resize_nearest_backward: out", planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("resize_nearest_bwd", 0.0,
+                  lambda: lib.kbn_resize_nearest_backward(gptr, gbs, optr, obs, n, c, height, width, H, W, _stream()),
+                  nbytes=4.0 * n * c * (height * width + H * W)), "kbn_resize_nearest_backward")
+    return out
+
+
+class _ResizeNearest(torch.autograd.Function):
+    """The nearest resize as a differentiable node; nothing is saved but the source size."""
+
+    @staticmethod
+    def forward(ctx, x, height, width):
+        ctx.size = tuple(x.shape[2:])
+        return resize_nearest_forward(x.detach(), height, width)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        return resize_nearest_backward(grad_out.contiguous(), *ctx.size), None, None
+
+
+@_on_tensor_device
+def resize_nearest(x: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """resize_nearest_forward, differentiable with respect to x when grad mode is on and x requires grad (one node)."""
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        _planes(x, "x")
+        return _ResizeNearest.apply(x, int(height), int(width))
+    return resize_nearest_forward(x, height, width)
+
+
+@_on_tensor_device
+def kb_xyz_backward(z: torch.Tensor, coordinates: torch.Tensor, grad_xyz: torch.Tensor, negative_slope: Optional[float] = 0.2,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of xyz = coordinates * z, z = act(pre), with respect to `pre` (kbn_kb_xyz_backward): act'(z) sum_c coordinates_c
+    grad_xyz_c, the branch read from z (z <= 0 takes the slope; `negative_slope` None: no activation).  z N x 1 x H x W; coordinates
+    and grad_xyz N x 3 x H x W, either may be a channel slice."""
+    lib = _lib.load()
+    zptr, zbs = _planes(z, "z")
+    n, _, h, w = z.shape
+    if n < 1 or h < 1 or w < 1 or z.shape[1] != 1:
+        raise KbnError(f"kb_xyz_backward: z must be a non-empty N x 1 x H x W tensor, got {tuple(z.shape)}")
+    cptr, cbs = _planes(coordinates, "coordinates")
+    gptr, gbs = _planes(grad_xyz, "grad_xyz")
+    for t, name in ((coordinates, "coordinates"), (grad_xyz, "grad_xyz")):
+        if tuple(t.shape) != (n, 3, h, w):
+            raise KbnError(f"kb_xyz_backward: {name} is {tuple(t.shape)}, expected {(n, 3, h, w)}")
+    out = _out_tensor(out, (n, 1, h, w), z.device, "kb_xyz_backward: out", planes=True)
+    optr, obs = _planes(out, "out")
+    check(_launch("kb_xyz_bwd", 0.0, lambda: lib.kbn_kb_xyz_backward(zptr, zbs, cptr, cbs, gptr, gbs, optr, obs, n, h, w,
+                                                                     *_act_args(negative_slope), _stream()),
+                  nbytes=4.0 * n * h * w * 8), "kbn_kb_xyz_backward")
+    return out
+
+
+@_on_tensor_device
+def depth_map_backward(logits: torch.Tensor, depth: torch.Tensor, grad_depth: torch.Tensor, min_predict_depth: float,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gradient of depth = d_min / (sigmoid(logits) + d_min / d_max) with respect to the logits (kbn_depth_map_backward):
+    -grad_depth depth^2 / d_min * s (1 - s).  Three contiguous fp32 tensors of one shape: what depth_head(return_logits=True) gave
+    and the incoming gradient.  `out`: a contiguous tensor of that shape to write into."""
+    for t, name in ((logits, "logits"), (depth, "depth"), (grad_depth, "grad_depth")):
+        _require(t, name)
+        if t.shape != logits.shape or not t.is_contiguous() or t.numel() < 1:
+            raise KbnError(f"depth_map_backward: {name} must be contiguous, non-empty and of one shape with logits, got {tuple(t.shape)}")
+    if not min_predict_depth > 0:
+        raise KbnError(f"depth_map_backward: min_predict_depth must be positive, got {min_predict_depth}")
+    lib = _lib.load()
+    g = _out_tensor(out, tuple(logits.shape), logits.device, "depth_map_backward: out")
+    check(_launch("depth_map_bwd", 0.0, lambda: lib.kbn_depth_map_backward(logits.data_ptr(), depth.data_ptr(), grad_depth.data_ptr(),
+                                                                          g.data_ptr(), logits.numel(), float(min_predict_depth), _stream()),
+                  nbytes=16.0 * logits.numel()), "kbn_depth_map_backward")
+    return g
+
+
+_KBNET_CASES = ((3, 1), (3, 2), (1, 1), (1, 2))
+
+
+def _kbnet_weight_gradient(inputs, g, k, stride):
+    """The weight gradient of a conv over one to three concatenated inputs through the entry points that take two: it is linear in
+    the input-channel blocks, so a third input is a second call and the results are joined along dim 1."""
+    fn = (lambda ins: conv2d_s2_backward_weight(ins, g, k)) if (k, stride) == (3, 2) else (lambda ins: conv2d_backward_weight(ins, g, k, stride))
+    if len(inputs) <= 2:
+        return fn(inputs)
+    return torch.cat([fn(inputs[:2]), fn(inputs[2:])], dim=1)
+
+
+def _kbnet_data_gradient(g, weight, k, stride, cin, h, w, packed_t):
+    """One launch over all `cin` channels into one buffer (the caller slices it by input)."""
+    if (k, stride) == (3, 2):
+        blob = packed_t(weight) if packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
+        return conv2d_s2_backward_data(g, blob, [cin], k, h, w)[0]
+    blob = packed_t(weight) if packed_t is not None else pack_conv2d_backward_data_weight(weight, stride)
+    return conv2d_backward_data(g, blob, cin, k, stride, h, w)
+
+
+def _kbnet_conv_launch(inputs, weight, stride, negative_slope, packed):
+    oc, _, k, _ = weight.shape
+    if packed is None:
+        packed = pack_conv_weight(weight, stride)
+    n, _, h, w = inputs[0].shape
+    out = torch.empty((n, oc, -(-h // stride), -(-w // stride)), device=weight.device, dtype=torch.float32)
+    return conv2d([tensor_src(t.detach(), f"inputs[{i}]") for i, t in enumerate(inputs)], packed, n, oc, k, stride, h, w, out,
+                  negative_slope=negative_slope)
+
+
+class _Conv2dKbnet(torch.autograd.Function):
+    """act(conv(cat(inputs))) of the depth network as a differentiable node.  Saved: the output y (the activation's branch is its
+    sign), the inputs and the weight.  Backward: add_act_backward, the weight gradient through the two-input entry points, and --
+    only when an input asks -- ONE data-gradient launch over all channels, returned as channel slices of its buffer."""
+
+    @staticmethod
+    def forward(ctx, weight, stride, negative_slope, packed, packed_t, *inputs):
+        y = _kbnet_conv_launch(inputs, weight.detach(), stride, negative_slope, packed)
+        ctx.save_for_backward(weight, y, *inputs)
+        ctx.args = (stride, negative_slope, packed_t)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        weight, y, *inputs = ctx.saved_tensors
+        stride, slope, packed_t = ctx.args
+        k = weight.shape[2]
+        need = ctx.needs_input_grad
+        g = add_act_backward(y, grad_y.contiguous(), slope)
+        grad_w = _kbnet_weight_gradient(inputs, g, k, stride) if need[0] else None
+        grads = [None] * len(inputs)
+        if any(need[5:]):
+            h, w = inputs[0].shape[2:]
+            buf = _kbnet_data_gradient(g, weight, k, stride, weight.shape[1], h, w, packed_t)
+            at = 0
+            for i, t in enumerate(inputs):
+                if need[5 + i]:
+                    grads[i] = buf[:, at:at + t.shape[1]]
+                at += t.shape[1]
+        return (grad_w, None, None, None, None) + tuple(grads)
+
+
+@_on_tensor_device
+def conv2d_kbnet(inputs: Sequence[torch.Tensor], weight: torch.Tensor, stride: int, negative_slope: Optional[float] = 0.2,
+                 packed: Optional[torch.Tensor] = None, packed_t=None) -> torch.Tensor:
+    """act(conv_{k x k, stride, padding k // 2}(cat(inputs, 1))), no bias, act = max(v, slope v) in the conv's epilogue
+    (`negative_slope` None: none), for (k, stride) in {(3, 1), (3, 2), (1, 1), (1, 2)} and one to three inputs read in place
+    (kbn_conv2d_forward): a conv of the depth network.  Differentiable with respect to the weight and to every input that requires
+    grad -- any of the inputs may be data -- as one node, no double backward.  `packed`: the weight's pack_conv_weight blob when the
+    caller caches it; `packed_t`: a callable weight -> the data gradient's blob (pack_conv2d_s2_backward_data_weight at (3, 2),
+    pack_conv2d_backward_data_weight(weight, stride) elsewhere), asked only when a data gradient is needed."""
+    inputs = list(inputs)
+    w = _weight(weight)
+    if w.shape[2] != w.shape[3]:
+        raise KbnError("square kernels only")
+    k = w.shape[2]
+    if (k, stride) not in _KBNET_CASES:
+        raise KbnError(f"conv2d_kbnet: (kernel size, stride) one of {_KBNET_CASES}, got ({k}, {stride})")
+    if not 1 <= len(inputs) <= 3:
+        raise KbnError(f"conv2d_kbnet: one to three inputs, got {len(inputs)}")
+    if negative_slope is not None and negative_slope < 0:
+        raise KbnError(f"conv2d_kbnet: negative_slope must be >= 0 (the backward reads the branch from y's sign), got {negative_slope}")
+    for i, t in enumerate(inputs):
+        _planes(t, f"inputs[{i}]")
+        if t.shape[0] != inputs[0].shape[0] or t.shape[2:] != inputs[0].shape[2:] or min(t.shape) < 1:
+            raise KbnError(f"conv2d_kbnet: inputs[{i}] is {tuple(t.shape)} beside inputs[0] {tuple(inputs[0].shape)}")
+    cin = sum(t.shape[1] for t in inputs)
+    if cin != w.shape[1]:
+        raise KbnError(f"conv2d_kbnet: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
+    if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
+        return _Conv2dKbnet.apply(weight, stride, negative_slope, packed, packed_t, *inputs)
+    return _kbnet_conv_launch(inputs, w, stride, negative_slope, packed)
+
+
+class _KbXyz(torch.autograd.Function):
+    """xyz = coordinates * act(proj_depth(depth)) of a KB layer as a differentiable node.  Saved: depth, the weight, z and the
+    coordinates the forward multiplied by.  Backward: kb_xyz_backward gives the pre-activation's gradient, then the 1 x 1 conv's two
+    gradients."""
+
+    @staticmethod
+    def forward(ctx, depth, weight, coordinates, negative_slope, packed, packed_t):
+        z = _kbnet_conv_launch([depth], weight.detach(), 1, negative_slope, packed)
+        ctx.save_for_backward(depth, weight, z, coordinates)
+        ctx.args = (negative_slope, packed_t)
+        ctx.mark_non_differentiable(z)
+        return scale_planes(coordinates, z), z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_xyz, _):
+        depth, weight, z, coordinates = ctx.saved_tensors
+        slope, packed_t = ctx.args
+        need = ctx.needs_input_grad
+        g = kb_xyz_backward(z, coordinates, grad_xyz, slope)
+        grad_w = conv2d_backward_weight([depth], g, 1, 1) if need[1] else None
+        grad_d = None
+        if need[0]:
+            h, w = depth.shape[2:]
+            grad_d = _kbnet_data_gradient(g, weight, 1, 1, depth.shape[1], h, w, packed_t)
+        return grad_d, grad_w, None, None, None, None
+
+
+@_on_tensor_device
+def kb_xyz(depth: torch.Tensor, weight: torch.Tensor, coordinates: torch.Tensor, negative_slope: Optional[float] = 0.2,
+           packed: Optional[torch.Tensor] = None, packed_t=None):
+    """(xyz, z) of a KB layer (reference src/net_utils.py:1352-1359): z = act(conv_{1 x 1}(depth)) with `weight` 1 x C x 1 x 1,
+    xyz = coordinates * z (scale_planes).  Differentiable with respect to depth and the weight (one node); `coordinates`
+    (N x 3 x H x W, camera_coordinates) are data.  z is returned for inspection and carries no gradient."""
+    w = _weight(weight)
+    _planes(depth, "depth")
+    if tuple(w.shape) != (1, depth.shape[1], 1, 1):
+        raise KbnError(f"kb_xyz: weight must be 1 x {depth.shape[1]} x 1 x 1, got {tuple(w.shape)}")
+    if coordinates.requires_grad:
+        raise KbnError("kb_xyz: coordinates require grad, but they are data and get no gradient; detach them")
+    if negative_slope is not None and negative_slope < 0:
+        raise KbnError(f"kb_xyz: negative_slope must be >= 0, got {negative_slope}")
+    if torch.is_grad_enabled() and (weight.requires_grad or depth.requires_grad):
+        return _KbXyz.apply(depth, weight, coordinates, negative_slope, packed, packed_t)
+    z = _kbnet_conv_launch([depth], w, 1, negative_slope, packed)
+    return scale_planes(coordinates, z), z
+
+
+_IDENTITY_TAP = {}
+
+
+class _DepthMap(torch.autograd.Function):
+    """depth = d_min / (sigmoid(logits) + d_min / d_max) as a differentiable node.  Saved: the logits and the depth."""
+
+    @staticmethod
+    def forward(ctx, logits, min_predict_depth, max_predict_depth):
+        dev = logits.device
+        if dev not in _IDENTITY_TAP:   # the head kernel over the one plane with an identity tap: 1.0 * logit + eight exact zeros
+            _IDENTITY_TAP[dev] = torch.nn.functional.pad(torch.ones((1, 1, 1, 1), device=dev, dtype=torch.float32), (1, 1, 1, 1))
+        lg = logits.detach().contiguous()
+        depth = depth_head(lg, _IDENTITY_TAP[dev], min_predict_depth, max_predict_depth)
+        ctx.save_for_backward(lg, depth)
+        ctx.dmin = min_predict_depth
+        return depth
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_depth):
+        logits, depth = ctx.saved_tensors
+        return depth_map_backward(logits, depth, grad_depth.contiguous(), ctx.dmin), None, None
+
+
+@_on_tensor_device
+def depth_map(logits: torch.Tensor, min_predict_depth: float, max_predict_depth: float) -> torch.Tensor:
+    """KBNetModel.forward's mapping of the N x 1 x H x W logits (reference src/kbnet_model.py:181-184), differentiable (one node)."""
+    _require(logits, "logits", 4)
+    if logits.shape[1] != 1:
+        raise KbnError(f"depth_map: logits must be N x 1 x H x W, got {tuple(logits.shape)}")
+    return _DepthMap.apply(logits, float(min_predict_depth), float(max_predict_depth))

@@ -747,6 +747,41 @@ int kbn_add_act_forward(const float* a, const float* b, float* y, long long coun
 int kbn_add_act_backward(const float* y, const float* grad_y, float* grad, long long count, int apply_activation,
                          float negative_slope, kbn_stream_t stream);
 
+/* ------------------------------------------------- depth network (training: what only KBNet's backward needs) ----
+ * KBNetModel(trainable=True): the layers of the depth network one by one, each a differentiable node.  The conv gradients are the
+ * entries of the two sections above; these are the three pieces only KBNet has.  fp32 in and out, no atomics, nothing cleared
+ * beforehand, every output element written exactly once by the one launch: a call's bits are a function of its arguments alone.
+ *
+ * kbn_resize_nearest_forward: torch.nn.functional.interpolate(mode='nearest', size=(out_h, out_w)) in front of an up-conv
+ *   (UpConv2d.forward, reference src/net_utils.py:484-499; DecoderBlock.forward :1453-1487) as a tensor of its own:
+ *   out[n, c, Y, X] = in[n, c, idx(Y, in_h, out_h), idx(X, in_w, out_w)] with the index rule of KBN_RESIZE_NEAREST (the same device
+ *   function).  in N x channels x in_h x in_w, out N x channels x out_h x out_w, dense planes, frames *_batch_stride elements apart.
+ *   out_h >= in_h and out_w >= in_w; a smaller output is KBN_ERR_UNSUPPORTED.
+ * kbn_resize_nearest_backward: grad_in[n, c, y, x] = the sum of grad_out[n, c, Y, X] over the destination pixels with idx(Y) = y and
+ *   idx(X) = x, taken in row-major order (a gather: one thread per source pixel, or per four of a row). */
+int kbn_resize_nearest_forward(const float* in, long long in_batch_stride, float* out, long long out_batch_stride, int n,
+                               int channels, int in_height, int in_width, int out_height, int out_width, kbn_stream_t stream);
+int kbn_resize_nearest_backward(const float* grad_out, long long grad_out_batch_stride, float* grad_in,
+                                long long grad_in_batch_stride, int n, int channels, int in_height, int in_width, int out_height,
+                                int out_width, kbn_stream_t stream);
+
+/* The backprojection of a KB layer, z = act(proj_depth(depth)), xyz = coordinates * z (CalibratedBackprojectionBlock.forward,
+ * reference src/net_utils.py:1352-1359), differentiated with respect to proj_depth's PRE-activation:
+ *   grad_pre[n, 0, y, x] = act'(z) * sum_c coordinates[n, c, y, x] grad_xyz[n, c, y, x], c < 3; act'(z) = 1 where z > 0, negative_slope
+ *   elsewhere (the branch is read from the saved OUTPUT z, as kbn_add_act_backward reads it), 1 everywhere without apply_activation.
+ * z and grad_pre N x 1 x height x width, coordinates and grad_xyz N x 3 x height x width (grad_xyz usually a channel slice of
+ * conv_fused's data gradient), dense planes, frames *_batch_stride elements apart. */
+int kbn_kb_xyz_backward(const float* z, long long z_batch_stride, const float* coordinates, long long coordinates_batch_stride,
+                        const float* grad_xyz, long long grad_xyz_batch_stride, float* grad_pre, long long grad_pre_batch_stride,
+                        int n, int height, int width, int apply_activation, float negative_slope, kbn_stream_t stream);
+
+/* The gradient of KBNetModel.forward's depth mapping depth = d_min / (sigmoid(l) + d_min / d_max) (reference
+ * src/kbnet_model.py:181-184) over `count` contiguous floats: grad_logits = -grad_depth depth^2 / d_min * s (1 - s), s = sigmoid(l),
+ * with s (1 - s) taken as e / (1 + e)^2, e = exp(-|l|) (no cancellation where the sigmoid saturates).  logits and depth: what the
+ * forward produced (kbn_depth_head_forward with `logits`). */
+int kbn_depth_map_backward(const float* logits, const float* depth, const float* grad_depth, float* grad_logits, long long count,
+                           float min_predict_depth, kbn_stream_t stream);
+
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:
  *   data_utils.load_image   Image.open(path).convert('RGB') -> float32   reference src/data_utils.py:58-85

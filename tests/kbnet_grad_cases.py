@@ -1,0 +1,99 @@
+"""The cases the depth network's backward tests share (CPU oracle / power tests, the GPU model tests, the golden generator): what each
+is, and its inputs regenerated from seeds (kbnet_amd.synthetic) instead of stored.  The smallest shapes at which the kernels can still
+go wrong; narrow widths are KBNetConfig.narrow()."""
+import dataclasses
+
+import numpy as np
+import torch
+
+import kbnet_amd as kb
+
+KITTI, VOID = kb.kitti_config(), kb.void_config()
+GAIN = 1.0      # of synthetic.make_state_dicts: logits of order one (at 1.3 the depth saturates at both ends of its range)
+
+
+def _case(cfg, n, h, w, seed, kind="kitti"):
+    return dict(cfg=cfg, n=n, h=h, w=w, seed=seed, kind=kind)
+
+
+# the two goldens (tests/golden/kbnet_grad_*.npz): the reference's own autograd in fp64
+GOLDEN = {
+    # maps 23 x 39, 12 x 20, 6 x 10, 3 x 5, 2 x 3: every resize but one has H = 2h - 1 or W = 2w - 1
+    "kbnet_grad_kitti_odd": _case(KITTI.narrow(), 2, 45, 77, 31),
+    # plain levels 1 and 3: two conv_image weights without a gradient
+    "kbnet_grad_relu_kb02": _case(dataclasses.replace(KITTI.narrow(), resolutions_backprojection=(0, 2), activation_func="relu"), 2, 45, 77, 33),
+}
+# every case the GPU model tests run against the fp64 oracle: the gate's TOL is measured over these
+MODEL = dict(GOLDEN)
+MODEL.update({
+    "narrow_void": _case(VOID.narrow(), 2, 61, 50, 35, kind="void"),
+    # block 4 twice, block 5 unused: the reference needs levels 2 and 3 (and 4) of one width for it
+    "level4_listed": _case(dataclasses.replace(KITTI.narrow(), resolutions_backprojection=(0, 1, 2, 3, 4),
+                                               n_filters_encoder_image=(8, 16, 32, 32, 32), n_filters_encoder_depth=(4, 8, 16, 16, 16)),
+                           2, 45, 77, 37),
+    "linear": _case(dataclasses.replace(KITTI.narrow(), resolutions_backprojection=(0,), activation_func="linear"), 1, 33, 40, 59),
+    # two filter tiles and several channel tiles in every conv gradient
+    "full_width": _case(KITTI, 1, 64, 96, 61),
+    "tiny": _case(KITTI.narrow(), 1, 17, 19, 43),      # maps 9 x 10, 5 x 5, 3 x 3, 2 x 2, 1 x 1
+})
+
+
+def inputs(c):
+    """(image, sparse_depth, validity_map_depth, intrinsics, S2D / encoder / decoder state dicts, cotangent N x 1 x H x W fp64), CPU."""
+    frames = kb.synthetic.make_frames(c["n"], c["h"], c["w"], c["kind"], seed=c["seed"] + 100)
+    sds = kb.synthetic.make_state_dicts(c["cfg"], seed=c["seed"], gain=GAIN)
+    cot = torch.from_numpy(np.random.default_rng(c["seed"] + 200).standard_normal((c["n"], 1, c["h"], c["w"])))
+    return (*frames, *sds, cot)
+
+
+def golden(name):
+    """The two files of a golden (tests/golden/<name>.npz and <name>_enc.npz: the encoder's gradients apart, each under 1 MiB) as one
+    dict of tensors."""
+    import os
+    out = {}
+    for suffix in ("", "_enc"):
+        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + suffix + ".npz")) as z:
+            out.update({k: torch.from_numpy(np.asarray(z[k])) for k in z.files})
+    return out
+
+
+def checksums(image, sparse_depth, validity_map_depth, intrinsics, sd_s2d, sd_encoder, sd_decoder):
+    """Sums (fp64) that tie regenerated inputs to the ones a golden was made from."""
+    out = {"image": float(image.double().sum()), "sparse_depth": float(sparse_depth.double().sum()),
+           "validity_map_depth": float(validity_map_depth.double().sum()), "intrinsics": float(intrinsics.double().sum())}
+    for grp, sd in (("s2d", sd_s2d), ("enc", sd_encoder), ("dec", sd_decoder)):
+        out[grp] = float(sum(v.double().abs().sum() for v in sd.values()))
+    return out
+
+
+def untouched(c):
+    """The parameters no forward touches, whose .grad stays None, as the reference's autograd leaves them: conv_image of a KB level
+    whose successor is plain (the next conv_image reads conv_fused; the image branch lends only its shape), and with level 4 listed
+    all of block 5, which the reference builds and never calls."""
+    listed = tuple(c["cfg"].resolutions_backprojection)
+    out = []
+    for level in range(4):
+        if level in listed and (level + 1) not in listed:
+            out.append(f"enc::calibrated_backprojection{level + 1}.conv_image.conv_block.0.conv.weight")
+    if 4 in listed:
+        out += [f"enc::calibrated_backprojection5.{k}" for k in ("conv_image.conv_block.0.conv.weight", "conv_depth.conv_block.0.conv.weight",
+                                                                  "proj_depth.conv.weight", "conv_fused.conv.weight")]
+    return out
+
+
+def fp32_masks(c):
+    """The branches an fp32 run takes, as the GPU tests read them from the device: from the oracle's own fp32 forward."""
+    import kbnet_grad_oracle as kgo
+    args = inputs(c)
+    with torch.no_grad():
+        out = kgo.forward(*args[:7], c["cfg"])
+    return kgo.masks_of(out["pre"])
+
+
+# ---- operator cases (tests/test_kbnet_backward_gpu.py) ----
+def depth_map_inputs():
+    """(logits, gradient) fp64, exactly representable in fp32: logits spread over [-8, 8], and saturated ones at +-30."""
+    g = torch.Generator().manual_seed(11)
+    logits = torch.cat([(16 * torch.rand(2, 1, 33, 41, generator=g, dtype=torch.float64) - 8).flatten(),
+                        torch.tensor([30.0, -30.0, 30.0, -30.0, 0.0], dtype=torch.float64)]).float().double().view(1, 1, 1, -1)
+    return logits, torch.randn(logits.shape, generator=g, dtype=torch.float64).float().double()

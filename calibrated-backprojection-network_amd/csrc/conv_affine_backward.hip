@@ -6,12 +6,8 @@
 // fp32 in and out; NO floating-point atomics: every sum has a fixed order, two runs give the same bits.  The stride-2 3 x 3 and 7 x 7
 // convs keep the gradients of posenet_backward.hip; BatchNorm2d keeps its kernels there too.
 //
-// conv_bwd_weight_kernel<KS, STRIDE, MB>: the OIHW weight gradient for (k, stride) in {(3, 1), (1, 1), (1, 2)}, padding k / 2 -- the
-//   tiling of conv_s2_bwd_weight_kernel (posenet_backward.hip; conv_bwd_weight.h holds what the two share) with the stride a template
-//   argument and a K loop of its own (pose_igemm.h: a folded loop was slower):
-//   M = output channels, 16 MB per workgroup;  N = (input channel, ky, kx), 64 per workgroup, decoded once before the K loop;
-//   K = every output pixel of the batch, 32 per chunk, on v_mfma_f32_16x16x4_f32; double-buffered LDS with pitches = 17 mod 32;
-//   grid.z splits K into planes of a scratch buffer that sum_splits_kernel adds in split order.
+// The OIHW weight gradient for (k, stride) in {(3, 1), (1, 1), (1, 2)}: conv_bwd_weight.hip (the one kernel family and host body of
+//   every conv's weight gradient); kbn_conv2d_backward_weight here is this file's case check in front of it.
 //
 // The data gradient at stride 1 (k odd, padding k / 2) IS the forward conv of grad_out with the weight transposed (O <-> I) and both
 //   tap axes flipped: conv_bwd_data_pack_kernel writes that weight in conv_affine_kernel's packed order, with the unit scale and
@@ -32,126 +28,6 @@ namespace kbn {
 namespace {
 
 constexpr int CA_KC = 32;   // conv_affine.hip's K chunk: the packed order of the stride-1 data gradient's weight
-
-// ---- weight gradient ----------------------------------------------------------------------------------------------------
-template <int KS, int STRIDE, int MB>
-__global__ __launch_bounds__(256) void conv_bwd_weight_kernel(const BwParams p) {
-    constexpr int KK = KS * KS, PAD = KS / 2, BM = 16 * MB, AP = bw_ap(MB);
-    constexpr int AJ = BM / 8;    // rows of A a thread stages per chunk
-    __shared__ float As[2][BW_KC * AP];
-    __shared__ float Bs[2][BW_KC * BW_BP];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    const int nt = blockIdx.x, mt = blockIdx.y, split = blockIdx.z;
-    const int HW = p.H * p.W, OHW = p.OH * p.OW;
-    const int px = tid & (BW_KC - 1), cr = tid >> 5;   // this thread's pixel of a chunk; its first row / column
-
-    // the 8 columns (input channel, tap) this thread gathers, fixed over the K loop: c << 6 | ky << 3 | kx, or -1
-    int cols[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int col = nt * BW_BN + cr + 8 * j;
-        if (col < p.CK) {
-            const int c = col / KK, t = col - c * KK;
-            const int ky = t / KS, kx = t - ky * KS;
-            cols[j] = (c << 6) | (ky << 3) | kx;
-        } else {
-            cols[j] = -1;
-        }
-    }
-
-    const int c_begin = split * p.cps;
-    const int c_end = min(p.nchunks, c_begin + p.cps);
-
-    float va[AJ], vb[8];
-    auto load_chunk = [&](int chunk) {
-        const int m = chunk * BW_KC + px;
-        const bool mvalid = m < p.M;
-        int fn = 0, rem = 0, iy0 = 0, ix0 = 0;
-        if (mvalid) {
-            fn = m / OHW;
-            rem = m - fn * OHW;
-            const int oy = rem / p.OW, ox = rem - oy * p.OW;
-            iy0 = STRIDE * oy - PAD;
-            ix0 = STRIDE * ox - PAD;
-        }
-        const float* gf = p.g + (long long)fn * p.gbs + rem;
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) {
-            const int oc = mt * BM + cr + 8 * j;
-            va[j] = (mvalid && oc < p.OC) ? gf[(long long)oc * OHW] : 0.f;
-        }
-        const float* f0 = p.src0 + (long long)fn * p.bs0;
-        const float* f1 = p.src1 ? p.src1 + (long long)fn * p.bs1 : nullptr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int e = cols[j];
-            const int c = e >> 6, iy = iy0 + ((e >> 3) & 7), ix = ix0 + (e & 7);
-            float v = 0.f;
-            if (mvalid && e >= 0 && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
-                const float* plane = (c < p.C0) ? f0 + (long long)c * HW : f1 + (long long)(c - p.C0) * HW;
-                v = plane[iy * p.W + ix];
-            }
-            vb[j] = v;
-        }
-    };
-    auto store_chunk = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < AJ; ++j) As[buf][px * AP + cr + 8 * j] = va[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) Bs[buf][px * BW_BP + cr + 8 * j] = vb[j];
-    };
-
-    f32x4 acc[MB];
-#pragma unroll
-    for (int mi = 0; mi < MB; ++mi) acc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (c_begin < c_end) {
-        load_chunk(c_begin);
-        store_chunk(0);
-    }
-    __syncthreads();
-    for (int chunk = c_begin; chunk < c_end; ++chunk) {
-        const int buf = (chunk - c_begin) & 1;
-        const bool more = chunk + 1 < c_end;
-        if (more) load_chunk(chunk + 1);
-        const float* Ab = As[buf] + lk * AP + li;
-        const float* Bb = Bs[buf] + lk * BW_BP + wave * 16 + li;
-#pragma unroll
-        for (int k4 = 0; k4 < BW_KC / 4; ++k4) {
-            const float b = Bb[k4 * 4 * BW_BP];
-#pragma unroll
-            for (int mi = 0; mi < MB; ++mi)
-                acc[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(Ab[k4 * 4 * AP + mi * 16], b, acc[mi], 0, 0, 0);
-        }
-        if (more) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
-
-    // lane (li, lk) holds output channels 4 lk + r of each row block for column li of this wave's 16
-    const int col = nt * BW_BN + wave * 16 + li;
-    if (col < p.CK) {
-        float* o = p.out + (long long)split * p.OC * p.CK + col;
-#pragma unroll
-        for (int mi = 0; mi < MB; ++mi) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int oc = mt * BM + mi * 16 + lk * 4 + r;
-                if (oc < p.OC) o[(long long)oc * p.CK] = acc[mi][r];
-            }
-        }
-    }
-}
-
-template <int KS, int STRIDE>
-void bwd_weight_launch_mb(const BwParams& p, int mb, dim3 grid, hipStream_t stream) {
-    switch (mb) {
-        case 1: hipLaunchKernelGGL((conv_bwd_weight_kernel<KS, STRIDE, 1>), grid, dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((conv_bwd_weight_kernel<KS, STRIDE, 2>), grid, dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((conv_bwd_weight_kernel<KS, STRIDE, 4>), grid, dim3(256), 0, stream, p); break;
-    }
-}
 
 bool bw_case_ok(int ks, int stride) { return (ks == 3 && stride == 1) || (ks == 1 && (stride == 1 || stride == 2)); }
 
@@ -273,57 +149,18 @@ constexpr long long MAX_ELEMENTS = 0x7fffffffLL * 256LL;   // blocks of 256 thre
 
 using namespace kbn;
 
+// ---- weight gradient: conv_bwd_weight.hip behind this file's case check ---------------------------------------------------
 extern "C" size_t kbn_conv2d_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size, int stride,
                                                            int in_height, int in_width, int splits) {
     if (!bw_case_ok(kernel_size, stride)) return 0;
-    const BwPlan pl = bwd_weight_plan(n, out_channels, in_channels, kernel_size, stride, in_height, in_width, splits);
-    if (!pl.ok || pl.splits <= 1) return 0;
-    return (size_t)pl.splits * out_channels * pl.CK * sizeof(float);
+    return conv_bwd_weight_scratch_bytes(n, out_channels, in_channels, kernel_size, stride, in_height, in_width, splits);
 }
 
 extern "C" int kbn_conv2d_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out, long long grad_out_batch_stride,
                                           float* grad_weight, int n, int out_channels, int kernel_size, int stride, int in_height,
                                           int in_width, int splits, float* scratch, size_t scratch_bytes, kbn_stream_t stream) {
-    if (!srcs || !grad_out || !grad_weight) return KBN_ERR_INVALID_ARGUMENT;
-    if (n_src < 1 || n_src > 2 || n <= 0 || out_channels <= 0 || in_height <= 0 || in_width <= 0) return KBN_ERR_INVALID_ARGUMENT;
-    if (!bw_case_ok(kernel_size, stride)) return KBN_ERR_UNSUPPORTED;
-    BwParams p{};
-    int ctot = 0;
-    if (int rc = check_tensor_srcs(srcs, n_src, n, in_height, in_width, &ctot)) return rc;
-    if (ctot >= (1 << 24)) return KBN_ERR_UNSUPPORTED;   // the column code keeps the channel above 6 bits of tap
-    const BwPlan pl = bwd_weight_plan(n, out_channels, ctot, kernel_size, stride, in_height, in_width, splits);
-    if (!pl.ok) return KBN_ERR_UNSUPPORTED;
-    if (grad_out_batch_stride < (long long)out_channels * pl.OH * pl.OW && n > 1) return KBN_ERR_INVALID_ARGUMENT;
-    const long long total = (long long)out_channels * pl.CK;
-    if (pl.splits > 1 && (!scratch || scratch_bytes < (size_t)pl.splits * total * sizeof(float))) return KBN_ERR_INVALID_ARGUMENT;
-    p.g = grad_out;
-    p.gbs = grad_out_batch_stride;
-    p.src0 = srcs[0].data;
-    p.bs0 = srcs[0].batch_stride;
-    p.C0 = srcs[0].channels;
-    if (n_src == 2) { p.src1 = srcs[1].data; p.bs1 = srcs[1].batch_stride; }
-    p.Ctot = ctot;
-    p.out = pl.splits > 1 ? scratch : grad_weight;
-    p.N = n;
-    p.OC = out_channels;
-    p.H = in_height;
-    p.W = in_width;
-    p.OH = pl.OH;
-    p.OW = pl.OW;
-    p.M = pl.M;
-    p.CK = pl.CK;
-    p.nchunks = pl.nchunks;
-    p.cps = pl.cps;
-    const dim3 grid(pl.ntn, pl.ntm, (unsigned)pl.splits);
-    if (kernel_size == 3) bwd_weight_launch_mb<3, 1>(p, pl.mb, grid, (hipStream_t)stream);
-    else if (stride == 1) bwd_weight_launch_mb<1, 1>(p, pl.mb, grid, (hipStream_t)stream);
-    else bwd_weight_launch_mb<1, 2>(p, pl.mb, grid, (hipStream_t)stream);
-    KBN_CHECK_LAUNCH();
-    if (pl.splits > 1) {
-        sum_splits_launch(scratch, grad_weight, total, pl.splits, (hipStream_t)stream);
-        KBN_CHECK_LAUNCH();
-    }
-    return KBN_OK;
+    return conv_bwd_weight(bw_case_ok(kernel_size, stride), srcs, n_src, grad_out, grad_out_batch_stride, grad_weight, n, out_channels,
+                           kernel_size, stride, in_height, in_width, splits, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 static bool bd_case_ok(int ks, int stride) { return bw_case_ok(ks, stride); }

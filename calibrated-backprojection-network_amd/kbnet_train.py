@@ -48,13 +48,9 @@ def activation_names(resolutions_backprojection, n_pool_convs: int = 3) -> List[
 
 
 def _packed_t(layer):
-    """weight -> the data gradient's blob of a modules.Conv2d, cached on the layer and re-packed when the weight changed."""
-    from .modules import _PackedBlob
-    s2 = (layer.kernel_size, layer.stride) == (3, 2)
-    blob = layer.__dict__.get("_packed_bwd_data")
-    if blob is None:
-        blob = layer._packed_bwd_data = _PackedBlob(ops.pack_conv2d_s2_backward_data_weight if s2 else ops.pack_conv2d_backward_data_weight)
-    return (lambda w: blob.get(w)) if s2 else (lambda w: blob.get(w, stride=layer.stride))
+    """weight -> the data gradient's blob of a modules.Conv2d, from the cache on the layer (modules.data_gradient_blob)."""
+    from .modules import data_gradient_blob
+    return lambda weight: data_gradient_blob(layer, weight)
 
 
 def _conv(layer, inputs, inner: Dict[str, torch.Tensor], name: Optional[str]):

@@ -122,6 +122,16 @@ def packed_blobs(model):
     return [v for top in model.modules() for sub in top.modules() for v in vars(sub).values() if isinstance(v, _PackedBlob)]
 
 
+def data_gradient_blob(layer, weight):
+    """`weight` (the conv weight of `layer`: a Conv2d here, a PoseConv2d, a ResNetConv2d) as the data gradient of the layer's
+    (kernel size, stride) reads it.  The _PackedBlob is made on the first data gradient -- a model that never trains carries none --
+    and packed_blobs() finds it from then on."""
+    blob = layer.__dict__.get("_packed_bwd_data")
+    if blob is None:
+        blob = layer._packed_bwd_data = _PackedBlob(ops.pack_conv2d_data_gradient_weight)
+    return blob.get(weight, stride=layer.stride)
+
+
 # ------------------------------------------------------------------------ layers
 def _run_split(layer, weight, srcs, n, h, w, out=None, up2x=False, out_absmax=None, stats=None, pair_out=False, transposed=False):
     """Conv2d.run_split for `layer` = a Conv2d (weight = its OIHW parameter) or, with `transposed` and `up2x`, a TransposeConv2d

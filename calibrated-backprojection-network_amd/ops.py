@@ -1550,9 +1550,49 @@ def pose_head(latent: torch.Tensor, weight: torch.Tensor, return_dof: bool = Fal
     return (out, dof_out) if return_dof else out
 
 
+# ------------------------------------------------------------------ conv gradients: the family that serves a (kernel size, stride)
+# True: conv2d_s2_backward_data / conv2d_s2_backward_weight (csrc/posenet_backward.hip); False: conv2d_backward_data /
+# conv2d_backward_weight (csrc/conv_affine_backward.hip).  Both weight gradients are the one kernel of csrc/conv_bwd_weight.hip.
+# Every case list below and every choice between the two families reads this table.
+_S2_FAMILY = {(3, 2): True, (5, 2): True, (7, 2): True, (3, 1): False, (1, 1): False, (1, 2): False}
+_BACKWARD_CASES = tuple(ks for ks, s2 in _S2_FAMILY.items() if not s2)   # (3, 1), (1, 1), (1, 2): the error texts print them in this order
+_KBNET_CASES = ((3, 1), (3, 2), (1, 1), (1, 2))                          # the depth network's convs, in the order its error text prints
+assert set(_KBNET_CASES) <= set(_S2_FAMILY)
+
+
+def _conv_backward_weight(fn: str, check_case, record: str, ks, inputs, grad_out, splits, out):
+    """The one body of conv2d_s2_backward_weight and conv2d_backward_weight.  `ks`: (kernel size,) or (kernel size, stride) -- the
+    arguments of `check_case(fn, *ks)`, of the C pair kbn_<fn> / kbn_<fn>_scratch_bytes in that place, and of the launch record
+    `record`<ks, filter blocks>."""
+    lib = _lib.load()
+    check_case(fn, *ks)
+    kernel_size, stride = ks[0], (ks[1] if len(ks) == 2 else 2)
+    inputs, srcs, n, h, w, cin = _conv_inputs(fn, inputs)
+    gptr, gbs = _planes(grad_out, "grad_out")
+    oc, oh, ow = grad_out.shape[1], -(-h // stride), -(-w // stride)
+    if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
+        raise KbnError(f"{fn}: grad_out is {tuple(grad_out.shape)}, the conv of inputs {tuple(inputs[0].shape)} "
+                       f"has {n} frames of {oh} x {ow} maps")
+    if splits is not None and (not isinstance(splits, int) or splits < 1):
+        raise KbnError(f"{fn}: splits must be a positive integer or None, got {splits!r}")
+    splits = 0 if splits is None else splits
+    out = _out_tensor(out, (oc, cin, kernel_size, kernel_size), grad_out.device, f"{fn}: out")
+    nbytes = getattr(lib, f"kbn_{fn}_scratch_bytes")(n, oc, cin, *ks, h, w, splits)
+    scratch = torch.empty(nbytes // 4, device=grad_out.device, dtype=torch.float32) if nbytes else None
+    arr = (ConvSrc * len(srcs))(*srcs)
+    k2 = kernel_size * kernel_size
+    mt = 16 if oc <= 16 else (32 if oc <= 32 else 64)
+    check(_launch(f"{record}<{','.join(map(str, ks))},{mt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
+                  lambda: getattr(lib, f"kbn_{fn}")(arr, len(srcs), gptr, gbs, out.data_ptr(), n, oc, *ks, h, w, splits,
+                                                    scratch.data_ptr() if scratch is not None else None, nbytes, _stream()),
+                  executed=2.0 * (-(-n * oh * ow // 32) * 32) * (-(-cin * k2 // 64) * 64) * (-(-oc // mt) * mt), pipe="fp32",
+                  nbytes=_src_bytes(srcs, n) + 4.0 * (n * oc * oh * ow + oc * cin * k2)), f"kbn_{fn}")
+    return out
+
+
 # ------------------------------------------------------------------ pose network (training: csrc/posenet_backward.hip)
 def _s2_kernel_size(fn: str, kernel_size):
-    if kernel_size not in (3, 5, 7):
+    if not _S2_FAMILY.get((kernel_size, 2)):
         raise KbnError(f"{fn}: kernel size 3, 5 or 7, got {kernel_size}")
 
 
@@ -1612,29 +1652,7 @@ def conv2d_s2_backward_weight(inputs: Sequence[torch.Tensor], grad_out: torch.Te
     (kbn_conv2d_s2_backward_weight): -> F x sum(C_i) x k x k, plain OIHW.  The sum over the batch's output pixels is split over
     `splits` workgroups per tile (None: chosen from the shape) whose partial sums a second launch adds in split order: the bits
     are a function of the arguments (and of `splits`) alone."""
-    lib = _lib.load()
-    _s2_kernel_size("conv2d_s2_backward_weight", kernel_size)
-    inputs, srcs, n, h, w, cin = _conv_inputs("conv2d_s2_backward_weight", inputs)
-    gptr, gbs = _planes(grad_out, "grad_out")
-    oc, oh, ow = grad_out.shape[1], (h + 1) // 2, (w + 1) // 2
-    if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
-        raise KbnError(f"conv2d_s2_backward_weight: grad_out is {tuple(grad_out.shape)}, the conv of inputs {tuple(inputs[0].shape)} "
-                       f"has {n} frames of {oh} x {ow} maps")
-    if splits is not None and (not isinstance(splits, int) or splits < 1):
-        raise KbnError(f"conv2d_s2_backward_weight: splits must be a positive integer or None, got {splits!r}")
-    splits = 0 if splits is None else splits
-    out = _out_tensor(out, (oc, cin, kernel_size, kernel_size), grad_out.device, "conv2d_s2_backward_weight: out")
-    nbytes = lib.kbn_conv2d_s2_backward_weight_scratch_bytes(n, oc, cin, kernel_size, h, w, splits)
-    scratch = torch.empty(nbytes // 4, device=grad_out.device, dtype=torch.float32) if nbytes else None
-    arr = (ConvSrc * len(srcs))(*srcs)
-    k2 = kernel_size * kernel_size
-    mt = 16 if oc <= 16 else (32 if oc <= 32 else 64)
-    check(_launch(f"conv_s2_bwd_weight<{kernel_size},{mt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
-                  lambda: lib.kbn_conv2d_s2_backward_weight(arr, len(srcs), gptr, gbs, out.data_ptr(), n, oc, kernel_size, h, w, splits,
-                                                            scratch.data_ptr() if scratch is not None else None, nbytes, _stream()),
-                  executed=2.0 * (-(-n * oh * ow // 32) * 32) * (-(-cin * k2 // 64) * 64) * (-(-oc // mt) * mt), pipe="fp32",
-                  nbytes=_src_bytes(srcs, n) + 4.0 * (n * oc * oh * ow + oc * cin * k2)), "kbn_conv2d_s2_backward_weight")
-    return out
+    return _conv_backward_weight("conv2d_s2_backward_weight", _s2_kernel_size, "conv_s2_bwd_weight", (kernel_size,), inputs, grad_out, splits, out)
 
 
 def _channel_vector(fn: str, t, name: str, c: int) -> torch.Tensor:
@@ -1779,33 +1797,6 @@ def _conv2d_s2_launch(inputs, weight, packed):
     return conv2d_s2_affine([t.detach() for t in inputs], packed, ones, zeros, oc, k, negative_slope=None)
 
 
-class _Conv2dS2(torch.autograd.Function):
-    """The bias-free stride-2 conv as a differentiable node.  Saved: the weight and the inputs, nothing the forward computed.
-    Backward: one weight-gradient call, and one data-gradient launch only when an input asks for its gradient."""
-
-    @staticmethod
-    def forward(ctx, weight, packed, packed_t, *inputs):
-        ctx.save_for_backward(weight, *inputs)
-        ctx.packed_t = packed_t
-        return _conv2d_s2_launch(inputs, weight, packed)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_u):
-        weight, *inputs = ctx.saved_tensors
-        k = weight.shape[2]
-        need = ctx.needs_input_grad
-        g = grad_u.contiguous()
-        grad_w = conv2d_s2_backward_weight(inputs, g, k) if need[0] else None
-        grads = [None] * len(inputs)
-        if any(need[3:]):
-            packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
-            h, w = inputs[0].shape[2:]
-            got = conv2d_s2_backward_data(g, packed_t, [t.shape[1] for t in inputs], k, h, w)
-            grads = [gi if need[3 + i] else None for i, gi in enumerate(got)]
-        return (grad_w, None, None) + tuple(grads)
-
-
 @_on_tensor_device
 def conv2d_s2(inputs: Sequence[torch.Tensor], weight: torch.Tensor, packed: Optional[torch.Tensor] = None, packed_t=None) -> torch.Tensor:
     """conv_{k x k, stride 2, padding k // 2}(cat(inputs, 1)), no bias (k in {3, 5, 7}): conv2d_s2_affine's kernel with unit
@@ -1821,7 +1812,7 @@ def conv2d_s2(inputs: Sequence[torch.Tensor], weight: torch.Tensor, packed: Opti
     if cin != w.shape[1]:
         raise KbnError(f"conv2d_s2: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
     if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
-        return _Conv2dS2.apply(weight, packed, packed_t, *inputs)
+        return _RecordedConv.apply(lambda ins, wt: _conv2d_s2_launch(ins, wt, packed), False, None, 2, packed_t, weight, *inputs)
     return _conv2d_s2_launch(inputs, w, packed)
 
 
@@ -1913,9 +1904,6 @@ def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
 
 
 # ------------------------------------------------------------------ ResNet pose networks (training: csrc/conv_affine_backward.hip)
-_BACKWARD_CASES = ((3, 1), (1, 1), (1, 2))   # (kernel size, stride) of the new gradients; (3, 2) and (7, 2) are conv2d_s2_backward_*'s
-
-
 def _backward_case(fn: str, kernel_size, stride):
     if (kernel_size, stride) not in _BACKWARD_CASES:
         raise KbnError(f"{fn}: (kernel size, stride) one of {_BACKWARD_CASES}, got ({kernel_size}, {stride}); the 3 x 3 and 7 x 7 convs "
@@ -1930,30 +1918,7 @@ def conv2d_backward_weight(inputs: Sequence[torch.Tensor], grad_out: torch.Tenso
     conv2d_s2_backward_weight: the sum over the batch's output pixels is split over `splits` workgroups per tile (None: chosen
     from the shape) whose partial sums a second launch adds in split order; the bits are a function of the arguments (and of
     `splits`) alone."""
-    lib = _lib.load()
-    _backward_case("conv2d_backward_weight", kernel_size, stride)
-    inputs, srcs, n, h, w, cin = _conv_inputs("conv2d_backward_weight", inputs)
-    gptr, gbs = _planes(grad_out, "grad_out")
-    oc, oh, ow = grad_out.shape[1], -(-h // stride), -(-w // stride)
-    if oc < 1 or tuple(grad_out.shape) != (n, oc, oh, ow):
-        raise KbnError(f"conv2d_backward_weight: grad_out is {tuple(grad_out.shape)}, the conv of inputs {tuple(inputs[0].shape)} "
-                       f"has {n} frames of {oh} x {ow} maps")
-    if splits is not None and (not isinstance(splits, int) or splits < 1):
-        raise KbnError(f"conv2d_backward_weight: splits must be a positive integer or None, got {splits!r}")
-    splits = 0 if splits is None else splits
-    out = _out_tensor(out, (oc, cin, kernel_size, kernel_size), grad_out.device, "conv2d_backward_weight: out")
-    nbytes = lib.kbn_conv2d_backward_weight_scratch_bytes(n, oc, cin, kernel_size, stride, h, w, splits)
-    scratch = torch.empty(nbytes // 4, device=grad_out.device, dtype=torch.float32) if nbytes else None
-    arr = (ConvSrc * len(srcs))(*srcs)
-    k2 = kernel_size * kernel_size
-    mt = 16 if oc <= 16 else (32 if oc <= 32 else 64)
-    check(_launch(f"conv_bwd_weight<{kernel_size},{stride},{mt // 16}>", 2.0 * n * oh * ow * cin * k2 * oc,
-                  lambda: lib.kbn_conv2d_backward_weight(arr, len(srcs), gptr, gbs, out.data_ptr(), n, oc, kernel_size, stride, h, w,
-                                                         splits, scratch.data_ptr() if scratch is not None else None, nbytes,
-                                                         _stream()),
-                  executed=2.0 * (-(-n * oh * ow // 32) * 32) * (-(-cin * k2 // 64) * 64) * (-(-oc // mt) * mt), pipe="fp32",
-                  nbytes=_src_bytes(srcs, n) + 4.0 * (n * oc * oh * ow + oc * cin * k2)), "kbn_conv2d_backward_weight")
-    return out
+    return _conv_backward_weight("conv2d_backward_weight", _backward_case, "conv_bwd_weight", (kernel_size, stride), inputs, grad_out, splits, out)
 
 
 @_on_tensor_device
@@ -2017,39 +1982,70 @@ def _conv2d_pose_launch(inputs, weight, stride, packed):
     return conv2d_affine([t.detach() for t in inputs], packed, ones, zeros, oc, k, stride=stride, negative_slope=None)
 
 
-class _Conv2dPose(torch.autograd.Function):
-    """The bias-free conv of the ResNet pose networks as a differentiable node.  Saved: the weight and the inputs.  Backward by
-    (k, stride): (3, 2) and (7, 2) on conv2d_s2_backward_*, the rest on conv2d_backward_*; a data-gradient launch only when an
-    input asks for its gradient."""
+# ------------------------------------------------------------------ conv gradients: one dispatch, one recorded node
+def _weight_gradient(inputs, g, k, stride):
+    """The weight gradient of a conv over one to three concatenated inputs through the entry points that take two: it is linear in
+    the input-channel blocks, so a third input is a second call and the results are joined along dim 1."""
+    fn = (lambda ins: conv2d_s2_backward_weight(ins, g, k)) if _S2_FAMILY[(k, stride)] else (lambda ins: conv2d_backward_weight(ins, g, k, stride))
+    if len(inputs) <= 2:
+        return fn(inputs)
+    return torch.cat([fn(inputs[:2]), fn(inputs[2:])], dim=1)
+
+
+@_on_tensor_device
+def pack_conv2d_data_gradient_weight(weight: torch.Tensor, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """OIHW -> the blob the data gradient of conv_{k x k, stride, padding k // 2} reads: pack_conv2d_s2_backward_data_weight for k in
+    {3, 5, 7} at stride 2, pack_conv2d_backward_data_weight(weight, stride) at (3, 1), (1, 1) and (1, 2).  `out`: a blob to re-pack into."""
+    k = weight.shape[2] if isinstance(weight, torch.Tensor) and weight.dim() == 4 else None
+    if _S2_FAMILY.get((k, stride)):
+        return pack_conv2d_s2_backward_data_weight(weight, out)
+    return pack_conv2d_backward_data_weight(weight, stride, out)
+
+
+def _data_gradient(g, weight, k, stride, cin, h, w, packed_t):
+    """One launch over all `cin` channels into one buffer (the caller slices it by input).  `packed_t`: weight -> its
+    pack_conv2d_data_gradient_weight blob, from the caller's cache; None: packed here."""
+    blob = packed_t(weight) if packed_t is not None else pack_conv2d_data_gradient_weight(weight, stride)
+    if _S2_FAMILY[(k, stride)]:
+        return conv2d_s2_backward_data(g, blob, [cin], k, h, w)[0]
+    return conv2d_backward_data(g, blob, cin, k, stride, h, w)
+
+
+class _RecordedConv(torch.autograd.Function):
+    """[act](conv(cat(inputs))), no bias, as the one differentiable conv node of the three networks.  `launch(inputs, weight)` is
+    the network's forward launch; `epilogue`: that launch applied the activation `negative_slope`, so the output y is saved too (the
+    activation's branch is its sign) and the backward starts with add_act_backward.  Saved otherwise: the weight and the inputs,
+    nothing the forward computed.  Backward: the weight gradient through the two-input entry points, and -- only when an input asks
+    -- ONE data-gradient launch over all channels, returned as channel slices of its buffer."""
 
     @staticmethod
-    def forward(ctx, weight, stride, packed, packed_t, *inputs):
-        ctx.save_for_backward(weight, *inputs)
-        ctx.stride, ctx.packed_t = stride, packed_t
-        return _conv2d_pose_launch(inputs, weight, stride, packed)
+    def forward(ctx, launch, epilogue, negative_slope, stride, packed_t, weight, *inputs):
+        y = launch(inputs, weight.detach())
+        ctx.save_for_backward(weight, *inputs, *([y] if epilogue else []))
+        ctx.args = (epilogue, negative_slope, stride, packed_t)
+        return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_u):
+    def backward(ctx, grad_y):
+        epilogue, slope, stride, packed_t = ctx.args
         weight, *inputs = ctx.saved_tensors
-        k, stride = weight.shape[2], ctx.stride
-        need = ctx.needs_input_grad
-        g = grad_u.contiguous()
-        s2 = (k, stride) not in _BACKWARD_CASES
-        grad_w = None
-        if need[0]:
-            grad_w = conv2d_s2_backward_weight(inputs, g, k) if s2 else conv2d_backward_weight(inputs, g, k, stride)
+        g = grad_y.contiguous()
+        if epilogue:
+            g = add_act_backward(inputs.pop(), g, slope)
+        k = weight.shape[2]
+        need = ctx.needs_input_grad[5:]
+        grad_w = _weight_gradient(inputs, g, k, stride) if need[0] else None
         grads = [None] * len(inputs)
-        if any(need[4:]):
+        if any(need[1:]):
             h, w = inputs[0].shape[2:]
-            if s2:
-                packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
-                got = conv2d_s2_backward_data(g, packed_t, [t.shape[1] for t in inputs], k, h, w)
-            else:
-                packed_t = ctx.packed_t(weight) if ctx.packed_t is not None else pack_conv2d_backward_data_weight(weight, stride)
-                got = [conv2d_backward_data(g, packed_t, inputs[0].shape[1], k, stride, h, w)]
-            grads = [gi if need[4 + i] else None for i, gi in enumerate(got)]
-        return (grad_w, None, None, None) + tuple(grads)
+            buf = _data_gradient(g, weight, k, stride, weight.shape[1], h, w, packed_t)
+            at = 0
+            for i, t in enumerate(inputs):
+                if need[1 + i]:
+                    grads[i] = buf[:, at:at + t.shape[1]]
+                at += t.shape[1]
+        return (None,) * 5 + (grad_w,) + tuple(grads)
 
 
 @_on_tensor_device
@@ -2072,11 +2068,11 @@ def conv2d_pose(inputs: Sequence[torch.Tensor], weight: torch.Tensor, stride: in
     if cin != w.shape[1]:
         raise KbnError(f"conv2d_pose: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
     if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
-        if (k, stride) not in _BACKWARD_CASES + ((3, 2), (7, 2)):
+        if (k, stride) not in _S2_FAMILY:
             raise KbnError(f"conv2d_pose: no backward pass for kernel size {k} at stride {stride}")
-        if any(t.requires_grad for t in inputs) and len(inputs) > 1 and (k, stride) in _BACKWARD_CASES:
+        if any(t.requires_grad for t in inputs) and len(inputs) > 1 and not _S2_FAMILY[(k, stride)]:
             raise KbnError(f"conv2d_pose: the data gradient at kernel size {k}, stride {stride} takes one input, got {len(inputs)}")
-        return _Conv2dPose.apply(weight, stride, packed, packed_t, *inputs)
+        return _RecordedConv.apply(lambda ins, wt: _conv2d_pose_launch(ins, wt, stride, packed), False, None, stride, packed_t, weight, *inputs)
     return _conv2d_pose_launch(inputs, w, stride, packed)
 
 
@@ -2292,27 +2288,6 @@ def depth_map_backward(logits: torch.Tensor, depth: torch.Tensor, grad_depth: to
     return g
 
 
-_KBNET_CASES = ((3, 1), (3, 2), (1, 1), (1, 2))
-
-
-def _kbnet_weight_gradient(inputs, g, k, stride):
-    """The weight gradient of a conv over one to three concatenated inputs through the entry points that take two: it is linear in
-    the input-channel blocks, so a third input is a second call and the results are joined along dim 1."""
-    fn = (lambda ins: conv2d_s2_backward_weight(ins, g, k)) if (k, stride) == (3, 2) else (lambda ins: conv2d_backward_weight(ins, g, k, stride))
-    if len(inputs) <= 2:
-        return fn(inputs)
-    return torch.cat([fn(inputs[:2]), fn(inputs[2:])], dim=1)
-
-
-def _kbnet_data_gradient(g, weight, k, stride, cin, h, w, packed_t):
-    """One launch over all `cin` channels into one buffer (the caller slices it by input)."""
-    if (k, stride) == (3, 2):
-        blob = packed_t(weight) if packed_t is not None else pack_conv2d_s2_backward_data_weight(weight)
-        return conv2d_s2_backward_data(g, blob, [cin], k, h, w)[0]
-    blob = packed_t(weight) if packed_t is not None else pack_conv2d_backward_data_weight(weight, stride)
-    return conv2d_backward_data(g, blob, cin, k, stride, h, w)
-
-
 def _kbnet_conv_launch(inputs, weight, stride, negative_slope, packed):
     oc, _, k, _ = weight.shape
     if packed is None:
@@ -2321,39 +2296,6 @@ def _kbnet_conv_launch(inputs, weight, stride, negative_slope, packed):
     out = torch.empty((n, oc, -(-h // stride), -(-w // stride)), device=weight.device, dtype=torch.float32)
     return conv2d([tensor_src(t.detach(), f"inputs[{i}]") for i, t in enumerate(inputs)], packed, n, oc, k, stride, h, w, out,
                   negative_slope=negative_slope)
-
-
-class _Conv2dKbnet(torch.autograd.Function):
-    """act(conv(cat(inputs))) of the depth network as a differentiable node.  Saved: the output y (the activation's branch is its
-    sign), the inputs and the weight.  Backward: add_act_backward, the weight gradient through the two-input entry points, and --
-    only when an input asks -- ONE data-gradient launch over all channels, returned as channel slices of its buffer."""
-
-    @staticmethod
-    def forward(ctx, weight, stride, negative_slope, packed, packed_t, *inputs):
-        y = _kbnet_conv_launch(inputs, weight.detach(), stride, negative_slope, packed)
-        ctx.save_for_backward(weight, y, *inputs)
-        ctx.args = (stride, negative_slope, packed_t)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_y):
-        weight, y, *inputs = ctx.saved_tensors
-        stride, slope, packed_t = ctx.args
-        k = weight.shape[2]
-        need = ctx.needs_input_grad
-        g = add_act_backward(y, grad_y.contiguous(), slope)
-        grad_w = _kbnet_weight_gradient(inputs, g, k, stride) if need[0] else None
-        grads = [None] * len(inputs)
-        if any(need[5:]):
-            h, w = inputs[0].shape[2:]
-            buf = _kbnet_data_gradient(g, weight, k, stride, weight.shape[1], h, w, packed_t)
-            at = 0
-            for i, t in enumerate(inputs):
-                if need[5 + i]:
-                    grads[i] = buf[:, at:at + t.shape[1]]
-                at += t.shape[1]
-        return (grad_w, None, None, None, None) + tuple(grads)
 
 
 @_on_tensor_device
@@ -2384,7 +2326,8 @@ def conv2d_kbnet(inputs: Sequence[torch.Tensor], weight: torch.Tensor, stride: i
     if cin != w.shape[1]:
         raise KbnError(f"conv2d_kbnet: the inputs hold {cin} channels, the weight {tuple(w.shape)} takes {w.shape[1]}")
     if torch.is_grad_enabled() and (weight.requires_grad or any(t.requires_grad for t in inputs)):
-        return _Conv2dKbnet.apply(weight, stride, negative_slope, packed, packed_t, *inputs)
+        return _RecordedConv.apply(lambda ins, wt: _kbnet_conv_launch(ins, wt, stride, negative_slope, packed), True, negative_slope, stride,
+                                   packed_t, weight, *inputs)
     return _kbnet_conv_launch(inputs, w, stride, negative_slope, packed)
 
 
@@ -2408,11 +2351,11 @@ class _KbXyz(torch.autograd.Function):
         slope, packed_t = ctx.args
         need = ctx.needs_input_grad
         g = kb_xyz_backward(z, coordinates, grad_xyz, slope)
-        grad_w = conv2d_backward_weight([depth], g, 1, 1) if need[1] else None
+        grad_w = _weight_gradient([depth], g, 1, 1) if need[1] else None
         grad_d = None
         if need[0]:
             h, w = depth.shape[2:]
-            grad_d = _kbnet_data_gradient(g, weight, 1, 1, depth.shape[1], h, w, packed_t)
+            grad_d = _data_gradient(g, weight, 1, 1, depth.shape[1], h, w, packed_t)
         return grad_d, grad_w, None, None, None, None
 
 

@@ -70,7 +70,7 @@ class PoseConv2d(torch.nn.Module):
 
     def __init__(self, in_channels, out_channels, kernel_size, weight_initializer, slope):
         super().__init__()
-        self.in_channels, self.out_channels, self.kernel_size = in_channels, out_channels, kernel_size
+        self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, out_channels, kernel_size, 2
         self.slope = slope
         self.conv = _BareConv(in_channels, out_channels, kernel_size)
         _init_weight(self.conv.weight, weight_initializer)
@@ -79,21 +79,17 @@ class PoseConv2d(torch.nn.Module):
             p.requires_grad_(False)
         from .modules import _PackedBlob   # (modules.py imports this file at its end: not at the top)
         self._packed = _PackedBlob(ops.pack_conv2d_s2_affine_weight)
-        self._tkey = self._tblob = None   # the data gradient's transposed blob (packed_t): built on first use
         self._akey = self._scale = self._shift = None
 
     def packed(self):
         return self._packed.get(self.conv.weight)
 
     def packed_t(self, weight=None):
-        """The weight in the data gradient's order (ops.pack_conv2d_s2_backward_data_weight), re-packed when the weight changed.
-        Not a _PackedBlob: no graph of the eval-mode forward points into it, refresh_packed has nothing to do with it."""
-        weight = self.conv.weight if weight is None else weight
-        key = _state(weight)
-        if key != self._tkey:
-            self._tblob = ops.pack_conv2d_s2_backward_data_weight(weight, out=self._tblob)
-            self._tkey = key
-        return self._tblob
+        """The weight as the data gradient of this (k, stride) reads it (ops.pack_conv2d_data_gradient_weight), re-packed when the
+        weight changed.  A _PackedBlob like `_packed`, made on the first data gradient (modules.data_gradient_blob): refresh_packed
+        re-packs it only once it exists and its weight has changed, which the next backward would do anyway."""
+        from .modules import data_gradient_blob
+        return data_gradient_blob(self, self.conv.weight if weight is None else weight)
 
     def affine(self):
         """scale = g * rsqrt(var + eps), shift = b - mean * scale (BatchNorm2d.eval()), fp32 on the weights' device."""

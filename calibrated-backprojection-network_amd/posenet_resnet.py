@@ -56,18 +56,6 @@ class ResNetConv2d(PoseConv2d):
             self._shift = torch.zeros(self.out_channels, device=w.device)
         return self._scale, self._shift
 
-    def packed_t(self, weight=None):
-        """The weight as the data gradient of this (k, stride) reads it, re-packed when the weight changed: PoseConv2d.packed_t's
-        blob at (3, 2) and (7, 2), ops.pack_conv2d_backward_data_weight's elsewhere."""
-        if self.stride == 2 and self.kernel_size != 1:
-            return super().packed_t(weight)
-        weight = self.conv.weight if weight is None else weight
-        key = _state(weight)
-        if key != self._tkey:
-            self._tblob = ops.pack_conv2d_backward_data_weight(weight, self.stride, out=self._tblob)
-            self._tkey = key
-        return self._tblob
-
     def conv_recorded(self, inputs: List[torch.Tensor]):
         """`run_unfused` (PoseConv2d's: conv, [batch statistics], BatchNorm + activation; the conv alone without batch norm)
         starts from this conv."""

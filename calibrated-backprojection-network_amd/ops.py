@@ -2350,6 +2350,12 @@ class _KbXyz(torch.autograd.Function):
         depth, weight, z, coordinates = ctx.saved_tensors
         slope, packed_t = ctx.args
         need = ctx.needs_input_grad
+        # autograd hands over any layout (the stride-0 expand behind .sum(), channels-last, a step in W): dense planes -- KBNet's
+        # channel slice of the fused conv's data-gradient buffer -- are read in place, anything else (what _planes refuses) is made
+        # dense first
+        n, c, h, w = grad_xyz.shape
+        if grad_xyz.stride(3) != 1 or grad_xyz.stride(2) != w or grad_xyz.stride(1) != h * w:
+            grad_xyz = grad_xyz.contiguous()
         g = kb_xyz_backward(z, coordinates, grad_xyz, slope)
         grad_w = _weight_gradient([depth], g, 1, 1) if need[1] else None
         grad_d = None

@@ -35,6 +35,10 @@ MODEL.update({
     # two filter tiles and several channel tiles in every conv gradient
     "full_width": _case(KITTI, 1, 64, 96, 61),
     "tiny": _case(KITTI.narrow(), 1, 17, 19, 43),      # maps 9 x 10, 5 x 5, 3 x 3, 2 x 2, 1 x 1
+    # three and five frames on tiny maps: a 128-pixel tile or a 32-pixel K chunk of the deepest levels holds three or more frames, and
+    # frames straddle tiles.  Seeds by the rule written in resnet_pose_grad_cases.py, the first from 62 on with both properties.
+    "tiny_n3": _case(KITTI.narrow(), 3, 17, 19, 62),   # maps 9 x 10, 5 x 5, 3 x 3, 2 x 2, 1 x 1
+    "tiny_n5": _case(KITTI.narrow(), 5, 19, 35, 62),   # maps 10 x 18, 5 x 9, 3 x 5, 2 x 3, 1 x 2
 })
 
 

@@ -23,7 +23,7 @@ import kbnet_amd as kb
 import posenet_grad_oracle as pgo
 from oracle import kbnet_oracle as orc
 
-fraction, kink_check, KINK_BAND, KINK_SHARE = pgo.fraction, pgo.kink_check, pgo.KINK_BAND, pgo.KINK_SHARE
+fraction, kink_check, kink_room, KINK_BAND, KINK_SHARE = pgo.fraction, pgo.kink_check, pgo.kink_room, pgo.KINK_BAND, pgo.KINK_SHARE
 activation_names = kb.kbnet_train.activation_names      # the names are fixed in one place
 
 # The gate: |a - b| <= TOL |b| + TOL rms(b) per tensor, against fp64.  TOL = 3 x the worst fraction the oracle's own fp32 autograd

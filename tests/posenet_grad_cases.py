@@ -19,6 +19,11 @@ MODEL.update({
     "narrow_train_shape_running": dict(filters=pgo.FILTERS, n=2, h=130, w=136, seed=73, batch_norm="running"),
     "full_running": dict(filters=FULL, n=2, h=64, w=96, seed=75, batch_norm="running"),
     "full_batch": dict(filters=FULL, n=2, h=192, w=256, seed=77, batch_norm="batch"),   # last map 2 x 2: 8 values per channel
+    # three and five frames on tiny maps: a 128-pixel tile or a 32-pixel K chunk of the deepest levels holds three or more frames, and
+    # frames straddle tiles.  Seeds by the rule written in resnet_pose_grad_cases.py, the first from 78 on with both properties.
+    "narrow_n3_running": dict(filters=pgo.FILTERS, n=3, h=20, w=36, seed=78, batch_norm="running"),   # maps 10 x 18, 5 x 9, 3 x 5, 2 x 3, 1 x 2, 1 x 1, 1 x 1
+    "narrow_n5_running": dict(filters=pgo.FILTERS, n=5, h=21, w=43, seed=80, batch_norm="running"),   # maps 11 x 22, 6 x 11, 3 x 6, 2 x 3, 1 x 2, 1 x 1, 1 x 1
+    "narrow_n3_batch": dict(filters=pgo.FILTERS, n=3, h=33, w=260, seed=78, batch_norm="batch"),      # last map 1 x 3: 9 values per channel
 })
 
 

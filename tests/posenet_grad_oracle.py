@@ -106,6 +106,20 @@ def kink_check(masks, pres):
     return total
 
 
+KINK_NEAR = 5e-6     # of rms(z): where an fp32 run may land on the other side of 0 (half the forward's own 1e-5 error)
+
+
+def kink_room(pres):
+    """The property a model case's seed is picked for: no activation has more fp64 pre-activations within KINK_NEAR rms(z) of 0
+    than kink_check lets flip, so an fp32 run's few branch flips cannot exceed kink_check's share by bad luck.  -> the largest count."""
+    worst = 0
+    for i, z in enumerate(pres, 1):
+        count = int((z.double().abs() < KINK_NEAR * po.rms(z)).sum())
+        assert count <= max(1, int(KINK_SHARE * z.numel())), (i, count, z.numel())
+        worst = max(worst, count)
+    return worst
+
+
 def trainable(key):
     return key.endswith("conv.weight") or key.endswith("batch_norm.weight") or key.endswith("batch_norm.bias")
 

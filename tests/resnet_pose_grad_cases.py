@@ -27,6 +27,11 @@ MODEL.update({
     "narrow_34_batch": dict(NARROW, n_layer=34, n=2, h=130, w=136, seed=85, batch_norm="batch"),
     "full_18_running": dict(FULL, n_layer=18, n=2, h=64, w=96, seed=96, batch_norm="running"),
     "full_18_batch": dict(FULL, n_layer=18, n=2, h=256, w=256, seed=113, batch_norm="batch"),     # last map 2 x 2: 8 values per channel
+    # three and five frames on tiny maps (5 x 9 behind the pool, then 3 x 5, 2 x 3, 1 x 2 and the decoder's 1 x 1): a tile or a K chunk
+    # of the deepest levels holds three or more frames, and frames straddle tiles.  The first seeds from 114 on with (a) and (b).
+    "narrow_18_n3_running": dict(NARROW, n_layer=18, n=3, h=20, w=36, seed=114, batch_norm="running"),
+    "narrow_18_n5_running": dict(NARROW, n_layer=18, n=5, h=21, w=43, seed=115, batch_norm="running"),
+    "narrow_18_n3_batch": dict(NARROW, n_layer=18, n=3, h=33, w=260, seed=114, batch_norm="batch"),   # last map 1 x 3: 9 values per channel
 })
 
 

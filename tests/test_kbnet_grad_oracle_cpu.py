@@ -108,6 +108,18 @@ def test_every_case_is_well_conditioned(measured):
         assert kinks == 0, name      # kink_check holds for the reference alone: no fp32 branch differs from fp64's
 
 
+@pytest.mark.parametrize("name", ["tiny_n3", "tiny_n5"])
+def test_frame_axis_cases_keep_the_seed_rule(measured, name):
+    """The rule written in resnet_pose_grad_cases.py: (a) the oracle's own fp32 autograd under a third of the gate (measured: 1.3e-5
+    and 7.3e-6), (b) no activation with more fp64 pre-activations near 0 than kink_check lets flip."""
+    c = cases.MODEL[name]
+    assert c["n"] in (3, 5)
+    figure, where, kinks = measured[name]
+    assert 3.0 * figure <= kgo.TOL and kinks == 0, (name, figure, where, kinks)
+    pre = kgo.gradients(*cases.inputs(c), c["cfg"])["pre"]
+    kgo.kink_room(pre.values())
+
+
 def test_the_depth_mappings_gate_is_three_times_torchs_fp32_autograd():
     logits, g = cases.depth_map_inputs()
     assert float(logits.min()) == -30.0 and float(logits.max()) == 30.0 and torch.equal(logits, logits.float().double())

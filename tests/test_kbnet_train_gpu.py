@@ -108,6 +108,37 @@ def test_model_against_the_fp64_oracle(dev, name):
     _compare(name, got, want)
 
 
+def test_frame_order_leaves_the_gradients_inside_the_gate(dev):
+    """Five frames in another order (no frame keeps its place), the cotangent with them: every parameter gradient is a sum over the
+    frames in another order, so it stays within the gate of the SAME oracle result.  The input side moves with its frame: the
+    gradient with respect to the logits (a hook on the depth mapping's node), against cot * d depth / d logits of the oracle's fp64
+    logits -- the first data gradient of the backward pass, one row per pixel."""
+    c = cases.MODEL["tiny_n5"]
+    args = cases.inputs(c)
+    n = c["n"]
+    perm = torch.roll(torch.arange(n), 2)
+    inv = torch.argsort(perm)
+    assert not bool((perm == torch.arange(n)).any())
+    m = _model(dev, c, args[4:7])
+    depth, inner = m.forward(*[t[perm].to(dev) for t in args[:4]], return_inner=True)
+    seen = []
+    depth.grad_fn.register_hook(lambda grad_inputs, grad_outputs: seen.append(grad_inputs[0].detach().clone()))
+    (depth * args[7][perm].float().to(dev)).sum().backward()
+    got = _grads(m, c)
+    masks = kgo.masks_of({k: t.detach().cpu()[inv] for k, t in inner.items()})
+    want = kgo.gradients(*args, c["cfg"], masks=masks)
+    kgo.check_kinks(masks, want["pre"])
+    _depth_close(depth.detach().cpu()[inv], want["depth"])
+    _compare("tiny_n5, frames permuted", got, want)
+    assert len(seen) == 1 and tuple(seen[0].shape) == (n, 1, c["h"], c["w"])
+    dmin = c["cfg"].min_predict_depth
+    s = torch.sigmoid(want["logits"])
+    grad_logits = -args[7] * want["depth"] ** 2 / dmin * s * (1 - s)
+    f = kgo.fraction(seen[0].cpu()[inv], grad_logits)
+    print(f"tiny_n5, frames permuted: the logits' gradient at {f:.2e} of |b| + rms(b) (gate {kgo.TOL:.0e})")
+    assert f <= kgo.TOL
+
+
 def test_trainable_without_gradients_is_the_default_models_fused_forward(dev):
     c = cases.MODEL["full_width"]
     args = cases.inputs(c)

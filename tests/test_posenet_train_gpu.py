@@ -95,7 +95,8 @@ def test_narrow_model_against_the_references_autograd(dev, name):
     _running(name, m, gold, inputs[2], c["batch_norm"])
 
 
-@pytest.mark.parametrize("name", ["narrow_train_shape_running", "full_running", "full_batch"])
+@pytest.mark.parametrize("name", ["narrow_train_shape_running", "full_running", "full_batch", "narrow_n3_running", "narrow_n5_running",
+                                  "narrow_n3_batch"])
 def test_model_against_the_fp64_oracle(dev, name):
     c = cases.MODEL[name]
     if c["batch_norm"] == "batch":
@@ -106,6 +107,24 @@ def test_model_against_the_fp64_oracle(dev, name):
     print(f"{name}: {pgo.kink_check(masks, want['pre'])} activations on the other side of the kink than in fp64")
     _compare(name, got, want)
     _running(name, m, want, inputs[2], c["batch_norm"])
+
+
+def test_frame_order_leaves_the_gradients_inside_the_gate(dev):
+    """Five frames in another order (no frame keeps its place), the cotangent with them: every parameter gradient is a sum over the
+    frames in another order, so it stays within the gate of the SAME oracle result, and dof moves with its frame."""
+    c = cases.MODEL["narrow_n5_running"]
+    image0, image1, enc, dec, cot = cases.inputs(c)
+    perm = torch.roll(torch.arange(c["n"]), 2)
+    inv = torch.argsort(perm)
+    assert not bool((perm == torch.arange(c["n"])).any())
+    m = _model(dev, c, enc, dec, "running")
+    pose, dof, layers = m.forward(image0[perm].to(dev), image1[perm].to(dev), return_all=True)
+    (pose * cot[perm].float().to(dev)).sum().backward()
+    got = _grads(m, dof.detach().cpu()[inv])
+    masks = [(t.detach().cpu()[inv] > 0) for t in layers]
+    want = pgo.gradients(image0, image1, enc, dec, cot, batch_norm="running", masks=masks)
+    pgo.kink_check(masks, want["pre"])
+    _compare("narrow_n5_running, frames permuted", got, want)
 
 
 def test_defaults_are_unchanged(dev):

@@ -75,6 +75,23 @@ def test_every_case_is_well_conditioned(measured):
             assert cases.last_map_values(c) >= 8, name
 
 
+FRAME_AXIS = ["narrow_18_n3_running", "narrow_18_n5_running", "narrow_18_n3_batch"]     # the cases with three and five frames
+
+
+@pytest.mark.parametrize("name", FRAME_AXIS)
+def test_frame_axis_cases_keep_the_seed_rule(measured, name):
+    """The rule written in resnet_pose_grad_cases.py: (a) the oracle's own fp32 autograd under a third of the gate (measured: 1.0e-4,
+    8.9e-5 and 5.8e-5), (b) no activation with more fp64 pre-activations near 0 than kink_check lets flip."""
+    c = cases.MODEL[name]
+    assert c["n"] in (3, 5)
+    figure, where, kinks = measured[name]
+    assert 3.0 * figure <= rgo.TOL and kinks == 0, (name, figure, where, kinks)
+    image0, image1, enc, dec, _ = cases.inputs(c)
+    with torch.no_grad():
+        ref = rgo.forward(image0.double(), image1.double(), *po.to64(enc, dec), n_layer=c["n_layer"], batch_norm=c["batch_norm"])
+    rgo.pgo.kink_room(ref["pre"].values())
+
+
 def test_kink_check_accepts_the_fp32_branches_and_rejects_wrong_ones():
     c = cases.MODEL["narrow_34_running"]
     masks, indices = cases.fp32_branches(c)

@@ -125,7 +125,8 @@ def test_narrow_model_against_the_references_autograd(dev, name):
     _running(name, m, gold, inputs[2:4], c["batch_norm"])
 
 
-@pytest.mark.parametrize("name", ["narrow_34_running", "narrow_34_batch", "full_18_running", "full_18_batch"])
+@pytest.mark.parametrize("name", ["narrow_34_running", "narrow_34_batch", "full_18_running", "full_18_batch", "narrow_18_n3_running",
+                                  "narrow_18_n5_running", "narrow_18_n3_batch"])
 def test_model_against_the_fp64_oracle(dev, name):
     c = cases.MODEL[name]
     if c["batch_norm"] == "batch":
@@ -137,6 +138,24 @@ def test_model_against_the_fp64_oracle(dev, name):
     print(f"{name}: {kinks} activations / pool windows on the other side of the kink than in fp64")
     _compare(name, got, want)
     _running(name, m, want, inputs[2:4], c["batch_norm"])
+
+
+def test_frame_order_leaves_the_gradients_inside_the_gate(dev):
+    """Five frames in another order (no frame keeps its place), the cotangent with them: every parameter gradient is a sum over the
+    frames in another order, so it stays within the gate of the SAME oracle result, and dof moves with its frame."""
+    c = cases.MODEL["narrow_18_n5_running"]
+    image0, image1, enc, dec, cot = cases.inputs(c)
+    perm = torch.roll(torch.arange(c["n"]), 2)
+    inv = torch.argsort(perm)
+    assert not bool((perm == torch.arange(c["n"])).any())
+    m = _model(dev, c, enc, dec, "running")
+    pose, dof, layers, inner = m.forward(image0[perm].to(dev), image1[perm].to(dev), return_all=True, return_inner=True)
+    (pose * cot[perm].float().to(dev)).sum().backward()
+    got = _grads(m, dof.detach().cpu()[inv], c)
+    masks, indices = _branches(c, [t.detach().cpu()[inv] for t in layers], {k: t.detach().cpu()[inv] for k, t in inner.items()})
+    want = rgo.gradients(image0, image1, enc, dec, cot, n_layer=c["n_layer"], batch_norm="running", masks=masks, pool_indices=indices)
+    rgo.kink_check(masks, want["pre"], indices, want["pool_in"])
+    _compare("narrow_18_n5_running, frames permuted", got, want)
 
 
 def test_trainable_without_gradients_is_the_default_models_fused_forward(dev):

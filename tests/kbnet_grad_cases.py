@@ -39,6 +39,9 @@ MODEL.update({
     # frames straddle tiles.  Seeds by the rule written in resnet_pose_grad_cases.py, the first from 62 on with both properties.
     "tiny_n3": _case(KITTI.narrow(), 3, 17, 19, 62),   # maps 9 x 10, 5 x 5, 3 x 3, 2 x 2, 1 x 1
     "tiny_n5": _case(KITTI.narrow(), 5, 19, 35, 62),   # maps 10 x 18, 5 x 9, 3 x 5, 2 x 3, 1 x 2
+    # the extent of tests/grad_extent_cases.py inside a real backward pass: 71 806 pixels per full-resolution weight gradient, the
+    # split count at its 512-workgroup cap (449 splits of 5 chunks), a ragged last chunk and a chunk across the frame boundary
+    "wide_frame": _case(KITTI.narrow(), 2, 161, 223, 71),   # maps 81 x 112, 41 x 56, 21 x 28, 11 x 14, 6 x 7
 })
 
 

@@ -22,6 +22,7 @@ KBN_SRC_TENSOR, KBN_SRC_COORDS, KBN_SRC_XYZ, KBN_SRC_PAIR = 0, 1, 2, 3
 KBN_ACT_ELU, KBN_ACT_SIGMOID = 1, 2
 KBN_RESIZE_NONE, KBN_RESIZE_NEAREST = 0, 1
 KBN_MAX_SRC = 3
+KBN_ADAM_TABLE_CAPACITY, KBN_ADAM_PASS_ELEMENTS = 48, 524288   # tensors a kbn_adam_step launch carries; elements one pass of its widest grid covers
 ABI_VERSION = 11
 
 
@@ -45,6 +46,24 @@ class ConvSrc(C.Structure):
         ("kinv", C.c_void_p),
         ("absmax", C.c_void_p),
         ("scale", C.c_void_p),
+    ]
+
+
+class AdamTensor(C.Structure):
+    """Mirror of `kbn_adam_tensor` (include/kbnet_hip.h): one tensor of a kbn_adam_step call."""
+    _fields_ = [
+        ("param", C.c_void_p),
+        ("grad", C.c_void_p),
+        ("exp_avg", C.c_void_p),
+        ("exp_avg_sq", C.c_void_p),
+        ("numel", C.c_longlong),
+        ("weight_decay", C.c_float),
+        ("one_minus_beta1", C.c_float),
+        ("beta2", C.c_float),
+        ("one_minus_beta2", C.c_float),
+        ("step_size", C.c_float),
+        ("bc2_sqrt", C.c_float),
+        ("eps", C.c_float),
     ]
 
 
@@ -143,6 +162,7 @@ SIGNATURES = {
     "kbn_conv1x1s2_split_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "kbn_conv1x1s2_split_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "kbn_kb_xyz_s2_forward": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _F, _P, _L, _I, _P]),
+    "kbn_adam_step": (_I, [C.POINTER(AdamTensor), _I, _P]),
     "kbn_png_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),
     "kbn_png_decode": (_I, [_P, C.c_size_t, _P, C.c_size_t]),
     "kbn_png_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -25,7 +25,7 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, optim
 from ._lib import KbnError
 from .config import KBNetConfig
 
@@ -1522,10 +1522,16 @@ class KBNetModel(object):
             m.load_state_dict(sd, strict=True)
 
     def restore_model(self, checkpoint_path, optimizer=None):
-        """Loads a reference checkpoint (reference src/kbnet_model.py:378-406)."""
+        """Loads a reference checkpoint (reference src/kbnet_model.py:378-406).  With an `optimizer` (kb.optim.Adam or
+        torch.optim.Adam over this model's parameters, and the pose model's if the checkpoint was written with both groups) the
+        checkpoint's `optimizer_state_dict` is loaded into it: Adam's moments and step counts resume where they were saved.  An empty
+        dict -- what save_model(..., optimizer=None) writes -- leaves the optimizer as it is.  A dict that does not fit the optimizer
+        raises what load_state_dict raises (the reference swallows that error, src/kbnet_model.py:400-403, and resumes from zero
+        moments without a word)."""
         ckpt = torch.load(checkpoint_path, map_location=self.device)
         self.load_state_dicts(ckpt["sparse_to_dense_pool_state_dict"], ckpt["encoder_state_dict"],
                               ckpt["decoder_state_dict"])
+        optim.load_checkpoint_state(optimizer, ckpt)
         return ckpt.get("train_step", 0), optimizer
 
     def save_model(self, checkpoint_path, step=0, optimizer=None):

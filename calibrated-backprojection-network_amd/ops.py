@@ -8,6 +8,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import functools
+import struct
 from typing import List, Optional, Sequence
 
 import torch
@@ -2416,3 +2417,128 @@ def depth_map(logits: torch.Tensor, min_predict_depth: float, max_predict_depth:
     if logits.shape[1] != 1:
         raise KbnError(f"depth_map: logits must be N x 1 x H x W, got {tuple(logits.shape)}")
     return _DepthMap.apply(logits, float(min_predict_depth), float(max_predict_depth))
+
+
+# ------------------------------------------------------------------ the optimizer
+ADAM_TABLE_CAPACITY = _lib.KBN_ADAM_TABLE_CAPACITY   # tensors one launch of kbn_adam_step carries in its kernel arguments
+ADAM_PASS_ELEMENTS = _lib.KBN_ADAM_PASS_ELEMENTS     # elements of one tensor the widest grid covers before its stride loop repeats
+
+
+def _per_tensor(fn: str, value, name: str, count: int):
+    """`value` as one host number per tensor: a number for all of them, or a sequence of `count` numbers."""
+    if isinstance(value, torch.Tensor):
+        raise KbnError(f"{fn}: {name} must be a host number (or one per tensor), not a tensor")
+    if isinstance(value, (int, float)):
+        return [float(value)] * count
+    values = [float(v) for v in value]
+    if len(values) != count:
+        raise KbnError(f"{fn}: {name} has {len(values)} entries for {count} tensors")
+    return values
+
+
+_ADAM_RECORD = struct.Struct("@PPPPq7f4x")      # _lib.AdamTensor's layout: four pointers, numel, seven floats, padding to 72 bytes
+
+
+def _adam_refuse(fn: str, i: int, p, g, m, v, device):
+    """Raises for tensor i of an adam_step call, naming what is wrong with it (the call's checks found something)."""
+    for t, name in ((p, "params"), (g, "grads"), (m, "exp_avgs"), (v, "exp_avg_sqs")):
+        _require(t, f"{fn}: {name}[{i}]")
+        if t.device != device:
+            raise KbnError(f"{fn}: tensors live on different devices ({device} and {t.device})")
+        if t.shape != p.shape:
+            raise KbnError(f"{fn}: {name}[{i}] has shape {tuple(t.shape)}, params[{i}] {tuple(p.shape)}")
+        if name != "grads" and not t.is_contiguous():
+            raise KbnError(f"{fn}: {name}[{i}] must be dense (contiguous), got strides {t.stride()}: it is updated in place")
+    raise KbnError(f"{fn}: tensor {i} was refused")
+
+
+def adam_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+              exp_avg_sqs: Sequence[torch.Tensor], steps: Sequence[int], *, lr, betas, eps, weight_decay) -> None:
+    """One Adam step over a list of tensors, in place (kbn_adam_step; torch's _single_tensor_adam with L2 weight decay, no amsgrad, no
+    maximize, no decoupled decay).  Per element, in fp32:
+        g' = g + weight_decay * p;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g'^2;  p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+    with step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) computed here in fp64 from steps[i] = t >= 1, the number of THIS
+    step for tensor i (tensors may be at different steps).  lr, eps and weight_decay are host numbers, one for all tensors or a
+    sequence with one per tensor (param groups); betas a (beta1, beta2) pair or a sequence of pairs.
+
+    params[i], exp_avgs[i], exp_avg_sqs[i] (all written) and grads[i] (read) are fp32 tensors of one shape on one HIP device.
+    Parameters and states must be dense (contiguous; any storage offset -- a tensor that is not 16-byte aligned takes the kernel's
+    scalar path): KbnError otherwise, since a copy would not be updated.  A gradient that is not dense is copied.  Empty tensors are
+    skipped.  CPU tensors raise: there is no CPU fallback.  The work goes to torch's current stream of the tensors' device in
+    ceil(non-empty tensors / ADAM_TABLE_CAPACITY) launches, with no host synchronisation, no allocation and no copy (but that of a
+    gradient that is not dense); each launch is
+    one ops.PROFILE record ("adam_step", nbytes = 28 B an element: p, g, m, v read, p, m, v written).
+
+    THE VERSION CONTRACT.  The kernel writes the parameters through raw pointers, which torch's version counters do not see, and
+    the packed-weight caches (modules._PackedBlob, GraphedForward's re-pack before a replay) follow nothing but a parameter's
+    `_version`.  So this function bumps the version of every parameter it wrote (torch.autograd.graph.increment_version), and so
+    must anything else that writes a parameter through a pointer: without the bump every later forward runs on stale weights,
+    silently.  (The bump also makes autograd refuse a backward through a graph recorded before the step, as after torch's own
+    in-place update.)  Not capturable into a HIP graph: the bias corrections are host numbers."""
+    fn = "adam_step"
+    lists = [list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)]
+    count = len(lists[0])
+    steps = list(steps)
+    if any(len(x) != count for x in lists) or len(steps) != count:
+        raise KbnError(f"{fn}: params, grads, exp_avgs, exp_avg_sqs and steps must have one length, got "
+                       f"{[len(x) for x in lists] + [len(steps)]}")
+    if count == 0:
+        return
+    lrs, epss, wds = (_per_tensor(fn, v, k, count) for v, k in ((lr, "lr"), (eps, "eps"), (weight_decay, "weight_decay")))
+    betas = list(betas)
+    if len(betas) == 2 and all(isinstance(b, (int, float)) for b in betas):
+        betas = [betas] * count
+    if len(betas) != count:
+        raise KbnError(f"{fn}: betas has {len(betas)} entries for {count} tensors")
+    device = lists[0][0].device if isinstance(lists[0][0], torch.Tensor) else None
+    f32 = torch.float32
+    records = bytearray(_ADAM_RECORD.size * count)     # kbn_adam_tensor[count], packed in one call a tensor
+    written, keep, used, scalars = [], [], 0, {}     # keep: the dense copies of gradients, alive until the launches are enqueued
+    for i, (p, g, m, v) in enumerate(zip(*lists)):
+        try:
+            shape = p.shape
+            ok = (p.is_cuda and p.dtype is f32 and g.dtype is f32 and m.dtype is f32 and v.dtype is f32 and g.shape == shape
+                  and m.shape == shape and v.shape == shape and p.device == device and g.device == device and m.device == device
+                  and v.device == device and p.is_contiguous() and m.is_contiguous() and v.is_contiguous())
+        except AttributeError:
+            ok = False
+        if not ok:
+            _adam_refuse(fn, i, p, g, m, v, device)
+        numel = p.numel()
+        if numel == 0:
+            continue
+        if not g.is_contiguous():
+            g = g.contiguous()
+            keep.append(g)
+        t = int(steps[i])
+        if t < 1 or t != steps[i]:
+            raise KbnError(f"{fn}: steps[{i}] must be a whole number >= 1 (the number of this step), got {steps[i]!r}")
+        beta1, beta2 = betas[i]
+        key = (t, lrs[i], beta1, beta2)
+        sc = scalars.get(key)
+        if sc is None:
+            beta1, beta2 = float(beta1), float(beta2)
+            sc = scalars[key] = (1.0 - beta1, beta2, 1.0 - beta2, lrs[i] / (1.0 - beta1 ** t), (1.0 - beta2 ** t) ** 0.5)
+        try:
+            _ADAM_RECORD.pack_into(records, used * _ADAM_RECORD.size, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), numel,
+                                   wds[i], sc[0], sc[1], sc[2], sc[3], sc[4], epss[i])
+        except (struct.error, OverflowError):
+            raise KbnError(f"{fn}: a scalar of tensor {i} is outside the fp32 range (lr {lrs[i]}, eps {epss[i]}, weight_decay {wds[i]}, "
+                           f"step_size {sc[3]})") from None
+        used += 1
+        written.append(p)
+    if not used:
+        return
+    lib = _lib.load()
+    table = (_lib.AdamTensor * used).from_buffer(records)
+    with torch.cuda.device(device):
+        stream = _stream()
+        if PROFILE is None:
+            check(lib.kbn_adam_step(table, used, stream), "kbn_adam_step")
+        else:    # one entry-point call a launch, so that each record times one launch
+            for start in range(0, used, ADAM_TABLE_CAPACITY):
+                n = min(ADAM_TABLE_CAPACITY, used - start)
+                chunk = C.cast(C.byref(table, start * _ADAM_RECORD.size), C.POINTER(_lib.AdamTensor))
+                elements = sum(table[j].numel for j in range(start, start + n))
+                check(_launch("adam_step", 0.0, lambda: lib.kbn_adam_step(chunk, n, stream), nbytes=28.0 * elements), "kbn_adam_step")
+    torch.autograd.graph.increment_version(written)

@@ -20,7 +20,7 @@ from typing import List, Optional
 
 import torch
 
-from . import ops
+from . import ops, optim
 from ._lib import KbnError
 
 POSENET_FILTERS = (16, 32, 64, 128, 256, 256, 256)
@@ -289,9 +289,11 @@ class PoseModelBase(object):
             m.load_state_dict(sd, strict=True)
 
     def restore_model(self, checkpoint_path, optimizer=None):
-        """Loads a reference checkpoint (reference src/posenet_model.py:174-198)."""
+        """Loads a reference checkpoint (reference src/posenet_model.py:174-198); its non-empty `optimizer_state_dict` goes into
+        `optimizer` when one is given, and an error of load_state_dict propagates (KBNetModel.restore_model)."""
         ckpt = torch.load(checkpoint_path, map_location=self.device)
         self.load_state_dicts(ckpt["encoder_state_dict"], ckpt["decoder_state_dict"])
+        optim.load_checkpoint_state(optimizer, ckpt)
         return ckpt.get("train_step", 0), optimizer
 
     def save_model(self, checkpoint_path, step=0, optimizer=None):

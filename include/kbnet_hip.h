@@ -782,6 +782,38 @@ int kbn_kb_xyz_backward(const float* z, long long z_batch_stride, const float* c
 int kbn_depth_map_backward(const float* logits, const float* depth, const float* grad_depth, float* grad_logits, long long count,
                            float min_predict_depth, kbn_stream_t stream);
 
+/* ------------------------------------------------------------- the optimizer ----
+ * torch.optim.Adam as the reference's training loop constructs and steps it:
+ *   optimizer = torch.optim.Adam([{'params': parameters_depth_model, 'weight_decay': w_weight_decay_depth},
+ *                                 {'params': parameters_pose_model, 'weight_decay': w_weight_decay_pose}], lr=learning_rate)
+ *   ... optimizer.step()                                                  reference src/kbnet.py:360-369, 453
+ * kbn_adam_step applies ONE Adam step (L2 weight decay; no amsgrad, no maximize, no decoupled decay) to `count` fp32 tensors, each a
+ * run of `numel` contiguous floats, in place.  Per element, in fp32, in this order (torch's _single_tensor_adam):
+ *   g' = grad + weight_decay * param                              (skipped when weight_decay == 0)
+ *   exp_avg    = exp_avg + one_minus_beta1 * (g' - exp_avg)
+ *   exp_avg_sq = beta2 * exp_avg_sq + one_minus_beta2 * g' * g'
+ *   param      = param - step_size * exp_avg / (sqrt(exp_avg_sq) / bc2_sqrt + eps)
+ * with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) computed by the caller in fp64 for the tensor's own step
+ * count t.  `tensors` is a HOST array, read before the call returns; the records travel to the device in the kernel arguments,
+ * KBN_ADAM_TABLE_CAPACITY a launch, so the call issues ceil(records with numel > 0 / capacity) launches and nothing else: no
+ * device table, no copy, no allocation, no synchronisation.  Tensors whose four pointers are 16-byte aligned are processed four
+ * elements a thread; one pass of the widest grid covers KBN_ADAM_PASS_ELEMENTS elements of a tensor (longer ones loop).
+ * A record with numel == 0 is skipped (its pointers may be NULL).  KBN_ERR_INVALID_ARGUMENT for a NULL table, count < 1, numel < 0 or
+ * a NULL pointer in a record with numel > 0 -- checked for every record before anything is launched.  The four tensors of a record
+ * must not overlap each other or another record's. */
+#define KBN_ADAM_TABLE_CAPACITY 48
+#define KBN_ADAM_MAX_BLOCKS_X 512
+#define KBN_ADAM_PASS_ELEMENTS 524288 /* KBN_ADAM_MAX_BLOCKS_X blocks x 256 threads x 4 elements */
+typedef struct kbn_adam_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    long long numel;
+    float weight_decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps;
+} kbn_adam_tensor;
+int kbn_adam_step(const kbn_adam_tensor* tensors, int count, kbn_stream_t stream);
+
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:
  *   data_utils.load_image   Image.open(path).convert('RGB') -> float32   reference src/data_utils.py:58-85

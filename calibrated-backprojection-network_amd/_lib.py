@@ -23,6 +23,11 @@ KBN_ACT_ELU, KBN_ACT_SIGMOID = 1, 2
 KBN_RESIZE_NONE, KBN_RESIZE_NEAREST = 0, 1
 KBN_MAX_SRC = 3
 KBN_ADAM_TABLE_CAPACITY, KBN_ADAM_PASS_ELEMENTS = 48, 524288   # tensors a kbn_adam_step launch carries; elements one pass of its widest grid covers
+KBN_AUGMENT_ROLE_IMAGE, KBN_AUGMENT_ROLE_RANGE, KBN_AUGMENT_ROLE_VALIDITY = 0, 1, 2
+KBN_AUGMENT_RANGE_0_255, KBN_AUGMENT_RANGE_0_1, KBN_AUGMENT_RANGE_M1_1 = 0, 1, 2
+KBN_AUGMENT_NOISE_NONE, KBN_AUGMENT_NOISE_GAUSSIAN, KBN_AUGMENT_NOISE_UNIFORM = 0, 1, 2
+KBN_AUGMENT_STAGE_SELECT, KBN_AUGMENT_STAGE_APPLY = 1, 2
+KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames whose flags one launch carries; workspace bytes a frame and range map
 ABI_VERSION = 11
 
 
@@ -64,6 +69,22 @@ class AdamTensor(C.Structure):
         ("step_size", C.c_float),
         ("bc2_sqrt", C.c_float),
         ("eps", C.c_float),
+    ]
+
+
+class AugmentTensor(C.Structure):
+    """Mirror of `kbn_augment_tensor` (include/kbnet_hip.h): one tensor of a kbn_augment_forward call."""
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("stride_n", C.c_longlong),
+        ("stride_c", C.c_longlong),
+        ("stride_h", C.c_longlong),
+        ("stride_w", C.c_longlong),
+        ("channels", C.c_int),
+        ("role", C.c_int),
+        ("map_index", C.c_int),
+        ("reserved", C.c_int),
     ]
 
 
@@ -163,6 +184,8 @@ SIGNATURES = {
     "kbn_conv1x1s2_split_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "kbn_kb_xyz_s2_forward": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _F, _P, _L, _I, _P]),
     "kbn_adam_step": (_I, [C.POINTER(AdamTensor), _I, _P]),
+    "kbn_augment_workspace_bytes": (C.c_size_t, [C.POINTER(AugmentTensor), _I, _I, _I, _I]),
+    "kbn_augment_forward": (_I, [C.POINTER(AugmentTensor), _I, C.c_char_p, _I, _I, _I, _P, _P, C.c_size_t, _I, _I, _F, C.c_ulonglong, C.c_uint, _I, _P]),
     "kbn_png_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),
     "kbn_png_decode": (_I, [_P, C.c_size_t, _P, C.c_size_t]),
     "kbn_png_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _P]),

@@ -2542,3 +2542,109 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp
                 elements = sum(table[j].numel for j in range(start, start + n))
                 check(_launch("adam_step", 0.0, lambda: lib.kbn_adam_step(chunk, n, stream), nbytes=28.0 * elements), "kbn_adam_step")
     torch.autograd.graph.increment_version(written)
+
+
+# ------------------------------------------------------------------ the augmentation
+AUGMENT_FLIP_HORIZONTAL, AUGMENT_FLIP_VERTICAL, AUGMENT_REMOVE, AUGMENT_NOISE = 1, 2, 4, 8     # the bits of a frame's flags
+_AUGMENT_RECORD = struct.Struct("@PP4q4i")      # _lib.AugmentTensor's layout: two pointers, four strides, channels, role, map index, reserved
+_AUGMENT_RANGES = {(0.0, 255.0): _lib.KBN_AUGMENT_RANGE_0_255, (0.0, 1.0): _lib.KBN_AUGMENT_RANGE_0_1, (-1.0, 1.0): _lib.KBN_AUGMENT_RANGE_M1_1}
+_AUGMENT_NOISES = {"none": _lib.KBN_AUGMENT_NOISE_NONE, "gaussian": _lib.KBN_AUGMENT_NOISE_GAUSSIAN, "uniform": _lib.KBN_AUGMENT_NOISE_UNIFORM}
+
+
+def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], validity_maps: Sequence[torch.Tensor], flags: Sequence[int],
+            densities: Optional[torch.Tensor], *, normalized_image_range=(0, 255), noise_type: str = "none", noise_spread: float = 0.0,
+            seed: int = 0, call: int = 0):
+    """The device part of the reference's Transforms.transform (src/transforms.py:61-183) over three lists of N x C x H x W fp32
+    tensors (kbn_augment_forward, csrc/augment.hip).  Returns (images, range_maps, validity_maps) as lists of NEW dense tensors; no
+    input is written (the reference flips in place).
+
+    flags: one host integer a frame -- AUGMENT_FLIP_HORIZONTAL | AUGMENT_FLIP_VERTICAL (every tensor), AUGMENT_REMOVE | AUGMENT_NOISE
+    (range maps only).  Images are normalised to `normalized_image_range` ([0, 1]: x / 255; [-1, 1]: 2 (x / 255) - 1; [0, 255]: as
+    they came; anything else ValueError).  Removal: of the elements > 0 of frame b of a range map (count of them), the
+    k = trunc(fp32(densities[b]) * fp32(count)) with the smallest (key, element index in the source frame) become 0.  Noise, after
+    removal: out = (v + noise_spread * noise) * (v > 0), noise_type 'gaussian' or 'uniform' (anything else ValueError once a frame
+    has the bit).  Every random word is Philox4x32-10 of (seed; element, frame, call, purpose | map index << 8): the same
+    arguments give the same bits, and tests/transforms_oracle.py computes them on the host.
+
+    densities: an fp32 DEVICE tensor of N, needed when a frame has AUGMENT_REMOVE and there is a range map, else None.  It is read
+    on the device: the count and k never reach the host.  Inputs may be any views (a view that is not 16-byte aligned or whose rows
+    are not dense takes the kernel's scalar path); CPU tensors raise, there is no CPU fallback.  The call enqueues at most two
+    launches on torch's current stream of the tensors' device -- selection (ops.PROFILE record "augment_select") and apply
+    ("augment_apply", nbytes = 8 B an element) -- and, besides the outputs and (with AUGMENT_REMOVE) a workspace of the size of
+    two range maps (the candidate lists of the selection), allocates nothing, copies nothing from or to the host, and never waits
+    for the device: the flags travel in the kernel arguments."""
+    fn = "augment"
+    lists = [list(images), list(range_maps), list(validity_maps)]
+    rng = tuple(float(v) for v in normalized_image_range)
+    if rng not in _AUGMENT_RANGES:
+        raise ValueError("Unsupported normalization range: {}".format(list(normalized_image_range)))
+    names = ("images", "range_maps", "validity_maps")
+    first = None
+    for lst, name in zip(lists, names):     # what is wrong with a tensor is named before where it lives: a CPU box can test the refusals
+        for i, t in enumerate(lst):
+            if not isinstance(t, torch.Tensor):
+                raise KbnError(f"{fn}: {name}[{i}]: expected a tensor, got {type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise KbnError(f"{fn}: {name}[{i}]: expected float32, got {t.dtype}")
+            if t.dim() != 4:
+                raise ValueError("Unsupported number of dimensions: {}".format(t.dim()))
+            first = t if first is None else first
+            if t.shape[0] != first.shape[0] or t.shape[2:] != first.shape[2:] or t.shape[1] < 1:
+                raise KbnError(f"{fn}: {name}[{i}] has shape {tuple(t.shape)}, expected ({first.shape[0]}, c >= 1, {first.shape[2]}, "
+                               f"{first.shape[3]}) as the first tensor's")
+    if first is None:
+        return [], [], []
+    n, _, h, w = first.shape
+    flags = [int(f) for f in flags]
+    if len(flags) != n or any(f < 0 or f > 15 for f in flags):
+        raise KbnError(f"{fn}: flags must hold one value in 0..15 for each of the {n} frames, got {flags}")
+    any_remove = any(f & AUGMENT_REMOVE for f in flags) and bool(lists[1])
+    any_noise = any(f & AUGMENT_NOISE for f in flags) and bool(lists[1])
+    if noise_type not in ("gaussian", "uniform"):
+        if any_noise:
+            raise ValueError("Unsupported noise type: {}".format(noise_type))
+        noise_type = "none"     # never applied in this call
+    for lst, name in zip(lists, names):
+        for i, t in enumerate(lst):
+            _require(t, f"{fn}: {name}[{i}]")
+            if t.device != first.device:
+                raise KbnError(f"{fn}: tensors live on different devices ({first.device} and {t.device})")
+    device = first.device
+    if any_remove:
+        _require(densities, f"{fn}: densities")
+        if densities.device != device or tuple(densities.shape) != (n,) or not densities.is_contiguous():
+            raise KbnError(f"{fn}: densities must be a dense tensor of {n} numbers on {device}, got {tuple(densities.shape)} on {densities.device}")
+    count = sum(len(lst) for lst in lists)
+    records = bytearray(_AUGMENT_RECORD.size * count)
+    outs = [[], [], []]
+    used = elements = 0
+    for role, lst in enumerate(lists):
+        for i, t in enumerate(lst):
+            out = torch.empty(t.shape, device=device, dtype=torch.float32)
+            outs[role].append(out)
+            _AUGMENT_RECORD.pack_into(records, used * _AUGMENT_RECORD.size, t.data_ptr(), out.data_ptr(), *t.stride(), t.shape[1], role,
+                                      i if role == _lib.KBN_AUGMENT_ROLE_RANGE else 0, 0)
+            used += 1
+            elements += t.numel()
+    if n * h * w == 0:
+        return tuple(outs)
+    lib = _lib.load()
+    table = (_lib.AugmentTensor * used).from_buffer(records)
+    workspace = None
+    if any_remove:      # a 16-byte record and a list of 8 bytes an element for every frame of every range map
+        workspace = torch.empty(lib.kbn_augment_workspace_bytes(table, used, n, h, w) // 8, device=device, dtype=torch.int64)
+    with torch.cuda.device(device):
+        stream = _stream()
+
+        def run(stages):
+            return lib.kbn_augment_forward(table, used, bytes(flags), n, h, w, densities.data_ptr() if any_remove else None,
+                                           workspace.data_ptr() if any_remove else None, workspace.numel() * 8 if any_remove else 0,
+                                           _AUGMENT_RANGES[rng], _AUGMENT_NOISES[noise_type], float(noise_spread),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, stages, stream)
+        if PROFILE is None:
+            check(run(_lib.KBN_AUGMENT_STAGE_SELECT | _lib.KBN_AUGMENT_STAGE_APPLY), "kbn_augment_forward")
+        else:    # one entry-point call a stage, so that each record times one stage
+            if any_remove:
+                check(_launch("augment_select", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_SELECT)), "kbn_augment_forward")
+            check(_launch("augment_apply", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_APPLY), nbytes=8.0 * elements), "kbn_augment_forward")
+    return tuple(outs)

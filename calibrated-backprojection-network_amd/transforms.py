@@ -1,0 +1,96 @@
+"""The training step's augmentation: the reference's Transforms (src/transforms.py) over ops.augment (csrc/augment.hip), and the
+lines of the training loop in front of it (src/kbnet.py:403-422) as one call.
+
+    transforms = kb.transforms.Transforms(normalized_image_range=[0, 1], random_flip_type=['none'],
+                                          random_remove_points=[0.60, 0.70], random_noise_type='none', random_noise_spread=-1)
+    [image0, image1, image2], [sparse_depth0], [filtered_sparse_depth0, filtered_validity_map_depth0] = transforms.transform(
+        images_arr=[image0, image1, image2], range_maps_arr=[sparse_depth0],
+        validity_maps_arr=[filtered_sparse_depth0, filtered_validity_map_depth0], random_transform_probability=p)
+
+The per-frame decisions are drawn on the host with np.random.rand in the reference's order (`draw`), so the same np.random.seed
+makes the reference's decisions; the removal densities are `(max - min) * torch.rand(n, device=device) + min` as in the reference
+and stay on the device; which points go and what noise they get comes from Philox4x32-10 keyed by this object's seed and its count
+of transform() calls.  Differences from the reference, on purpose: the inputs are never written (the reference flips its arguments
+in place, which with range [0, 255] changes the caller's images); CPU tensors raise; 5-D inputs raise ValueError."""
+
+from __future__ import annotations
+
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class Transforms(object):
+
+    def __init__(self,
+                 normalized_image_range=[0, 255],
+                 random_flip_type=['none'],
+                 random_remove_points=[0.70, 0.70],
+                 random_noise_type=['none'],
+                 random_noise_spread=-1,
+                 seed: Optional[int] = None):
+        """The reference's arguments (src/transforms.py:23-59), and `seed`: the 64-bit key of the removal and noise draws;
+        None takes torch.initial_seed(), so that torch.manual_seed before the construction fixes it."""
+        self.normalized_image_range = normalized_image_range
+        self.do_random_horizontal_flip = 'horizontal' in random_flip_type
+        self.do_random_vertical_flip = 'vertical' in random_flip_type
+        self.do_random_remove_points = -1 not in random_remove_points
+        self.remove_points_range = random_remove_points
+        self.do_random_noise = random_noise_type != 'none' and random_noise_spread > 0
+        self.random_noise_type = random_noise_type
+        self.random_noise_spread = random_noise_spread
+        self.seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+        self.calls = 0      # transform() calls so far: a word of every draw's counter
+
+    def draw(self, n_batch: int, random_transform_probability: float = 0.50) -> List[int]:
+        """The host part of transform(): one flags value a frame (ops.AUGMENT_* bits), from np.random.rand(n_batch) drawn in the
+        reference's order -- the transform decision, then one more draw for each enabled branch: horizontal flip, vertical flip,
+        remove points, noise -- each `<= 0.5` and ANDed with the first."""
+        do_random_transform = np.random.rand(n_batch) <= random_transform_probability
+        flags = np.zeros(n_batch, dtype=np.int64)
+        for enabled, bit in ((self.do_random_horizontal_flip, ops.AUGMENT_FLIP_HORIZONTAL), (self.do_random_vertical_flip, ops.AUGMENT_FLIP_VERTICAL),
+                             (self.do_random_remove_points, ops.AUGMENT_REMOVE), (self.do_random_noise, ops.AUGMENT_NOISE)):
+            if enabled:
+                flags |= bit * np.logical_and(do_random_transform, np.random.rand(n_batch) <= 0.50)
+        return [int(f) for f in flags]
+
+    def transform(self,
+                  images_arr,
+                  range_maps_arr=[],
+                  validity_maps_arr=[],
+                  random_transform_probability=0.50):
+        """The reference's transform (src/transforms.py:61-183): lists of N x C x H x W fp32 device tensors in, the lists that are
+        not empty out (the one list itself when only one is)."""
+        first = images_arr[0] if len(images_arr) else next(iter(list(range_maps_arr) + list(validity_maps_arr)), None)
+        if not isinstance(first, torch.Tensor) or first.dim() != 4:
+            raise ValueError('Unsupported number of dimensions: {}'.format(first.dim() if isinstance(first, torch.Tensor) else None))
+        n_batch = first.shape[0]
+        flags = self.draw(n_batch, random_transform_probability)
+        densities = None
+        if self.do_random_remove_points:    # drawn whether or not a frame is flagged, as the reference does: torch's stream stays in step
+            remove_points_min, remove_points_max = self.remove_points_range
+            densities = (remove_points_max - remove_points_min) * torch.rand(n_batch, device=first.device) + remove_points_min
+        call = self.calls
+        self.calls += 1
+        outputs = ops.augment(images_arr, range_maps_arr, validity_maps_arr, flags, densities,
+                              normalized_image_range=self.normalized_image_range, noise_type=self.random_noise_type,
+                              noise_spread=self.random_noise_spread, seed=self.seed, call=call)
+        outputs = [o for o in outputs if len(o) > 0]
+        return outputs[0] if len(outputs) == 1 else outputs
+
+
+def train_inputs(transforms: Transforms, image0, image1, image2, sparse_depth0, random_transform_probability,
+                 kernel_size: int = 7, threshold: float = 1.5):
+    """Reference src/kbnet.py:403-422 in one call: the validity map of the sparse depth, OutlierRemoval.remove_outliers
+    (ops.preprocess), then transforms.transform over (images, [sparse_depth0], [filtered_sparse_depth0, filtered_validity_map_depth0]).
+    Returns (image0, image1, image2, sparse_depth0, filtered_sparse_depth0, filtered_validity_map_depth0)."""
+    _, filtered_validity_map_depth0, filtered_sparse_depth0 = ops.preprocess(None, sparse_depth0, kernel_size=kernel_size, threshold=threshold)
+    [image0, image1, image2], [sparse_depth0], [filtered_sparse_depth0, filtered_validity_map_depth0] = transforms.transform(
+        images_arr=[image0, image1, image2],
+        range_maps_arr=[sparse_depth0],
+        validity_maps_arr=[filtered_sparse_depth0, filtered_validity_map_depth0],
+        random_transform_probability=random_transform_probability)
+    return image0, image1, image2, sparse_depth0, filtered_sparse_depth0, filtered_validity_map_depth0

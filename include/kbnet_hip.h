@@ -814,6 +814,57 @@ typedef struct kbn_adam_tensor {
 } kbn_adam_tensor;
 int kbn_adam_step(const kbn_adam_tensor* tensors, int count, kbn_stream_t stream);
 
+/* ------------------------------------------------- the training step's augmentation ----
+ *   [images, depths, validity] = transforms.transform(images_arr=..., range_maps_arr=..., validity_maps_arr=...,
+ *                                                     random_transform_probability=...)     reference src/kbnet.py:411-422
+ * kbn_augment_forward does the device part of the reference's Transforms.transform (src/transforms.py:61-183) for `count` fp32
+ * tensors of n frames of channels x height x width elements: src (any non-negative element strides) is read, dst (dense) is
+ * written, nothing else.  flags[n] is a HOST array, a nibble a frame, drawn by the caller: bit 0 horizontal flip, bit 1 vertical
+ * flip (every tensor), bit 2 remove points, bit 3 noise (range maps only).  By role:
+ *   image      normalization KBN_AUGMENT_RANGE_0_1: x / 255; _M1_1: 2 (x / 255) - 1, one rounding for the subtraction; _0_255: x
+ *   range      remove: of the frame's elements > 0 (count of them, over all channels), the k = trunc(fp32(densities[b]) *
+ *              fp32(count)) with the smallest (key, source element index) become 0; then noise: out = (v + spread * noise) *
+ *              (v > 0 ? 1 : 0), each operation rounded on its own
+ *   validity   a copy
+ * Random words come from Philox4x32-10 with key = (low, high word of `seed`) and counter = (element index in the SOURCE frame,
+ * frame index, `call`, purpose | map_index << 8): purpose 0 is the removal key (word 0), purpose 1 the noise -- uniform:
+ * (w0 >> 8) 2^-24 - 0.5; gaussian: sqrtf(-2 logf(((w0 >> 8) + 1) 2^-24)) cosf(2 pi (w1 >> 8) 2^-24).
+ * densities[n] is DEVICE memory; count and k never reach the host.  `stages`: KBN_AUGMENT_STAGE_SELECT finds each flagged frame's
+ * threshold into `workspace` (kbn_augment_workspace_bytes(...) bytes, 8-byte aligned: first KBN_AUGMENT_WORKSPACE_RECORD_BYTES a
+ * frame and range map, in the order of the range maps in `tensors` -- words key, index, k, count -- then a list of 8 bytes an
+ * element for the candidates of each), KBN_AUGMENT_STAGE_APPLY writes the outputs and reads the thresholds; pass both for the
+ * whole operation (a caller that times the stages passes them one by one, with the same arguments).  The records and flags travel
+ * in the kernel arguments: launches only, no copy, no allocation, no synchronisation.  densities and workspace may be NULL when
+ * no frame has bit 2 or no tensor is a range map.  KBN_ERR_INVALID_ARGUMENT for NULL pointers, zero sizes, a flag above 15, bit 3
+ * with KBN_AUGMENT_NOISE_NONE; KBN_ERR_WORKSPACE for a workspace that is too small; KBN_ERR_UNSUPPORTED for a frame of 2^31
+ * elements or more -- all checked before anything is launched. */
+#define KBN_AUGMENT_ROLE_IMAGE 0
+#define KBN_AUGMENT_ROLE_RANGE 1
+#define KBN_AUGMENT_ROLE_VALIDITY 2
+#define KBN_AUGMENT_RANGE_0_255 0
+#define KBN_AUGMENT_RANGE_0_1 1
+#define KBN_AUGMENT_RANGE_M1_1 2
+#define KBN_AUGMENT_NOISE_NONE 0
+#define KBN_AUGMENT_NOISE_GAUSSIAN 1
+#define KBN_AUGMENT_NOISE_UNIFORM 2
+#define KBN_AUGMENT_STAGE_SELECT 1
+#define KBN_AUGMENT_STAGE_APPLY 2
+#define KBN_AUGMENT_MAX_FRAMES 512 /* frames whose flags one launch carries; longer batches take more launches */
+#define KBN_AUGMENT_WORKSPACE_RECORD_BYTES 16
+typedef struct kbn_augment_tensor {
+    const float* src;
+    float* dst;
+    long long stride_n, stride_c, stride_h, stride_w; /* of src, in elements */
+    int channels;
+    int role;      /* KBN_AUGMENT_ROLE_* */
+    int map_index; /* range maps: the map's index among the call's range maps (a word of the random counter) */
+    int reserved;
+} kbn_augment_tensor;
+size_t kbn_augment_workspace_bytes(const kbn_augment_tensor* tensors, int count, int n, int height, int width); /* 0 for bad arguments */
+int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
+                        const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
+                        float noise_spread, unsigned long long seed, unsigned call, int stages, kbn_stream_t stream);
+
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:
  *   data_utils.load_image   Image.open(path).convert('RGB') -> float32   reference src/data_utils.py:58-85

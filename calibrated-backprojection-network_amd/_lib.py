@@ -28,6 +28,7 @@ KBN_AUGMENT_RANGE_0_255, KBN_AUGMENT_RANGE_0_1, KBN_AUGMENT_RANGE_M1_1 = 0, 1, 2
 KBN_AUGMENT_NOISE_NONE, KBN_AUGMENT_NOISE_GAUSSIAN, KBN_AUGMENT_NOISE_UNIFORM = 0, 1, 2
 KBN_AUGMENT_STAGE_SELECT, KBN_AUGMENT_STAGE_APPLY = 1, 2
 KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames whose flags one launch carries; workspace bytes a frame and range map
+KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_forward launch carries
 ABI_VERSION = 11
 
 
@@ -85,6 +86,18 @@ class AugmentTensor(C.Structure):
         ("role", C.c_int),
         ("map_index", C.c_int),
         ("reserved", C.c_int),
+    ]
+
+
+class TrainFrame(C.Structure):
+    """Mirror of `kbn_train_frame` (include/kbnet_hip.h): one frame of a kbn_unpack_train_frames_forward call."""
+    _fields_ = [
+        ("image_offset", C.c_longlong),
+        ("depth_offset", C.c_longlong),
+        ("height", C.c_int),
+        ("raw_width", C.c_int),
+        ("y_start", C.c_int),
+        ("x_start", C.c_int),
     ]
 
 
@@ -193,6 +206,7 @@ SIGNATURES = {
     "kbn_png_encode_gray16_bound": (C.c_size_t, [_I, _I]),
     "kbn_png_encode_gray16": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
     "kbn_unpack_frames_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "kbn_unpack_train_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(TrainFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -15,16 +15,23 @@ src/data_utils.py:58-152).  At > 1000 frames/s per GPU that loader is the bottle
 
 `load_image`, `load_depth`, `load_image_triplet` mirror the reference functions of the same names
 (numpy in, numpy out) on top of the same decoder.
+
+Training (`TrainingFrameLoader`, in place of a `DataLoader` over `datasets.KBNetTrainingDataset`, reference
+src/datasets.py:161-228, src/kbnet.py:134-144) takes the same road with all three images of a triplet, frames of
+different raw sizes in one batch and the reference's random crop: `draw_crop` makes the reference's np.random
+decisions on the host, `kbn_unpack_train_frames_forward` cuts every frame's crop out of its raw bytes on the device.
+`random_crop` is the reference-named NumPy function on top of `draw_crop`.
 """
 
 from __future__ import annotations
 
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+import torch.utils.data
 
 from . import _lib, ops
 from ._lib import KbnError, check
@@ -260,8 +267,236 @@ class InferenceFrameLoader:
             image, depth, k, done = pending.pop(0).result()
             if b + self.prefetch < nb:
                 pending.append(self._driver.submit(self._submit, b + self.prefetch))
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(done)
-            for t in (image, depth, k):
-                t.record_stream(cur)
-            yield image, depth, k
+            yield _hand_over(self.device, done, (image, depth, k))
+
+
+def _hand_over(device, done, tensors):
+    """A batch produced on a loader's copy stream, for the consumer's current stream: that stream waits for the batch's event, and
+    the caching allocator learns that it uses the tensors (they were allocated on the copy stream)."""
+    cur = torch.cuda.current_stream(device)
+    cur.wait_event(done)
+    for t in tensors:
+        t.record_stream(cur)
+    return tensors
+
+
+# --------------------------------------------------------------------------- the training set
+def draw_crop(o_height: int, o_width: int, shape, crop_type=("none",)) -> Tuple[int, int]:
+    """(y_start, x_start) of the reference's random_crop (src/datasets.py:92-141) for an o_height x o_width frame: the same
+    np.random calls in the same order, so the same np.random.seed gives the reference's crops.  The centre by default;
+    'horizontal': randint over the anchors 0, 0.5, 1 when 'anchored', else over [0, d_width); 'bottom' takes the lowest crop and
+    draws nothing; otherwise 'vertical' moves 30 % of the crops, over the anchors 0.5, 1 or over [0, d_height).  As in the
+    reference an unanchored crop at the raw size raises NumPy's ValueError (randint(0, 0)).  Unlike the reference, which returns a
+    short slice, a crop larger than the frame raises KbnError."""
+    n_height, n_width = (int(v) for v in shape)
+    d_height, d_width = int(o_height) - n_height, int(o_width) - n_width
+    if d_height < 0 or d_width < 0:
+        raise KbnError(f"draw_crop: a {n_height} x {n_width} crop does not fit a {o_height} x {o_width} frame")
+    y_start, x_start = d_height // 2, d_width // 2
+    if "horizontal" in crop_type:
+        if "anchored" in crop_type:
+            widths = [anchor * d_width for anchor in (0.0, 0.50, 1.0)]
+            x_start = int(widths[np.random.randint(low=0, high=len(widths))])
+        else:
+            x_start = np.random.randint(low=0, high=d_width)
+    if "bottom" in crop_type:
+        y_start = d_height
+    elif "vertical" in crop_type and np.random.rand() <= 0.30:
+        if "anchored" in crop_type:
+            heights = [anchor * d_height for anchor in (0.50, 1.0)]
+            y_start = int(heights[np.random.randint(low=0, high=len(heights))])
+        else:
+            y_start = np.random.randint(low=0, high=d_height)
+    return int(y_start), int(x_start)
+
+
+def _crop_intrinsics(intrinsics: np.ndarray, y_start: int, x_start: int) -> np.ndarray:
+    """The reference's expression (src/datasets.py:152-154), evaluated as NumPy evaluates it there (the list becomes a float64
+    array; adding 0.0 to the other seven entries turns a -0.0 into 0.0); the caller casts to float32."""
+    return intrinsics + [[0.0, 0.0, -x_start],
+                         [0.0, 0.0, -y_start],
+                         [0.0, 0.0, 0.0]]
+
+
+def random_crop(inputs, shape, intrinsics=None, crop_type=["none"]):
+    """reference src/datasets.py:74-158: every C x H x W array of `inputs` cropped to `shape` at draw_crop's position (the first
+    array gives the frame's size) and, if given, the 3 x 3 intrinsics moved with it."""
+    _, o_height, o_width = inputs[0].shape
+    y_start, x_start = draw_crop(o_height, o_width, shape, crop_type)
+    y_end, x_end = y_start + shape[0], x_start + shape[1]
+    outputs = [T[:, y_start:y_end, x_start:x_end] for T in inputs]
+    if intrinsics is not None:
+        return outputs, _crop_intrinsics(intrinsics, y_start, x_start)
+    return outputs
+
+
+def _align16(v: int) -> int:
+    return (v + 15) & ~15
+
+
+class TrainingFrameLoader:
+    """Iterates `(image0, image1, image2, sparse_depth0, intrinsics)` device batches -- images N x 3 x h x w in 0..255, depth
+    N x 1 x h x w, intrinsics N x 3 x 3 -- over the files `datasets.KBNetTrainingDataset` reads (the same first five constructor
+    arguments, reference src/datasets.py:181-197): what the reference's
+    `DataLoader(KBNetTrainingDataset(...), batch_size, shuffle, drop_last=False)` yields after `.to(device)` (src/kbnet.py:134-144).
+
+    Each `iter()` is one epoch.  Its order is drawn when it starts: file order, or with `shuffle` what
+    `torch.utils.data.RandomSampler(range(n), generator=generator)` yields.  The crops are drawn with `draw_crop` from np.random
+    on the ITERATING thread, batch by batch in epoch order and sample by sample inside a batch, just before the batch goes to the
+    pool: they do not depend on the pool's timing, and under np.random.seed(s) with shuffle=False the batches are the reference
+    dataset's samples in index order.  Raw sizes come from the PNG headers (the first 33 bytes of a file, read once).
+
+    The pipeline is InferenceFrameLoader's: files are read by a thread pool, decoded by the library (`decode_png_batch`) straight
+    into PINNED staging -- frames may differ in size, so each sits at its own 16-byte-aligned offset of a flat buffer -- the used
+    prefix of each buffer crosses PCIe as raw bytes in one asynchronous copy on a side stream, and `ops.unpack_train_frames`
+    splits, crops and converts there.  `prefetch` batches are in flight.  Without a crop (`shape` None or not positive) the frames of
+    a batch must have one size.  An error found while a batch is prepared is raised when that batch is due.  One epoch at a time:
+    `iter()` first waits for what an epoch that was left early still has in flight."""
+
+    def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str], intrinsics_paths: Sequence[str],
+                 shape=None, random_crop_type=["none"], batch_size: int = 8, shuffle: bool = True,
+                 device: Optional[torch.device] = None, workers: int = 8, prefetch: int = 4, generator=None):
+        what = "TrainingFrameLoader"
+        self.n_sample = len(image_paths)
+        if len(sparse_depth_paths) != self.n_sample or len(intrinsics_paths) != self.n_sample:
+            raise KbnError(f"{what}: {self.n_sample} image, {len(sparse_depth_paths)} sparse depth and {len(intrinsics_paths)} intrinsics paths")
+        if device is None or torch.device(device).type != "cuda":
+            raise KbnError(f"{what}: a CUDA/HIP device is required (no CPU fallback)")
+        if int(batch_size) < 1:
+            raise KbnError(f"{what}: batch_size {batch_size}")
+        self.image_paths, self.sparse_depth_paths = list(image_paths), list(sparse_depth_paths)
+        self.intrinsics_paths = list(intrinsics_paths)
+        self.shape = shape
+        self.random_crop_type = random_crop_type
+        self.batch_size = int(batch_size)
+        self.shuffle = bool(shuffle)
+        self.generator = generator
+        self.device = torch.device(device)
+        self.workers = max(1, min(16, int(workers)))             # file-read threads, and decode threads per batch (inside the library)
+        self.pool = ThreadPoolExecutor(max_workers=self.workers)
+        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self.prefetch = max(1, int(prefetch))                    # batches decoded concurrently, each in its own staging set
+        self._driver = ThreadPoolExecutor(max_workers=min(16, self.prefetch))
+        self._stage: List[Optional[dict]] = [None] * (self.prefetch + 1)
+        self._headers: List[Optional[tuple]] = [None] * self.n_sample
+        self._pending: list = []
+        self._serial = 0                                         # batches submitted so far: picks the staging set
+
+    @property
+    def do_random_crop(self) -> bool:
+        return self.shape is not None and all([x > 0 for x in self.shape])      # reference src/datasets.py:193-194
+
+    def __len__(self):
+        return (self.n_sample + self.batch_size - 1) // self.batch_size
+
+    # -- on the iterating thread: the batch's raw sizes, its checks and its crops --
+    def _header(self, i: int):
+        if self._headers[i] is None:
+            heads = []
+            for path in (self.image_paths[i], self.sparse_depth_paths[i]):
+                with open(path, "rb") as f:
+                    heads.append(png_info(f.read(33)))           # signature + IHDR
+            self._headers[i] = tuple(heads)
+        return self._headers[i]
+
+    def _plan(self, idx: Sequence[int]):
+        """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped."""
+        heads = [self._header(i) for i in idx]
+        (_, _, c, bits), (_, _, cd, dbits) = heads[0]
+        if bits != 8 or cd != 1:
+            raise KbnError(f"TrainingFrameLoader: expected 8-bit images and single-channel depth PNGs ({self.image_paths[idx[0]]}, {self.sparse_depth_paths[idx[0]]})")
+        sizes = []
+        for i, ((wraw, hraw, ci, bi), (wd, hd, cdi, dbi)) in zip(idx, heads):
+            if (ci, bi, cdi, dbi) != (c, 8, 1, dbits):
+                raise KbnError(f"TrainingFrameLoader: the frames of a batch must have one format: {self.image_paths[i]} has {ci} channels of {bi} bits "
+                               f"and {cdi}-channel depth of {dbi} bits, {self.image_paths[idx[0]]} has {c} of 8 and 1 of {dbits}")
+            if wraw % 3:
+                raise ValueError("array split does not result in an equal division")     # np.split in the reference's load_image_triplet
+            if (hd, wd) != (hraw, wraw // 3):
+                raise KbnError(f"TrainingFrameLoader: depth map {self.sparse_depth_paths[i]} is {hd} x {wd}, image {self.image_paths[i]} is {hraw} x {wraw // 3}")
+            sizes.append((hraw, wraw // 3))
+        if self.do_random_crop:
+            shape = (int(self.shape[0]), int(self.shape[1]))
+            starts = [draw_crop(hh, ww, shape, self.random_crop_type) for hh, ww in sizes]
+        else:
+            shape = sizes[0]
+            for i, size in zip(idx, sizes):
+                if size != shape:
+                    raise KbnError(f"TrainingFrameLoader: without a crop shape the frames of a batch must have one size: {self.image_paths[i]} is "
+                                   f"{size[0]} x {size[1]}, {self.image_paths[idx[0]]} is {shape[0]} x {shape[1]}")
+            starts = [(0, 0)] * len(idx)
+        return [(i, hh, ww, y, x) for i, (hh, ww), (y, x) in zip(idx, sizes, starts)], shape, c, dbits, self.do_random_crop
+
+    # -- on a driver thread: read, decode into pinned memory, async H2D + unpack on the copy stream --
+    def _staging(self, slot: int, image_bytes: int, depth_bytes: int, frames: int):
+        st = self._stage[slot]
+        if st is None:
+            st = self._stage[slot] = {"image": None, "depth": None, "k": None, "done": None}
+        if st["done"] is not None:
+            st["done"].synchronize()      # the copies that last used this staging set: it is not reused, let alone replaced, before
+        for name, need in (("image", image_bytes), ("depth", depth_bytes)):
+            if st[name] is None or st[name].numel() < need:
+                st[name] = torch.empty(need + need // 8, dtype=torch.uint8).pin_memory()     # some room: the next batch's frames differ a little
+        if st["k"] is None or st["k"].shape[0] < frames:
+            st["k"] = torch.empty((frames, 3, 3), dtype=torch.float32).pin_memory()
+        return st
+
+    def _submit(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool):
+        nb = len(plan)
+        idx = [p[0] for p in plan]
+        files = list(self.pool.map(_read, [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]))
+        img_files, dep_files = files[:nb], files[nb:]
+        frames, img_at, dep_at = [], 0, 0
+        for j, (i, hraw, w, y, x) in enumerate(plan):
+            if png_info(img_files[j]) != (3 * w, hraw, c, 8) or png_info(dep_files[j]) != (w, hraw, 1, dbits):
+                raise KbnError(f"TrainingFrameLoader: {self.image_paths[i]} or {self.sparse_depth_paths[i]} changed since its header was read")
+            frames.append((img_at, dep_at, hraw, w, y, x))
+            img_at = _align16(img_at + hraw * 3 * w * c)
+            dep_at = _align16(dep_at + hraw * w * (dbits // 8))
+        st = self._staging(slot, img_at, dep_at, max(nb, self.batch_size))
+        img_np, dep_np, k_np = st["image"].numpy(), st["depth"].numpy(), st["k"].numpy()
+        for j, (i, hraw, w, y, x) in enumerate(plan):
+            k = np.load(self.intrinsics_paths[i]).astype(np.float32)
+            k_np[j] = (_crop_intrinsics(k, y, x) if cropped else k).astype(np.float32)
+        outs = [img_np[f[0]:f[0] + f[2] * 3 * f[3] * c] for f in frames] + [dep_np[f[1]:f[1] + f[2] * f[3] * (dbits // 8)] for f in frames]
+        # one library call decodes the whole batch on its own threads (images first: they are the long poles)
+        decode_png_batch(img_files + dep_files, outs, threads=self.workers)
+        with torch.cuda.stream(self.copy_stream):
+            img_d = st["image"][:img_at].to(self.device, non_blocking=True)
+            dep_d = st["depth"][:dep_at].to(self.device, non_blocking=True)
+            k_d = st["k"][:nb].to(self.device, non_blocking=True)
+            batch = ops.unpack_train_frames(img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,)
+            done = torch.cuda.Event()
+            done.record(self.copy_stream)
+        st["done"] = done
+        return batch, done
+
+    def _enqueue(self, idx: Sequence[int]):
+        """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn."""
+        slot = self._serial % (self.prefetch + 1)
+        self._serial += 1
+        try:
+            plan = self._plan(idx)
+        except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
+            failed: Future = Future()
+            failed.set_exception(e)
+            return failed
+        return self._driver.submit(self._submit, slot, *plan)
+
+    def __iter__(self):
+        for f in self._pending:      # batches of an epoch that was left early still own staging sets
+            f.exception()
+        if self.shuffle:
+            order = list(torch.utils.data.RandomSampler(range(self.n_sample), generator=self.generator))
+        else:
+            order = list(range(self.n_sample))
+        batches = [order[lo:lo + self.batch_size] for lo in range(0, self.n_sample, self.batch_size)]
+        self._pending = pending = [self._enqueue(batches[b]) for b in range(min(self.prefetch, len(batches)))]
+        return self._epoch(batches, pending)
+
+    def _epoch(self, batches, pending):
+        for b in range(len(batches)):
+            batch, done = pending.pop(0).result()
+            if b + self.prefetch < len(batches):
+                pending.append(self._enqueue(batches[b + self.prefetch]))
+            yield _hand_over(self.device, done, batch)

@@ -1262,6 +1262,71 @@ def unpack_frames(image_u8, depth_raw, width: Optional[int] = None, x_offset: in
     return image, depth
 
 
+_TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
+
+
+def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16):
+    """The decoded bytes of a batch of image triplets and depth maps on the device -> (image0, image1, image2, sparse_depth0): what
+    the reference's KBNetTrainingDataset.__getitem__ returns (src/datasets.py:199-225), batched -- the images (t, t-1, t+1; the
+    middle, left and right third of the triplet) N x 3 x h x w float32 in 0..255, the depth N x 1 x h x w float32 = sample / 256
+    (kbn_unpack_train_frames_forward, csrc/unpack_train.hip: one launch per _lib.KBN_UNPACK_TRAIN_MAX_FRAMES frames).
+
+    images_u8 / depths_u8: packed 1-d uint8 device buffers.  frames: one (image_offset, depth_offset, H, W, y_start, x_start) a
+    frame -- the byte offsets of its H x 3 W x channels triplet and of its H x W depth samples (uint16 in host byte order for
+    depth_bits 16, uint8 for 8) in the two buffers, and where its crop starts inside each third.  Frames may differ in size;
+    shape = (h, w) is the crop of all of them (output pixel (y, x) is raw pixel (y_start + y, x_start + x)).  channels in 1, 3, 4
+    (gray is replicated, alpha dropped).  What is wrong with a frame raises KbnError naming it; CPU tensors raise, there is no
+    CPU fallback.  The records travel in the kernel arguments: nothing is allocated but the outputs, nothing copied, no wait."""
+    fn = "unpack_train_frames"
+    h, w = (int(v) for v in shape)
+    channels, depth_bits = int(channels), int(depth_bits)
+    if h < 1 or w < 1:
+        raise KbnError(f"{fn}: the crop shape must be positive, got {h} x {w}")
+    if channels not in (1, 3, 4):
+        raise KbnError(f"{fn}: image channels must be 1, 3 or 4, got {channels}")
+    if depth_bits not in (8, 16):
+        raise KbnError(f"{fn}: depth samples must have 8 or 16 bits, got {depth_bits}")
+    frames = [tuple(int(v) for v in f) for f in frames]
+    n = len(frames)
+    if n < 1:
+        raise KbnError(f"{fn}: no frames")
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise KbnError(f"{fn}: {name}: expected a dense 1-d uint8 tensor")
+    records = bytearray(_TRAIN_FRAME_RECORD.size * n)
+    for i, f in enumerate(frames):
+        if len(f) != 6:
+            raise KbnError(f"{fn}: frame {i}: expected (image_offset, depth_offset, H, W, y_start, x_start), got {f}")
+        io, do, H, W, y, x = f
+        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
+            raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
+        if y < 0 or y + h > H or x < 0 or x + w > W:
+            raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
+        if io < 0 or io + H * 3 * W * channels > images_u8.numel():
+            raise KbnError(f"{fn}: frame {i}: its {H} x {3 * W} x {channels} triplet at byte {io} leaves the image buffer of {images_u8.numel()} bytes")
+        if do < 0 or do % (depth_bits // 8) or do + H * W * (depth_bits // 8) > depths_u8.numel():
+            raise KbnError(f"{fn}: frame {i}: its {H} x {W} depth map of {depth_bits}-bit samples at byte {do} is misaligned or leaves "
+                           f"the depth buffer of {depths_u8.numel()} bytes")
+        _TRAIN_FRAME_RECORD.pack_into(records, i * _TRAIN_FRAME_RECORD.size, io, do, H, 3 * W, y, x)
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not t.is_cuda:
+            raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+    device = images_u8.device
+    if depths_u8.device != device:
+        raise KbnError(f"{fn}: tensors live on different devices ({device} and {depths_u8.device})")
+    image0, image1, image2 = (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(3))
+    depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
+    lib = _lib.load()
+    table = (_lib.TrainFrame * n).from_buffer(records)
+    with torch.cuda.device(device):
+        check(_launch("unpack_train_frames", 0.0,
+                      lambda: lib.kbn_unpack_train_frames_forward(images_u8.data_ptr(), images_u8.numel(), depths_u8.data_ptr(), depths_u8.numel(),
+                                                                  table, n, h, w, channels, depth_bits, image0.data_ptr(), image1.data_ptr(),
+                                                                  image2.data_ptr(), depth.data_ptr(), _stream()),
+                      nbytes=float(n * h * w) * (3 * channels + depth_bits // 8 + 40)), "kbn_unpack_train_frames_forward")
+    return image0, image1, image2, depth
+
+
 @_on_tensor_device
 def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate_depth: float,
                  max_evaluate_depth: float):

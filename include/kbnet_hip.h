@@ -912,6 +912,37 @@ int kbn_unpack_frames_forward(const unsigned char* image_u8, const void* depth_r
                               float* sparse_depth, int n, int height, int width, int raw_width,
                               int x_offset, int image_channels, int depth_bits, kbn_stream_t stream);
 
+/* The TRAINING batch: what KBNetTrainingDataset.__getitem__ returns (reference src/datasets.py:199-225), batched, from the decoded
+ * bytes of `n` image triplets and their depth maps -- the triplet split (load_image_triplet, :22-46), the crop (random_crop's
+ * slices, :143-148), uint8 -> float32 and depth / 256 in ONE launch per KBN_UNPACK_TRAIN_MAX_FRAMES frames.
+ *   images       a packed buffer of `image_bytes` bytes; frame i's triplet is height_i x raw_width_i x image_channels uint8
+ *                (1 gray, 3 RGB, 4 RGBA; the same for all frames) at byte image_offset_i, raw_width_i = 3 x W_i
+ *   depths       a packed buffer of `depth_bytes` bytes; frame i's samples are height_i x W_i uint16 (depth_bits 16, host byte
+ *                order, depth_offset_i even) or uint8 (8) at byte depth_offset_i
+ *   frames       a HOST array of n records, read before the call returns; they travel to the device in the kernel arguments
+ *                (no device table, no copy, no allocation).  Frames may differ in size; the crop `height` x `width` is one.
+ *   image0 / image1 / image2   n x 3 x height x width float32, values 0..255: the middle (t), left (t-1) and right (t+1) third
+ *                of the triplet; output pixel (y, x) of frame i is raw pixel (y_start_i + y, x_start_i + x) of that third
+ *                (gray replicated, alpha dropped)
+ *   sparse_depth0              n x 1 x height x width float32 = sample / 256
+ * A thread writes four consecutive pixels of a row of all four tensors, with 16-byte stores when width % 4 == 0 and the four
+ * outputs are 16-byte aligned.  Pure data movement and exact conversions: the results are the reference's bits.
+ * Checked for every record before anything is launched -- KBN_ERR_INVALID_ARGUMENT: a NULL pointer, n < 1, height or width < 1,
+ * a raw width that is not 3 x W, a crop that leaves its frame (y_start < 0, y_start + height > height_i, x_start < 0,
+ * x_start + width > W_i), a negative or (16-bit depth) odd offset, a frame that does not lie inside its packed buffer;
+ * KBN_ERR_UNSUPPORTED: other image_channels / depth_bits, a crop of more than 2^31 - 1 four-pixel groups. */
+#define KBN_UNPACK_TRAIN_MAX_FRAMES 64 /* records a launch carries (2 KB of its argument block); longer batches take more launches */
+typedef struct kbn_train_frame {
+    long long image_offset; /* bytes, into `images` */
+    long long depth_offset; /* bytes, into `depths` */
+    int height;             /* raw rows of the triplet and of the depth map */
+    int raw_width;          /* raw columns of the triplet: 3 x W */
+    int y_start, x_start;   /* the crop's first row and its first column inside each third */
+} kbn_train_frame;
+int kbn_unpack_train_frames_forward(const unsigned char* images, size_t image_bytes, const unsigned char* depths, size_t depth_bytes,
+                                    const kbn_train_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
+                                    float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,241 @@
+#!/usr/bin/env python3
+"""The training input pipeline on the GPU box: does a loader keep the training step fed?
+
+    python tools/train_loader_bench.py [--out FILE] [--quick]
+
+Writes 64 KITTI-sized samples into a temporary directory with PIL -- RGB triplets of 3726 x 375 mixed with 3672 x 370 (a smooth
+scene plus sensor noise: compresses like a photograph), 16-bit sparse depth with about 5 % positive points, intrinsics -- and
+reports, for batches of 8 cropped to 320 x 768 with the KITTI script's crop type (horizontal vertical anchored bottom):
+
+1. Loader throughput, triplets/s: (a) kb.loader.TrainingFrameLoader(workers=8) against (b) the reference's algorithm restated
+   here (PIL decode -> float32 -> split -> NumPy crop in `datasets.KBNetTrainingDataset`'s order, under
+   torch.utils.data.DataLoader(num_workers=8, batch_size=8, shuffle=True), then `.to(device)` of the five tensors, reference
+   src/kbnet.py:134-144, 392-397).  Both on the same host CPUs.  A host clock around whole epochs that end in a device
+   synchronise, after a warm epoch (page cache, pinned staging, worker start-up); the median epoch with the smallest and largest.
+   The (b) workers are separate processes started BEFORE this process touches the GPU, and they never touch it.
+2. Kernel time: the device time of kbn_unpack_train_frames_forward alone on one batch's bytes (outputs preallocated, the entry
+   point called directly, `iters` launches between two device events, the median of 5 windows after a warm-up) against the same
+   four tensors computed by torch from the same device bytes (slice, permute, .float(), / 256; the same windows).  The calls rotate
+   through 8 output sets (94 MB each) and 4 input sets, more than the 256 MiB last-level cache holds.  Bytes per output pixel:
+   3 C + 2 read, 40 written.  The two results are compared bit for bit first.
+3. Bytes that cross PCIe per batch for both loaders, from the shapes.
+
+One GPU process; nothing is retried."""
+import argparse
+import os
+import shutil
+import statistics
+import sys
+import tempfile
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from PIL import Image  # noqa: E402
+
+import kbnet_amd as kb  # noqa: E402
+
+N_FILES, BATCH, SHAPE, WORKERS = 64, 8, (320, 768), 8
+CROP_TYPE = ["horizontal", "vertical", "anchored", "bottom"]     # bash/kitti/train_kbnet_kitti.sh
+RAW_SIZES = [(375, 1242), (370, 1224)]
+STEP_MS = 42.7                                                    # the training step at 8 x 320 x 768, DESIGN.md section 8i
+
+
+def write_sample(args):
+    d, i = args
+    h, w = RAW_SIZES[i % 2]
+    g = np.random.Generator(np.random.Philox(100 + i))
+    yy, xx = np.mgrid[0:h, 0:3 * w]
+    base = 128 + 60 * np.sin(xx / 90.0 + i) * np.cos(yy / 40.0) + 30 * np.sin((xx + yy) / 17.0)
+    rgb = np.stack([base + g.normal(0, 6, base.shape) + 20 * c for c in range(3)], axis=-1).clip(0, 255).astype(np.uint8)
+    Image.fromarray(rgb).save(os.path.join(d, f"im{i}.png"), compress_level=6)
+    z = (g.random((h, w)) < 0.05) * (g.random((h, w)) * 79 + 1) * 256
+    Image.fromarray(z.astype(np.uint16)).save(os.path.join(d, f"sd{i}.png"))
+    np.save(os.path.join(d, f"k{i}.npy"), np.array([[721.5, 0, 609.6], [0, 721.5, 172.9], [0, 0, 1]]))
+
+
+class ReferenceStyleDataset(torch.utils.data.Dataset):
+    """The reference's KBNetTrainingDataset.__getitem__ (src/datasets.py:199-225) restated: PIL, float32, split, NumPy crop."""
+
+    def __init__(self, images, depths, ks, shape, crop_type):
+        self.images, self.depths, self.ks, self.shape, self.crop_type = images, depths, ks, shape, crop_type
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, i):
+        triplet = np.transpose(np.asarray(Image.open(self.images[i]).convert("RGB"), np.float32), (2, 0, 1))
+        image1, image0, image2 = np.split(triplet, indices_or_sections=3, axis=-1)
+        z = np.array(Image.open(self.depths[i]), dtype=np.float32) / 256.0
+        z[z <= 0] = 0.0
+        z = np.expand_dims(z, axis=0)
+        k = np.load(self.ks[i]).astype(np.float32)
+        [image0, image1, image2, z], k = kb.loader.random_crop([image0, image1, image2, z], self.shape, intrinsics=k, crop_type=self.crop_type)
+        return [T.astype(np.float32) for T in (image0, image1, image2, z, k)]
+
+
+def epochs(run_epoch, count):
+    """Triplets/s of `count` epochs, each timed on its own, after one warm epoch."""
+    run_epoch()
+    rates = []
+    for _ in range(count):
+        t = time.perf_counter()
+        n = run_epoch()
+        rates.append(n / (time.perf_counter() - t))
+    return rates
+
+
+def spread(values, fmt="{:.1f}"):
+    return f"{fmt.format(statistics.median(values))} (min {fmt.format(min(values))}, max {fmt.format(max(values))})"
+
+
+def windows(fn, iters, count=5):
+    """Device ms a call: `count` windows of `iters` calls between two device events, after a warm-up of 16 calls."""
+    for i in range(16):
+        fn(i)
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(count):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(iters):
+            fn(i)
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) / iters)
+    return out
+
+
+def kernel_part(dev, images, depths, quick):
+    """One batch's decoded bytes on the device: the unpack launch alone against torch ops."""
+    lib = kb._lib.load()
+    files = [open(p, "rb").read() for p in images[:BATCH] + depths[:BATCH]]
+    raw = [kb.loader.decode_png(f) for f in files]
+    frames, img_at, dep_at = [], 0, 0
+    np.random.seed(0)
+    for im, z in zip(raw[:BATCH], raw[BATCH:]):
+        y, x = kb.loader.draw_crop(z.shape[0], z.shape[1], SHAPE, CROP_TYPE)
+        frames.append((img_at, dep_at, z.shape[0], z.shape[1], y, x))
+        img_at, dep_at = (img_at + im.nbytes + 15) & ~15, (dep_at + z.nbytes + 15) & ~15
+    img_host, dep_host = np.zeros(img_at, np.uint8), np.zeros(dep_at, np.uint8)
+    for f, im, z in zip(frames, raw[:BATCH], raw[BATCH:]):
+        img_host[f[0]:f[0] + im.nbytes] = im.reshape(-1)
+        dep_host[f[1]:f[1] + z.nbytes] = z.reshape(-1).view(np.uint8)
+    n_in, n_out = (2, 2) if quick else (4, 8)
+    ins = [(torch.from_numpy(img_host).to(dev), torch.from_numpy(dep_host).to(dev)) for _ in range(n_in)]
+    h, w = SHAPE
+    outs = [[torch.empty((BATCH, c, h, w), device=dev) for c in (3, 3, 3, 1)] for _ in range(n_out)]
+    table = (kb._lib.TrainFrame * BATCH)()
+    for slot, (io, do, H, W, y, x) in zip(table, frames):
+        slot.image_offset, slot.depth_offset, slot.height, slot.raw_width, slot.y_start, slot.x_start = io, do, H, 3 * W, y, x
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def ours(i):
+        (im, z), o = ins[i % n_in], outs[i % n_out]
+        rc = lib.kbn_unpack_train_frames_forward(im.data_ptr(), im.numel(), z.data_ptr(), z.numel(), table, BATCH, h, w, 3, 16,
+                                                 o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), stream)
+        assert rc == 0, rc
+
+    def torch_ops(i):
+        (im, z), o = ins[i % n_in], outs[i % n_out]
+        for n, (io, do, H, W, y, x) in enumerate(frames):
+            triplet = im[io:io + H * 3 * W * 3].view(H, 3 * W, 3)
+            for out, third in zip(o[:3], (1, 0, 2)):
+                out[n] = triplet[y:y + h, third * W + x:third * W + x + w].permute(2, 0, 1).float()
+            o[3][n, 0] = z[do:do + H * W * 2].view(torch.int16).view(H, W)[y:y + h, x:x + w].float() / 256.0      # (the samples are below 2^15)
+
+    ours(0)
+    mine = [t.clone() for t in outs[0]]
+    torch_ops(0)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(mine, outs[0])), "the two computations differ"
+    t_ours = windows(ours, 20 if quick else 400)
+    t_torch = windows(torch_ops, 5 if quick else 50)
+    pixels = BATCH * h * w
+    moved = pixels * (3 * 3 + 2 + 40)
+    us = statistics.median(t_ours) * 1e3
+    return [f"2. kernel: one batch, {BATCH} frames of {RAW_SIZES[0][0]} x {RAW_SIZES[0][1]} / {RAW_SIZES[1][0]} x {RAW_SIZES[1][1]} -> {h} x {w}; results equal bit for bit",
+            f"   kbn_unpack_train_frames_forward   device {spread([t * 1e3 for t in t_ours])} us a launch; 11 B read + 40 B written a pixel = "
+            f"{moved / 1e6:.1f} MB -> {moved / (us * 1e-6) / 1e12:.2f} TB/s",
+            f"   torch ops on the same bytes       device {spread([t * 1e3 for t in t_torch])} us a batch ({4 * BATCH} slice-permute-convert copies and "
+            f"{BATCH} divisions; event window, launch gaps included)",
+            f"   torch / kernel = {statistics.median(t_torch) / statistics.median(t_ours):.1f} x"], frames
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--quick", action="store_true", help="16 files, short windows: a rehearsal, not a measurement")
+    args = ap.parse_args()
+    n_files = 16 if args.quick else N_FILES
+    d = tempfile.mkdtemp(prefix="kbn_train_loader_")
+    try:
+        with ThreadPoolExecutor(max_workers=WORKERS) as ex:
+            list(ex.map(write_sample, [(d, i) for i in range(n_files)]))
+        images = [os.path.join(d, f"im{i}.png") for i in range(n_files)]
+        depths = [os.path.join(d, f"sd{i}.png") for i in range(n_files)]
+        ks = [os.path.join(d, f"k{i}.npy") for i in range(n_files)]
+        mb = sum(os.path.getsize(p) for p in images + depths) / 1e6
+        lines = [f"train_loader_bench: {n_files} samples, {mb / n_files:.2f} MB of PNG a sample, batch {BATCH}, crop {SHAPE[0]} x {SHAPE[1]} "
+                 f"{' '.join(CROP_TYPE)}, {WORKERS} workers"]
+        # (b) first: its worker processes start, and run a whole epoch, before this process touches the GPU
+        reference = torch.utils.data.DataLoader(ReferenceStyleDataset(images, depths, ks, SHAPE, CROP_TYPE), batch_size=BATCH, shuffle=True,
+                                                num_workers=WORKERS, drop_last=False, persistent_workers=True, multiprocessing_context="spawn")
+        for _ in reference:
+            pass
+        if not torch.cuda.is_available():
+            raise SystemExit("train_loader_bench needs a GPU: a time measured anywhere else says nothing")
+        dev = torch.device("cuda:0")
+        kb._lib.load()
+        lines[0] += f"; {torch.cuda.get_device_name(0)}"
+
+        def reference_epoch():
+            n = 0
+            for inputs in reference:
+                inputs = [in_.to(dev) for in_ in inputs]
+                n += inputs[0].shape[0]
+            torch.cuda.synchronize()
+            return n
+
+        rate_b = epochs(reference_epoch, 2 if args.quick else 4)
+        del reference
+        ours = kb.loader.TrainingFrameLoader(images, depths, ks, shape=SHAPE, random_crop_type=CROP_TYPE, batch_size=BATCH, shuffle=True,
+                                             device=dev, workers=WORKERS, prefetch=4)
+
+        def our_epoch():      # four epochs a window: one alone lasts some tens of milliseconds
+            n = 0
+            for _ in range(4):
+                for inputs in ours:
+                    n += inputs[0].shape[0]
+            torch.cuda.synchronize()
+            return n
+
+        rate_a = epochs(our_epoch, 2 if args.quick else 8)
+        need = BATCH / (STEP_MS * 1e-3)
+        verdict = lambda r: "keeps up" if statistics.median(r) >= need else "STARVES the step"
+        lines += [f"1. loader throughput, triplets/s (the {STEP_MS} ms step takes {need:.0f}):",
+                  f"   (a) TrainingFrameLoader              {spread(rate_a)}   {verdict(rate_a)}",
+                  f"   (b) PIL + NumPy under DataLoader     {spread(rate_b)}   {verdict(rate_b)}",
+                  f"   (a) / (b) = {statistics.median(rate_a) / statistics.median(rate_b):.2f}"]
+        part, frames = kernel_part(dev, images, depths, args.quick)
+        lines += part
+        ours_bytes = sum(H * 3 * W * 3 + H * W * 2 for _, _, H, W, _, _ in frames) + BATCH * 36
+        ref_bytes = BATCH * (10 * SHAPE[0] * SHAPE[1] * 4 + 36)
+        lines += [f"3. PCIe bytes a batch: (a) {ours_bytes / 1e6:.1f} MB (the raw uint8 triplets and uint16 depth, whole frames, + intrinsics)   "
+                  f"(b) {ref_bytes / 1e6:.1f} MB (ten float32 planes of the crop a frame + intrinsics)   (a) / (b) = {ours_bytes / ref_bytes:.2f}"]
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -23,6 +23,7 @@ KBN_ACT_ELU, KBN_ACT_SIGMOID = 1, 2
 KBN_RESIZE_NONE, KBN_RESIZE_NEAREST = 0, 1
 KBN_MAX_SRC = 3
 KBN_ADAM_TABLE_CAPACITY, KBN_ADAM_PASS_ELEMENTS = 48, 524288   # tensors a kbn_adam_step launch carries; elements one pass of its widest grid covers
+KBN_MULTI_COPY_TABLE_CAPACITY, KBN_MULTI_COPY_PASS_ELEMENTS = 48, 524288   # the same two numbers of a kbn_multi_tensor_scale_copy launch
 KBN_AUGMENT_ROLE_IMAGE, KBN_AUGMENT_ROLE_RANGE, KBN_AUGMENT_ROLE_VALIDITY = 0, 1, 2
 KBN_AUGMENT_RANGE_0_255, KBN_AUGMENT_RANGE_0_1, KBN_AUGMENT_RANGE_M1_1 = 0, 1, 2
 KBN_AUGMENT_NOISE_NONE, KBN_AUGMENT_NOISE_GAUSSIAN, KBN_AUGMENT_NOISE_UNIFORM = 0, 1, 2
@@ -70,6 +71,15 @@ class AdamTensor(C.Structure):
         ("step_size", C.c_float),
         ("bc2_sqrt", C.c_float),
         ("eps", C.c_float),
+    ]
+
+
+class CopyTensor(C.Structure):
+    """Mirror of `kbn_copy_tensor` (include/kbnet_hip.h): one tensor of a kbn_multi_tensor_scale_copy call."""
+    _fields_ = [
+        ("src", C.c_void_p),
+        ("dst", C.c_void_p),
+        ("numel", C.c_longlong),
     ]
 
 
@@ -197,6 +207,7 @@ SIGNATURES = {
     "kbn_conv1x1s2_split_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "kbn_kb_xyz_s2_forward": (_I, [_P, _L, _I, _I, _I, _P, _P, _I, _F, _P, _L, _I, _P]),
     "kbn_adam_step": (_I, [C.POINTER(AdamTensor), _I, _P]),
+    "kbn_multi_tensor_scale_copy": (_I, [C.POINTER(CopyTensor), _I, _F, _P]),
     "kbn_augment_workspace_bytes": (C.c_size_t, [C.POINTER(AugmentTensor), _I, _I, _I, _I]),
     "kbn_augment_forward": (_I, [C.POINTER(AugmentTensor), _I, C.c_char_p, _I, _I, _I, _P, _P, C.c_size_t, _I, _I, _F, C.c_ulonglong, C.c_uint, _I, _P]),
     "kbn_png_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),

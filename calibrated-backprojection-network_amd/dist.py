@@ -7,6 +7,9 @@ This replaces the reference's three `torch.nn.DataParallel` wrappers
 (reference src/kbnet_model.py:408-415), which scatter/replicate/gather per module
 and per forward inside a single process.
 
+Training takes the same form (`GradientAverager`): the weights resident on every rank, each rank differentiating its own frames,
+and one all-reduce of all gradients, packed into one flat buffer, per step.
+
 Works with backend "nccl" (= RCCL on ROCm) on GPUs and "gloo" on CPU (tests).
 """
 
@@ -17,6 +20,8 @@ from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
+
+from ._lib import KbnError
 
 
 def env_world() -> Tuple[int, int, int]:
@@ -209,6 +214,166 @@ class ShardedRunner:
         if dist.is_initialized() and dist.get_backend() == "nccl":
             return torch.device("cuda", torch.cuda.current_device())
         return torch.device("cpu")
+
+
+# ------------------------------------------------------------------------------------ data-parallel training
+def bucket_layout(numels: Sequence[int]) -> Tuple[list, int]:
+    """(offsets, total) of GradientAverager's flat buffer, in elements: tensor i owns [offsets[i], offsets[i] + numels[i]), every
+    offset and the total a multiple of four, so that each segment of an fp32 buffer starts 16-byte aligned (the vector paths of
+    ops.multi_tensor_scale_copy and ops.adam_step).  The padding of at most three elements after a segment belongs to nobody.  An
+    empty tensor gets the next tensor's offset and no room."""
+    offsets, at = [], 0
+    for n in numels:
+        n = int(n)
+        if n < 0:
+            raise KbnError(f"bucket_layout: a tensor of {n} elements")
+        offsets.append(at)
+        at += (n + 3) & ~3
+    return offsets, at
+
+
+class GradientAverager:
+    """The data-parallel training step: one process per GPU, the weights resident on each, ONE all-reduce a step (in place of the
+    reference's torch.nn.DataParallel, src/kbnet_model.py:408-415, which replicates the weights and gathers the gradients inside
+    one process per forward).
+
+        averager = kb.dist.GradientAverager(depth_model.parameters() + pose_model.parameters(), rank, world)
+        averager.broadcast_parameters()
+        for b, batch in enumerate(loader):                         # TrainingFrameLoader(..., rank=rank, world=world)
+            ...                                                    # forward and compute_loss on this rank's frames
+            optimizer.zero_grad(); loss.backward()
+            averager.average(n_local, loader.global_batch_size(b)); optimizer.step()
+
+    `parameters`: the list the optimizer steps -- dense fp32 tensors on one HIP device (KbnError otherwise) -- or (name, tensor)
+    pairs, whose names the error messages then use.  Construction makes one flat fp32 buffer laid out by `bucket_layout` and zeroes
+    it once; the padding between segments is never written, so it stays zero through every SUM.
+
+    average(n_local, n_global), between loss.backward() and optimizer.step(): every .grad is packed into its segment scaled by
+    float32(n_local / n_global) (ops.multi_tensor_scale_copy: ceil(tensors / its table capacity) launches), the buffer goes through
+    one all_reduce(SUM) (not AVG: gloo has none), and each packed parameter's .grad is rebound to its segment's view, so
+    optimizer.step() reads the reduced gradients where they are: there is no unpack pass.  The call enqueues and returns, without a
+    host synchronisation but the first call's agreement check below (and what the backend's all_reduce itself does).  A .grad that
+    already is its view (optimizer.zero_grad(set_to_none=False)) is scaled in place.
+
+    The weights are n_local / n_global, not 1 / world: TrainingFrameLoader keeps the ragged last batch, and with per-rank losses
+    that are means over the rank's n_local frames the weighted sum is the gradient of the mean over the n_global frames -- what one
+    process computes on the whole batch.  A rank with n_local == 0 (its shard of a short last batch is empty) runs no forward and no
+    backward: it zero-fills the buffer with one memset, takes part in the collective and binds the same views, so every rank applies
+    the same Adam step and the replicas stay bit-identical.
+
+    Parameters without a gradient (calibrated_backprojection4.conv_image, the `projection` of identity-skip ResNet blocks) keep
+    .grad None on every rank, so Adam skips them as in one process, and their segments stay zero.  Which parameters have gradients
+    follows from the architecture alone.  The FIRST average call agrees the set across ranks with one small blocking all-reduce (MAX)
+    of the mask and of its complement; a rank with n_local == 0 contributes to neither.  If two ranks disagree, EVERY rank raises
+    KbnError naming the first such parameter, after the collective: none is left waiting in the next one.  Later calls compare the
+    local set with the agreed one on the host before packing; a mismatch there raises on THAT RANK ONLY (the others then wait in
+    their all-reduce until the backend's timeout) -- it can only come from ranks that built different models.
+
+    broadcast_parameters(src=0) makes every rank's parameters rank `src`'s: packed into the buffer (scale 1), one broadcast, copied
+    back by the same op, which bumps the parameters' version counters (the packed-weight caches follow them); the buffer is zeroed
+    again afterwards.  The modules' floating-point BUFFERS -- BatchNorm running statistics -- are not broadcast: they stay per rank,
+    and rank 0's are the ones a checkpoint holds, which is what the reference's DataParallel does (replica statistics are dropped,
+    device 0's module keeps its own).
+
+    With world == 1 and no `reduce_single` no collective runs (as in ShardedRunner) and broadcast_parameters does nothing;
+    `reduce_single=True` runs the collectives on a one-rank group, for tests.  Any initialised backend that moves device tensors
+    works: "nccl" (RCCL), and "gloo" with ranks that share a device.  One buffer, one all-reduce: there is no bucket size."""
+
+    def __init__(self, parameters, rank: int, world: int, reduce_single: bool = False):
+        what = "GradientAverager"
+        names, params = [], []
+        for i, entry in enumerate(parameters):
+            name, p = entry if isinstance(entry, (tuple, list)) else (None, entry)
+            if not isinstance(p, torch.Tensor):
+                raise KbnError(f"{what}: parameter {i} is {type(p).__name__}, not a tensor")
+            names.append(str(name) if name is not None else f"parameter {i} {tuple(p.shape)}")
+            params.append(p)
+        if not params:
+            raise KbnError(f"{what}: no parameters")
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise KbnError(f"{what}: rank {rank} of world {world}")
+        device = params[0].device
+        for name, p in zip(names, params):
+            if not p.is_cuda:
+                raise KbnError(f"{what}: {name} is on {p.device}: a CUDA/HIP device is required (no CPU fallback)")
+            if p.dtype is not torch.float32:
+                raise KbnError(f"{what}: {name} is {p.dtype}, expected float32")
+            if p.device != device:
+                raise KbnError(f"{what}: parameters live on different devices ({device} and {p.device})")
+            if not p.is_contiguous():
+                raise KbnError(f"{what}: {name} must be dense (contiguous), got strides {p.stride()}")
+        if world > 1 and not (dist.is_initialized() and dist.get_world_size() == world and dist.get_rank() == rank):
+            raise KbnError(f"{what}: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init)")
+        self.names, self.params = names, params
+        self.rank, self.world = rank, world
+        self.collective = world > 1 or (bool(reduce_single) and dist.is_initialized())
+        self.offsets, self.total = bucket_layout([p.numel() for p in params])
+        self.buffer = torch.zeros(max(self.total, 4), dtype=torch.float32, device=device)
+        self.views = [self.buffer[o:o + p.numel()].view(p.shape) for o, p in zip(self.offsets, params)]
+        self._agreed = None      # per parameter: has a gradient (a tuple of bool), once the first average call has settled it
+
+    @torch.no_grad()
+    def broadcast_parameters(self, src: int = 0) -> None:
+        if not self.collective:
+            return
+        from . import ops
+        data = [p.detach() for p in self.params]
+        ops.multi_tensor_scale_copy(data, self.views, 1.0)
+        dist.broadcast(self.buffer, src=int(src))
+        ops.multi_tensor_scale_copy(self.views, self.params, 1.0)
+        self.buffer.zero_()      # the segments of parameters without a gradient must be zero in average()
+
+    def _agree(self, mask) -> None:
+        """The first average call's check; `mask` None on a rank without frames."""
+        n = len(self.params)
+        if not self.collective:
+            self._agreed = mask
+            return
+        votes = torch.zeros(2 * n, dtype=torch.int32)
+        if mask is not None:
+            has = torch.tensor(mask, dtype=torch.int32)
+            votes[:n], votes[n:] = has, 1 - has
+        votes = votes.to(self.buffer.device)
+        dist.all_reduce(votes, op=dist.ReduceOp.MAX)
+        votes = votes.cpu()
+        has, has_not = votes[:n], votes[n:]
+        split = torch.nonzero(has * has_not)
+        if split.numel():      # every rank reads the same reduced votes: all of them raise, none waits in the next collective
+            i = int(split[0])
+            raise KbnError(f"GradientAverager: the ranks disagree on which parameters have a gradient, first on {self.names[i]} "
+                           f"(rank {self.rank} {'has no frames' if mask is None else 'has one' if mask[i] else 'has none'}): they built different "
+                           "models, or one of them skipped a part of its backward pass")
+        if bool((has + has_not).all()):
+            self._agreed = tuple(bool(v) for v in has.tolist())
+
+    def average(self, n_local: int, n_global: int) -> None:
+        what = "GradientAverager.average"
+        n_local, n_global = int(n_local), int(n_global)
+        if n_global < 1 or not 0 <= n_local <= n_global:
+            raise KbnError(f"{what}: {n_local} local frames of {n_global}")
+        if n_local == 0 and not self.collective:
+            raise KbnError(f"{what}: no frames and no other rank")
+        mask = tuple(p.grad is not None for p in self.params) if n_local else None
+        if self._agreed is None:
+            self._agree(mask)
+        elif mask is not None and mask != self._agreed:
+            i = next(j for j, (a, b) in enumerate(zip(mask, self._agreed)) if a != b)
+            raise KbnError(f"{what}: {self.names[i]} has {'a' if mask[i] else 'no'} gradient on rank {self.rank}, on the first call it "
+                           f"had {'one' if self._agreed[i] else 'none'}")
+        bound = self._agreed if self._agreed is not None else mask
+        if n_local:
+            from . import ops
+            ops.multi_tensor_scale_copy([p.grad for p, m in zip(self.params, mask) if m], [v for v, m in zip(self.views, mask) if m],
+                                        n_local / n_global)
+        else:
+            self.buffer.zero_()
+        if self.collective:
+            dist.all_reduce(self.buffer, op=dist.ReduceOp.SUM)
+        if bound is not None:
+            for p, v, m in zip(self.params, self.views, bound):
+                if m:
+                    p.grad = v
 
 
 def barrier():

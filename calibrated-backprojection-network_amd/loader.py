@@ -35,6 +35,7 @@ import torch.utils.data
 
 from . import _lib, ops
 from ._lib import KbnError, check
+from .dist import shard_bounds
 
 
 # ------------------------------------------------------------------------- PNG decode
@@ -334,6 +335,18 @@ def _align16(v: int) -> int:
     return (v + 15) & ~15
 
 
+def shard_batches(order: Sequence[int], batch_size: int, rank: int, world: int) -> List[list]:
+    """One rank's part of an epoch: each global batch order[lo:lo + batch_size] split with dist.shard_bounds, so the ranks' shards
+    of a batch concatenate to it in rank order.  One entry a global batch; where the last batch holds fewer samples than there are
+    ranks, the entries of the last ranks are empty."""
+    out = []
+    for lo in range(0, len(order), batch_size):
+        batch = list(order[lo:lo + batch_size])
+        first, last = shard_bounds(len(batch), rank, world)
+        out.append(batch[first:last])
+    return out
+
+
 class TrainingFrameLoader:
     """Iterates `(image0, image1, image2, sparse_depth0, intrinsics)` device batches -- images N x 3 x h x w in 0..255, depth
     N x 1 x h x w, intrinsics N x 3 x 3 -- over the files `datasets.KBNetTrainingDataset` reads (the same first five constructor
@@ -351,12 +364,22 @@ class TrainingFrameLoader:
     prefix of each buffer crosses PCIe as raw bytes in one asynchronous copy on a side stream, and `ops.unpack_train_frames`
     splits, crops and converts there.  `prefetch` batches are in flight.  Without a crop (`shape` None or not positive) the frames of
     a batch must have one size.  An error found while a batch is prepared is raised when that batch is due.  One epoch at a time:
-    `iter()` first waits for what an epoch that was left early still has in flight."""
+    `iter()` first waits for what an epoch that was left early still has in flight.
+
+    Data-parallel training (`rank`, `world`; kb.dist.GradientAverager): every rank iterates the same `len()` GLOBAL batches and is
+    handed its shard of each (`shard_batches`), `global_batch_size(b)` frames in all.  The epoch's order is drawn as above on every
+    rank and, when a process group exists, replaced by rank 0's (one broadcast_object_list an epoch), so the ranks need no equally
+    seeded generators.  The crops are drawn for the rank's own samples only.  A rank whose shard of a short last batch is empty is
+    handed the five tensors with zero frames; nothing is launched for them."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str], intrinsics_paths: Sequence[str],
                  shape=None, random_crop_type=["none"], batch_size: int = 8, shuffle: bool = True,
-                 device: Optional[torch.device] = None, workers: int = 8, prefetch: int = 4, generator=None):
+                 device: Optional[torch.device] = None, workers: int = 8, prefetch: int = 4, generator=None, rank: int = 0,
+                 world: int = 1):
         what = "TrainingFrameLoader"
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise KbnError(f"{what}: rank {rank} of world {world}")
+        self.rank, self.world = int(rank), int(world)
         self.n_sample = len(image_paths)
         if len(sparse_depth_paths) != self.n_sample or len(intrinsics_paths) != self.n_sample:
             raise KbnError(f"{what}: {self.n_sample} image, {len(sparse_depth_paths)} sparse depth and {len(intrinsics_paths)} intrinsics paths")
@@ -388,6 +411,12 @@ class TrainingFrameLoader:
 
     def __len__(self):
         return (self.n_sample + self.batch_size - 1) // self.batch_size
+
+    def global_batch_size(self, b: int) -> int:
+        """The frames of global batch b over all ranks (the n_global of GradientAverager.average)."""
+        if not 0 <= b < len(self):
+            raise KbnError(f"TrainingFrameLoader: batch {b} of {len(self)}")
+        return min(self.batch_size, self.n_sample - b * self.batch_size)
 
     # -- on the iterating thread: the batch's raw sizes, its checks and its crops --
     def _header(self, i: int):
@@ -473,6 +502,12 @@ class TrainingFrameLoader:
 
     def _enqueue(self, idx: Sequence[int]):
         """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn."""
+        if not idx:      # this rank's shard of a short last batch: zero frames, no staging set, nothing launched
+            h, w = (int(self.shape[0]), int(self.shape[1])) if self.do_random_crop else (0, 0)
+            empty: Future = Future()
+            empty.set_result((tuple(torch.empty(s, dtype=torch.float32, device=self.device)
+                                    for s in ((0, 3, h, w), (0, 3, h, w), (0, 3, h, w), (0, 1, h, w), (0, 3, 3))), None))
+            return empty
         slot = self._serial % (self.prefetch + 1)
         self._serial += 1
         try:
@@ -490,7 +525,11 @@ class TrainingFrameLoader:
             order = list(torch.utils.data.RandomSampler(range(self.n_sample), generator=self.generator))
         else:
             order = list(range(self.n_sample))
-        batches = [order[lo:lo + self.batch_size] for lo in range(0, self.n_sample, self.batch_size)]
+        if self.world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            shared = [[int(i) for i in order]]
+            torch.distributed.broadcast_object_list(shared, src=0)
+            order = shared[0]
+        batches = shard_batches(order, self.batch_size, self.rank, self.world)
         self._pending = pending = [self._enqueue(batches[b]) for b in range(min(self.prefetch, len(batches)))]
         return self._epoch(batches, pending)
 
@@ -499,4 +538,4 @@ class TrainingFrameLoader:
             batch, done = pending.pop(0).result()
             if b + self.prefetch < len(batches):
                 pending.append(self._enqueue(batches[b + self.prefetch]))
-            yield _hand_over(self.device, done, batch)
+            yield batch if done is None else _hand_over(self.device, done, batch)

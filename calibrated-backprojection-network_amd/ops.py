@@ -2609,6 +2609,82 @@ def adam_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp
     torch.autograd.graph.increment_version(written)
 
 
+# ------------------------------------------------------------------ the data-parallel step's gradient pack
+MULTI_COPY_TABLE_CAPACITY = _lib.KBN_MULTI_COPY_TABLE_CAPACITY   # tensors one launch of kbn_multi_tensor_scale_copy carries
+MULTI_COPY_PASS_ELEMENTS = _lib.KBN_MULTI_COPY_PASS_ELEMENTS     # elements of one tensor the widest grid covers before its stride loop repeats
+_COPY_RECORD = struct.Struct("@PPq")      # _lib.CopyTensor's layout: two pointers, numel
+
+
+def multi_tensor_scale_copy(srcs: Sequence[torch.Tensor], dsts: Sequence[torch.Tensor], scale: float = 1.0) -> None:
+    """dsts[i] = srcs[i] * float32(scale), element by element in memory order, over two lists of fp32 tensors
+    (kbn_multi_tensor_scale_copy, csrc/multi_copy.hip): the pack and unpack pass of kb.dist.GradientAverager.  One fp32 multiply an
+    element: the bits of srcs[i] * torch.tensor(scale, dtype=torch.float32), the source's own bits for scale == 1, and a NaN or Inf
+    element stays in its own element.
+
+    srcs[i] and dsts[i] are fp32 tensors on one HIP device with the same number of elements (shapes may differ: a parameter and its
+    segment of a flat buffer).  Every destination must be dense (contiguous; any storage offset -- a pair that is not 16-byte aligned
+    takes the kernel's scalar path): KbnError otherwise, since a copy would not be written.  A source that is not dense is copied and
+    the copy kept alive until the launches are enqueued.  Empty tensors are skipped.  CPU tensors raise: there is no CPU fallback.
+    The work goes to torch's current stream of the tensors' device in ceil(non-empty tensors / MULTI_COPY_TABLE_CAPACITY) launches,
+    with no host synchronisation and no allocation; each launch is one ops.PROFILE record ("multi_tensor_scale_copy", nbytes = 8 B an
+    element: read once, written once).
+
+    A destination that is a parameter (an nn.Parameter, or any tensor that requires grad) is written through a raw pointer, so by
+    adam_step's VERSION CONTRACT its version counter is bumped here."""
+    fn = "multi_tensor_scale_copy"
+    srcs, dsts = list(srcs), list(dsts)
+    count = len(srcs)
+    if len(dsts) != count:
+        raise KbnError(f"{fn}: {count} sources and {len(dsts)} destinations")
+    if count == 0:
+        return
+    try:
+        scale = float(scale)
+        struct.pack("f", scale)
+    except (TypeError, ValueError, struct.error, OverflowError):
+        raise KbnError(f"{fn}: scale must be a host number inside the fp32 range, got {scale!r}") from None
+    device = srcs[0].device if isinstance(srcs[0], torch.Tensor) else None
+    f32 = torch.float32
+    records = bytearray(_COPY_RECORD.size * count)     # kbn_copy_tensor[count], packed in one call a tensor
+    written, keep, used = [], [], 0     # keep: the dense copies of sources, alive until the launches are enqueued
+    for i, (s, d) in enumerate(zip(srcs, dsts)):
+        for t, name in ((s, "srcs"), (d, "dsts")):
+            _require(t, f"{fn}: {name}[{i}]")
+            if t.device != device:
+                raise KbnError(f"{fn}: tensors live on different devices ({device} and {t.device})")
+        numel = d.numel()
+        if s.numel() != numel:
+            raise KbnError(f"{fn}: srcs[{i}] has {s.numel()} elements, dsts[{i}] {numel}")
+        if not d.is_contiguous():
+            raise KbnError(f"{fn}: dsts[{i}] must be dense (contiguous), got strides {d.stride()}: it is written in place")
+        if numel == 0:
+            continue
+        if not s.is_contiguous():
+            s = s.detach().contiguous()
+            keep.append(s)
+        _COPY_RECORD.pack_into(records, used * _COPY_RECORD.size, s.data_ptr(), d.data_ptr(), numel)
+        used += 1
+        if d.requires_grad or isinstance(d, torch.nn.Parameter):
+            written.append(d)
+    if not used:
+        return
+    lib = _lib.load()
+    table = (_lib.CopyTensor * used).from_buffer(records)
+    with torch.cuda.device(device):
+        stream = _stream()
+        if PROFILE is None:
+            check(lib.kbn_multi_tensor_scale_copy(table, used, scale, stream), "kbn_multi_tensor_scale_copy")
+        else:    # one entry-point call a launch, so that each record times one launch
+            for start in range(0, used, MULTI_COPY_TABLE_CAPACITY):
+                n = min(MULTI_COPY_TABLE_CAPACITY, used - start)
+                chunk = C.cast(C.byref(table, start * _COPY_RECORD.size), C.POINTER(_lib.CopyTensor))
+                elements = sum(table[j].numel for j in range(start, start + n))
+                check(_launch(fn, 0.0, lambda: lib.kbn_multi_tensor_scale_copy(chunk, n, scale, stream), nbytes=8.0 * elements),
+                      "kbn_multi_tensor_scale_copy")
+    if written:
+        torch.autograd.graph.increment_version(written)
+
+
 # ------------------------------------------------------------------ the augmentation
 AUGMENT_FLIP_HORIZONTAL, AUGMENT_FLIP_VERTICAL, AUGMENT_REMOVE, AUGMENT_NOISE = 1, 2, 4, 8     # the bits of a frame's flags
 _AUGMENT_RECORD = struct.Struct("@PP4q4i")      # _lib.AugmentTensor's layout: two pointers, four strides, channels, role, map index, reserved

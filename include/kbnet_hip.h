@@ -814,6 +814,29 @@ typedef struct kbn_adam_tensor {
 } kbn_adam_tensor;
 int kbn_adam_step(const kbn_adam_tensor* tensors, int count, kbn_stream_t stream);
 
+/* ------------------------------------------------- the data-parallel step's gradient pack ----
+ * The reference trains on every visible device through torch.nn.DataParallel (src/kbnet_model.py:408-415); here each GPU has its own
+ * process and the ranks meet in ONE all-reduce a step over one flat buffer (kb.dist.GradientAverager).
+ * kbn_multi_tensor_scale_copy fills and empties that buffer: dst[e] = src[e] * scale for `count` fp32 tensors, each a run of `numel`
+ * contiguous floats, `scale` one float for the call.  One fp32 multiply an element: the bits of src * scale (the source's own bits
+ * for scale == 1.0f); a NaN or Inf element stays in its own element.
+ * `tensors` is a HOST array, read before the call returns; the records travel to the device in the kernel arguments,
+ * KBN_MULTI_COPY_TABLE_CAPACITY a launch, so the call issues ceil(records with numel > 0 / capacity) launches and nothing else: no
+ * device table, no copy, no allocation, no synchronisation.  Tensors whose two pointers are 16-byte aligned are processed four
+ * elements a thread; one pass of the widest grid covers KBN_MULTI_COPY_PASS_ELEMENTS elements of a tensor (longer ones loop).
+ * A record with numel == 0 is skipped (its pointers may be NULL).  KBN_ERR_INVALID_ARGUMENT for a NULL table, count < 1, numel < 0 or
+ * a NULL pointer in a record with numel > 0 -- checked for every record before anything is launched.  The two tensors of a record
+ * must not overlap each other or another record's dst. */
+#define KBN_MULTI_COPY_TABLE_CAPACITY 48
+#define KBN_MULTI_COPY_MAX_BLOCKS_X 512
+#define KBN_MULTI_COPY_PASS_ELEMENTS 524288 /* KBN_MULTI_COPY_MAX_BLOCKS_X blocks x 256 threads x 4 elements */
+typedef struct kbn_copy_tensor {
+    const float* src;
+    float* dst;
+    long long numel;
+} kbn_copy_tensor;
+int kbn_multi_tensor_scale_copy(const kbn_copy_tensor* tensors, int count, float scale, kbn_stream_t stream);
+
 /* ------------------------------------------------- the training step's augmentation ----
  *   [images, depths, validity] = transforms.transform(images_arr=..., range_maps_arr=..., validity_maps_arr=...,
  *                                                     random_transform_probability=...)     reference src/kbnet.py:411-422

@@ -4,7 +4,7 @@ L = sum(depth * cotangent) -- for (a) KBNetModel(trainable=True) (kbnet_train.py
 csrc/conv_affine_backward.hip, csrc/kbnet_backward.hip) and (b) the same network in torch.nn.functional operations on the device
 (conv2d without bias, leaky_relu(0.2), interpolate(mode='nearest'), cat, sigmoid), beside (a)'s fused forward.
 
-    python tools/kbnet_train_bench.py [--out FILE] [--quick] [--size N H W] [--narrow]
+    python tools/kbnet_train_bench.py [--out FILE] [--quick] [--size N H W] [--narrow] [--averager]
 
 Method: device events around a loop of steps after a warm-up of the same shapes; the median of 5 windows.  Then one more step of (a)
 with ops.PROFILE on: the time of every launch between its own pair of events (this brackets enqueue gaps too; a kernel trace is the
@@ -94,6 +94,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="fewer iterations (a check that the script runs)")
     ap.add_argument("--size", type=int, nargs=3, default=(8, 320, 768), metavar=("N", "H", "W"))
     ap.add_argument("--narrow", action="store_true", help="KBNetConfig.narrow() widths")
+    ap.add_argument("--averager", action="store_true", help="also time (a) with a world-1 kb.dist.GradientAverager.average() after the backward pass")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("kbnet_train_bench: needs the GPU (no CPU timing stands in for it)")
@@ -136,6 +137,20 @@ def main():
     ta, tb = timed(step_ours, iters), timed(step_theirs, iters)
     lines.append(f"step  (a) HIP {ta[0]:8.3f} [{ta[1]:.3f}, {ta[2]:.3f}]   (b) torch {tb[0]:8.3f} [{tb[1]:.3f}, {tb[2]:.3f}]   (a)/(b) {ta[0] / tb[0]:.2f}")
     print(lines[-1], flush=True)
+    if a.averager:      # the data-parallel step's cost on one rank: the pack of every gradient into the one buffer, no collective
+        averager = kb.dist.GradientAverager(ours.parameters(), 0, 1)
+
+        def step_averaged():
+            step_ours()
+            averager.average(n, n)
+
+        tw, again = timed(step_averaged, iters), timed(step_ours, iters)
+        lines.append(f"step  (a) + GradientAverager(world 1).average {tw[0]:8.3f} [{tw[1]:.3f}, {tw[2]:.3f}]   (a) alone, timed again "
+                     f"{again[0]:8.3f} [{again[1]:.3f}, {again[2]:.3f}]   difference {1e3 * (tw[0] - again[0]):+.0f} us "
+                     f"({averager.total} buffer elements)")
+        print(lines[-1], flush=True)
+        for p in ours.parameters():
+            p.grad = None
     kb.ops.PROFILE = []
     try:
         step_ours()

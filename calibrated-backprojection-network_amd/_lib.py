@@ -30,6 +30,9 @@ KBN_AUGMENT_NOISE_NONE, KBN_AUGMENT_NOISE_GAUSSIAN, KBN_AUGMENT_NOISE_UNIFORM = 
 KBN_AUGMENT_STAGE_SELECT, KBN_AUGMENT_STAGE_APPLY = 1, 2
 KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames whose flags one launch carries; workspace bytes a frame and range map
 KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_forward launch carries
+KBN_SUMMARY_CELL_ZERO, KBN_SUMMARY_CELL_COPY, KBN_SUMMARY_CELL_PHOTO_ERR, KBN_SUMMARY_CELL_DEPTH, KBN_SUMMARY_CELL_REL_ERR = 0, 1, 2, 3, 4
+KBN_SUMMARY_COLORMAP_VIRIDIS, KBN_SUMMARY_COLORMAP_INFERNO = 0, 1
+KBN_SUMMARY_MAX_ROWS = 4   # rows of a kbn_summary_panel_forward panel
 ABI_VERSION = 11
 
 
@@ -108,6 +111,36 @@ class TrainFrame(C.Structure):
         ("raw_width", C.c_int),
         ("y_start", C.c_int),
         ("x_start", C.c_int),
+    ]
+
+
+class SummarySource(C.Structure):
+    """Mirror of `kbn_summary_source` (include/kbnet_hip.h): one tensor a cell of a kbn_summary_panel_forward call reads."""
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("stride_n", C.c_longlong),
+        ("stride_c", C.c_longlong),
+        ("stride_h", C.c_longlong),
+        ("stride_w", C.c_longlong),
+        ("channels", C.c_int),
+        ("reserved", C.c_int),
+    ]
+
+
+class SummaryCell(C.Structure):
+    """Mirror of `kbn_summary_cell`: a kind (KBN_SUMMARY_CELL_*) and up to three sources."""
+    _fields_ = [
+        ("kind", C.c_int),
+        ("reserved", C.c_int),
+        ("src", SummarySource * 3),
+    ]
+
+
+class SummaryRow(C.Structure):
+    """Mirror of `kbn_summary_row`: the left and the right cell of one row of a panel."""
+    _fields_ = [
+        ("left", SummaryCell),
+        ("right", SummaryCell),
     ]
 
 
@@ -210,6 +243,8 @@ SIGNATURES = {
     "kbn_multi_tensor_scale_copy": (_I, [C.POINTER(CopyTensor), _I, _F, _P]),
     "kbn_augment_workspace_bytes": (C.c_size_t, [C.POINTER(AugmentTensor), _I, _I, _I, _I]),
     "kbn_augment_forward": (_I, [C.POINTER(AugmentTensor), _I, C.c_char_p, _I, _I, _I, _P, _P, C.c_size_t, _I, _I, _F, C.c_ulonglong, C.c_uint, _I, _P]),
+    "kbn_summary_panel_forward": (_I, [C.POINTER(SummaryRow), _I, _I, _I, _I, _F, _P, _P]),
+    "kbn_summary_colorize_forward": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
     "kbn_png_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),
     "kbn_png_decode": (_I, [_P, C.c_size_t, _P, C.c_size_t]),
     "kbn_png_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _P]),

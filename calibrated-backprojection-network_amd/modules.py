@@ -1515,6 +1515,17 @@ class KBNetModel(object):
         return loss, {"loss_color": color, "loss_structure": structure, "loss_sparse_depth": sparse, "loss_smoothness": smooth,
                       "loss": loss, "image01": image01, "image02": image02, "per_frame": per_frame}
 
+    def log_summary(self, summary_writer, tag, step, image0=None, image01=None, image02=None, output_depth0=None, sparse_depth0=None,
+                    validity_map0=None, ground_truth0=None, pose01=None, pose02=None, scalars={}, n_display=4):
+        """The reference's log_summary (src/kbnet_model.py:417-650), same signature and defaults: the same add_histogram, add_scalar
+        and add_image calls on `summary_writer` (any object with those three methods; TensorBoard itself stays outside the package),
+        with the same tag strings, in the same order.  The two image panels -- inputs beside their colourised errors, a column a
+        frame -- are written by one kernel launch each (ops.summary_image_panel, ops.summary_depth_panel) and handed over as
+        3 x Hg x Wg device tensors; the reference builds them on the host through matplotlib and torchvision.  See summary.py."""
+        summary.log_summary(self.max_predict_depth, summary_writer, tag, step, image0=image0, image01=image01, image02=image02,
+                            output_depth0=output_depth0, sparse_depth0=sparse_depth0, validity_map0=validity_map0,
+                            ground_truth0=ground_truth0, pose01=pose01, pose02=pose02, scalars=scalars, n_display=n_display)
+
     def load_state_dicts(self, sd_s2d, sd_encoder, sd_decoder):
         """Accepts keys with or without the DataParallel `module.` prefix."""
         for m, sd in zip(self.modules(), (sd_s2d, sd_encoder, sd_decoder)):
@@ -1546,6 +1557,7 @@ class KBNetModel(object):
 
 
 from . import kbnet_train  # noqa: E402  (kbnet_train.py: the recorded forward of KBNetModel(trainable=True))
+from . import summary  # noqa: E402  (summary.py: KBNetModel.log_summary)
 from .posenet import PoseDecoder, PoseEncoder, PoseNetModel  # noqa: E402,F401  (posenet.py: the pose network beside KBNetModel)
 from .posenet_resnet import (ResNetBlock, ResNetEncoder, ResNetPoseDecoder, ResNetPoseNetModel,  # noqa: E402,F401  (posenet_resnet.py:
                              load_pose_model)                                                      # the ResNet-18 / 34 pose networks)

@@ -2789,3 +2789,148 @@ def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], 
                 check(_launch("augment_select", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_SELECT)), "kbn_augment_forward")
             check(_launch("augment_apply", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_APPLY), nbytes=8.0 * elements), "kbn_augment_forward")
     return tuple(outs)
+
+
+# ------------------------------------------------------------------ the training loop's image summaries
+_SUMMARY_SOURCES = {_lib.KBN_SUMMARY_CELL_ZERO: 0, _lib.KBN_SUMMARY_CELL_COPY: 1, _lib.KBN_SUMMARY_CELL_DEPTH: 1, _lib.KBN_SUMMARY_CELL_PHOTO_ERR: 2,
+                    _lib.KBN_SUMMARY_CELL_REL_ERR: 3}
+SUMMARY_COLORMAPS = {"viridis": _lib.KBN_SUMMARY_COLORMAP_VIRIDIS, "inferno": _lib.KBN_SUMMARY_COLORMAP_INFERNO}
+
+
+def _summary_n_display(fn: str, n_display) -> int:
+    if isinstance(n_display, bool) or not isinstance(n_display, int) or n_display < 1:
+        raise KbnError(f"{fn}: n_display must be an integer of at least 1 (the panel's columns), got {n_display!r}")
+    return n_display
+
+
+def _summary_inputs(fn: str, given, channels):
+    """The argument checks of the two panels: `given` name -> tensor or None, `channels` name -> the channel count the reference's
+    torch.cat needs.  What is wrong with a tensor is named before where it lives (a CPU box can test the refusals) -> (N, H, W)."""
+    first = first_name = None
+    for name, t in given.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise KbnError(f"{fn}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise KbnError(f"{fn}: {name}: expected float32, got {t.dtype}")
+        if t.dim() != 4:
+            raise KbnError(f"{fn}: {name}: expected N x C x H x W, got {tuple(t.shape)}")
+        if t.shape[1] != channels[name]:
+            raise KbnError(f"{fn}: {name} has {t.shape[1]} channels, expected {channels[name]} (shape {tuple(t.shape)})")
+        if first is None:
+            first, first_name = t, name
+        elif t.shape[0] != first.shape[0] or t.shape[2:] != first.shape[2:]:
+            raise KbnError(f"{fn}: {name} has shape {tuple(t.shape)}, but {first_name} has {tuple(first.shape)}: N, H and W must agree")
+    for name, t in given.items():
+        if t is not None:
+            _require(t, f"{fn}: {name}")
+            if t.device != first.device:
+                raise KbnError(f"{fn}: tensors live on different devices ({first.device} and {t.device})")
+    return (first.shape[0], first.shape[2], first.shape[3]) if first is not None else (0, 0, 0)
+
+
+def summary_panel_shape(n_rows: int, frames: int, height: int, width: int):
+    """(3, Hg, Wg) of a panel of `frames` tiles of n_rows x 2 cells: make_grid's padding of 2 around and between the tiles of several
+    frames, the tile itself for one frame."""
+    pad = 2 if frames > 1 else 0
+    return 3, n_rows * height + 2 * pad, frames * (2 * width + pad) + pad
+
+
+def _summary_panel(fn: str, rows, n: int, h: int, w: int, n_display: int, max_predict_depth: float, out: Optional[torch.Tensor]):
+    """One kbn_summary_panel_forward launch.  rows: [(left kind, [tensors]), (right kind, [tensors])] per row; None for fewer than
+    two rows (the reference logs no image then)."""
+    if len(rows) < 2:
+        return None
+    if n < 1 or h < 1 or w < 1:
+        raise KbnError(f"{fn}: nothing to show in tensors of {n} x . x {h} x {w}")
+    frames = min(n_display, n)
+    device = rows[0][0][1][0].device
+    records = (_lib.SummaryRow * len(rows))()
+    for record, (left, right) in zip(records, rows):
+        for cell, (kind, tensors) in ((record.left, left), (record.right, right)):
+            assert len(tensors) == _SUMMARY_SOURCES[kind]
+            cell.kind = kind
+            for src, t in zip(cell.src, tensors):
+                src.data = t.data_ptr()
+                src.stride_n, src.stride_c, src.stride_h, src.stride_w = t.stride()
+                src.channels = t.shape[1]
+    panel = _out_tensor(out, summary_panel_shape(len(rows), frames, h, w), device, f"{fn}: out")
+    if panel.device != device:
+        raise KbnError(f"{fn}: out lives on {panel.device}, the inputs on {device}")
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        stream = _stream()
+        cells = 2.0 * len(rows) * frames * h * w
+        check(_launch(fn, 0.0, lambda: lib.kbn_summary_panel_forward(records, len(rows), frames, h, w, float(max_predict_depth), panel.data_ptr(),
+                                                                       stream), nbytes=4.0 * 3 * panel.shape[1] * panel.shape[2] + 4.0 * 1.5 * cells),
+              "kbn_summary_panel_forward")
+    return panel
+
+
+def summary_image_panel(image0, image01=None, image02=None, n_display: int = 4, out: Optional[torch.Tensor] = None):
+    """The image panel of the reference's log_summary (src/kbnet_model.py:474-531, 636-642) as one 3 x Hg x Wg fp32 device tensor,
+    written by ONE launch (kbn_summary_panel_forward, csrc/summary.hip): what
+        torchvision.utils.make_grid(torch.cat(rows, dim=2), nrow=n_display)
+    returns for the rows  image0 | 0,  image01 | inferno(mean_c |image0 - image01| / 0.10),  image02 | the same for image02  of the
+    first min(n_display, N) frames.  A row exists where the reference's `if` holds (image01 and image02 need image0); with fewer than
+    two rows the reference logs no image and this returns None.  The inputs (N x 3 x H x W fp32, any views) are never written and
+    only their first min(n_display, N) frames are read.  `out`: write into this dense tensor of the panel's shape
+    (summary_panel_shape) instead of a new one.  CPU tensors raise: there is no CPU fallback."""
+    fn = "summary_image_panel"
+    n_display = _summary_n_display(fn, n_display)
+    n, h, w = _summary_inputs(fn, {"image0": image0, "image01": image01, "image02": image02}, {"image0": 3, "image01": 3, "image02": 3})
+    rows = []
+    if image0 is not None:
+        rows.append(((_lib.KBN_SUMMARY_CELL_COPY, [image0]), (_lib.KBN_SUMMARY_CELL_ZERO, [])))
+        for warped in (image01, image02):
+            if warped is not None:
+                rows.append(((_lib.KBN_SUMMARY_CELL_COPY, [warped]), (_lib.KBN_SUMMARY_CELL_PHOTO_ERR, [image0, warped])))
+    return _summary_panel(fn, rows, n, h, w, n_display, 1.0, out)
+
+
+def summary_depth_panel(output_depth0, max_predict_depth: float, image0=None, sparse_depth0=None, validity_map0=None, ground_truth0=None,
+                        n_display: int = 4, out: Optional[torch.Tensor] = None):
+    """The depth panel of the reference's log_summary (src/kbnet_model.py:474-487, 533-617, 644-650), one launch as
+    summary_image_panel.  Rows, each where the reference's `if` holds:
+        image0 | 0                                                                 image0 given
+        viridis(output / max_predict_depth) | 0                                    output_depth0 given
+        viridis(sparse / max) | inferno(rel(output, sparse, validity) / 0.05)      output, sparse_depth0 and validity_map0 given
+        viridis(gt[:, 0] / max) | inferno(rel(output, gt[:, 0], gt[:, 1]) / 0.05)  output and ground_truth0 (N x 2 x H x W) given
+    with rel(o, r, v) = (|o - r| + 1e-8) / (r + 1e-8) where v == 1, else v.  None with fewer than two rows.  The ground truth's two
+    planes are read in place (no copy)."""
+    fn = "summary_depth_panel"
+    n_display = _summary_n_display(fn, n_display)
+    given = {"image0": image0, "output_depth0": output_depth0, "sparse_depth0": sparse_depth0, "validity_map0": validity_map0,
+             "ground_truth0": ground_truth0}
+    n, h, w = _summary_inputs(fn, given, {"image0": 3, "output_depth0": 1, "sparse_depth0": 1, "validity_map0": 1, "ground_truth0": 2})
+    zero = (_lib.KBN_SUMMARY_CELL_ZERO, [])
+    rows = []
+    if image0 is not None:
+        rows.append(((_lib.KBN_SUMMARY_CELL_COPY, [image0]), zero))
+    if output_depth0 is not None:
+        rows.append(((_lib.KBN_SUMMARY_CELL_DEPTH, [output_depth0]), zero))
+        if sparse_depth0 is not None and validity_map0 is not None:
+            rows.append(((_lib.KBN_SUMMARY_CELL_DEPTH, [sparse_depth0]), (_lib.KBN_SUMMARY_CELL_REL_ERR, [output_depth0, sparse_depth0, validity_map0])))
+        if ground_truth0 is not None:
+            depth, validity = ground_truth0[:, 0:1], ground_truth0[:, 1:2]
+            rows.append(((_lib.KBN_SUMMARY_CELL_DEPTH, [depth]), (_lib.KBN_SUMMARY_CELL_REL_ERR, [output_depth0, depth, validity])))
+    return _summary_panel(fn, rows, n, h, w, n_display, float(max_predict_depth), out)
+
+
+@_on_tensor_device
+def summary_colorize(x: torch.Tensor, colormap: str) -> torch.Tensor:
+    """matplotlib's Colormap.__call__ on an N x 1 x H x W fp32 device tensor -> N x 3 x H x W (kbn_summary_colorize_forward): entry
+    (int)(x * 256), entry 0 below 0, entry 255 from 1 on, (0, 0, 0) for NaN.  'viridis' and 'inferno' only."""
+    if colormap not in SUMMARY_COLORMAPS:
+        raise ValueError(f"summary_colorize: colormap {colormap!r} is not built in (have: {', '.join(SUMMARY_COLORMAPS)})")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 1:
+        raise KbnError(f"summary_colorize: expected an N x 1 x H x W tensor, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    _require(x, "summary_colorize: T", 4)
+    n, _, h, w = x.shape
+    out = torch.empty((n, 3, h, w), device=x.device, dtype=torch.float32)
+    for first in range(0, n if h * w else 0, 65535):    # a launch's grid carries 65535 frames
+        part = x[first:first + 65535]
+        check(_lib.load().kbn_summary_colorize_forward(part.data_ptr(), part.stride(0), part.stride(2), part.stride(3), part.shape[0], h, w,
+                                                       SUMMARY_COLORMAPS[colormap], out[first:].data_ptr(), _stream()), "kbn_summary_colorize_forward")
+    return out

@@ -888,6 +888,59 @@ int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsi
                         const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
                         float noise_spread, unsigned long long seed, unsigned call, int stages, kbn_stream_t stream);
 
+/* ------------------------------------------------- the training loop's image summaries ----
+ *   depth_model.log_summary(summary_writer, tag, step, image0, image01, image02, output_depth0, ...)   reference src/kbnet.py:455-472
+ * kbn_summary_panel_forward writes, in ONE launch, one finished panel of the reference's log_summary (src/kbnet_model.py:417-650):
+ * the 3 x Hg x Wg fp32 tensor torchvision.utils.make_grid(torch.cat(rows, dim=2), nrow=n_display) returns, for `frames` frames
+ * (the first `frames` of every source) and n_rows rows (2 .. KBN_SUMMARY_MAX_ROWS) of a left and a right height x width cell.
+ *   frames > 1    panel 3 x (n_rows height + 4) x (frames (2 width + 2) + 2): make_grid's padding 2, pad_value 0; frame k's tile
+ *                 at row 2, column k (2 width + 2) + 2
+ *   frames == 1   panel 3 x (n_rows height) x (2 width): the tile itself, no padding
+ * Every element of `panel` (dense) is written, padding and zero cells included; the sources are only read.  Cell kinds, each
+ * operation rounded on its own in fp32 with IEEE division:
+ *   ZERO        (right)  0                                                                           no source
+ *   COPY        (left)   src[0], a 3-channel image, as it is
+ *   PHOTO_ERR   (right)  inferno((((|a0 - b0| + |a1 - b1|) + |a2 - b2|) / 3) / 0.10f)                 a = src[0], b = src[1], 3 channels
+ *   DEPTH       (left)   viridis(d / max_predict_depth)                                              d = src[0], 1 channel
+ *   REL_ERR     (right)  inferno((v == 1 ? (|out - ref| + 1e-8f) / (ref + 1e-8f) : v) / 0.05f)       out, ref, v = src[0 .. 2], 1 channel
+ * The colour lookup is matplotlib's Colormap.__call__ on float32 data: t = x * 256; t < 0 entry 0, t >= 256 entry 255, else entry
+ * (int)t, NaN (0, 0, 0); the tables are matplotlib's `viridis` and `inferno` rounded to float32 (csrc/colormaps.h).
+ * `rows` is a HOST array read before the call returns; the records travel in the kernel arguments (no device table, no allocation,
+ * no synchronisation).  Sources may have any non-negative element strides; a cell whose sources have unit element stride, other
+ * strides that are multiples of 4 and 16-byte aligned pointers is read with 16-byte loads when width % 4 == 0.
+ * KBN_ERR_INVALID_ARGUMENT: NULL pointers, n_rows outside 2 .. 4, sizes < 1, a negative stride, a kind on the wrong side, a NaN
+ * max_predict_depth; KBN_ERR_UNSUPPORTED: a COPY / PHOTO_ERR source that is not 3-channel, a DEPTH / REL_ERR source that is not
+ * 1-channel, a panel of 2^31 elements or more -- all checked before anything is launched.
+ *
+ * kbn_summary_colorize_forward is the lookup alone (log_utils.colorize, reference src/log_utils.py:48-75): x, n frames of height x
+ * width values at the given element strides -> out, n x 3 x height x width dense.  KBN_ERR_UNSUPPORTED for another colormap. */
+#define KBN_SUMMARY_CELL_ZERO 0
+#define KBN_SUMMARY_CELL_COPY 1
+#define KBN_SUMMARY_CELL_PHOTO_ERR 2
+#define KBN_SUMMARY_CELL_DEPTH 3
+#define KBN_SUMMARY_CELL_REL_ERR 4
+#define KBN_SUMMARY_COLORMAP_VIRIDIS 0
+#define KBN_SUMMARY_COLORMAP_INFERNO 1
+#define KBN_SUMMARY_MAX_ROWS 4
+typedef struct kbn_summary_source {
+    const float* data;
+    long long stride_n, stride_c, stride_h, stride_w; /* in elements */
+    int channels;
+    int reserved;
+} kbn_summary_source;
+typedef struct kbn_summary_cell {
+    int kind; /* KBN_SUMMARY_CELL_* */
+    int reserved;
+    kbn_summary_source src[3];
+} kbn_summary_cell;
+typedef struct kbn_summary_row {
+    kbn_summary_cell left, right;
+} kbn_summary_row;
+int kbn_summary_panel_forward(const kbn_summary_row* rows, int n_rows, int frames, int height, int width, float max_predict_depth,
+                              float* panel, kbn_stream_t stream);
+int kbn_summary_colorize_forward(const float* x, long long stride_n, long long stride_h, long long stride_w, int n, int height, int width,
+                                 int colormap, float* out, kbn_stream_t stream);
+
 /* ------------------------------------------------- input pipeline ----
  * The reference reads every sample through PIL on one DataLoader worker:
  *   data_utils.load_image   Image.open(path).convert('RGB') -> float32   reference src/data_utils.py:58-85

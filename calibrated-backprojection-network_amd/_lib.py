@@ -208,6 +208,10 @@ SIGNATURES = {
     "kbn_bn_stats_forward": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, _P]),
     "kbn_bn_act_forward": (_I, [_P, _L, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _P]),
     "kbn_bn_act_backward": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _F, _I, _P]),
+    "kbn_bn_moments_forward": (_I, [_P, _L, _P, _I, _I, _I, _I, _P]),
+    "kbn_bn_moments_merge": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "kbn_bn_act_backward_sums": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "kbn_bn_act_backward_sync_apply": (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _I, _I, _F, _P]),
     "kbn_conv2d_affine_packed_weight_bytes": (C.c_size_t, [_I, _I, _I]),
     "kbn_conv2d_affine_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "kbn_conv2d_affine_forward": (_I, [C.POINTER(ConvSrc), _I, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _F, _P]),

@@ -20,35 +20,12 @@
 //   gradient); kbn_conv2d_s2_backward_weight here is this file's case check (k in {3, 5, 7}, stride 2) in front of it.
 //
 // bn_stats_kernel, bn_bwd_sums_kernel: one workgroup per channel, fp64, a fixed tree.  bn_act_kernel, bn_bwd_apply_kernel: elementwise.
+//   The block sum, the two-pass moments and g_z live in bn_common.h, which bn_sync.hip (the same over several ranks' frames) shares.
+#include "bn_common.h"
 #include "conv_bwd_weight.h"
 
 namespace kbn {
 namespace {
-
-// ---- fixed-order block sum of two doubles (256 threads) -----------------------------------------------------------------
-constexpr int RT = 256;
-
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds /* 2 * RT / 64 doubles */) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        a += __shfl_xor(a, o);
-        b += __shfl_xor(b, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();   // the previous use of `lds` is over
-    if (lane == 0) {
-        lds[wave] = a;
-        lds[RT / 64 + wave] = b;
-    }
-    __syncthreads();
-    a = 0.0;
-    b = 0.0;
-#pragma unroll
-    for (int w = 0; w < RT / 64; ++w) {
-        a += lds[w];
-        b += lds[RT / 64 + w];
-    }
-}
 
 // ---- data gradient ------------------------------------------------------------------------------------------------------
 constexpr int BD_KC = 16;
@@ -206,31 +183,15 @@ bool ks_ok(int ks) { return ks == 3 || ks == 5 || ks == 7; }
 
 // ---- BatchNorm2d --------------------------------------------------------------------------------------------------------
 // mean and BIASED variance of channel blockIdx.x over N, H, W: two passes in fp64 (the mean, then the centred squares).
-__global__ __launch_bounds__(RT) void bn_stats_kernel(const float* __restrict__ x, long long bs, float* __restrict__ mean,
-                                                      float* __restrict__ var, int N, int HW) {
-    __shared__ double red[2 * RT / 64];
+__global__ __launch_bounds__(BN_RT) void bn_stats_kernel(const float* __restrict__ x, long long bs, float* __restrict__ mean,
+                                                         float* __restrict__ var, int N, int HW) {
+    __shared__ double red[2 * BN_RT / 64];
     const int c = blockIdx.x;
-    const float* xc = x + (long long)c * HW;
-    double s = 0.0, unused = 0.0;
-    for (int n = 0; n < N; ++n) {
-        const float* plane = xc + (long long)n * bs;
-        for (int i = threadIdx.x; i < HW; i += RT) s += (double)plane[i];
-    }
-    block_sum2(s, unused, red);
-    const double count = (double)N * (double)HW;
-    const double mu = s / count;
-    double q = 0.0;
-    for (int n = 0; n < N; ++n) {
-        const float* plane = xc + (long long)n * bs;
-        for (int i = threadIdx.x; i < HW; i += RT) {
-            const double d = (double)plane[i] - mu;
-            q += d * d;
-        }
-    }
-    block_sum2(q, unused, red);
+    double mu, q;
+    bn_channel_moments(x + (long long)c * HW, bs, N, HW, red, mu, q);
     if (threadIdx.x == 0) {
         mean[c] = (float)mu;
-        var[c] = (float)(q / count);
+        var[c] = (float)(q / ((double)N * (double)HW));
     }
 }
 
@@ -248,26 +209,20 @@ __global__ void bn_act_kernel(const float* __restrict__ u, long long ubs, const 
     y[(long long)n * ybs + (long long)c * HW + rem] = v;
 }
 
-// g_z = g_y (z > 0 ? 1 : slope), z = u scale + shift exactly as bn_act_kernel forms it; xhat = (u - mean) rstd
-__device__ __forceinline__ float bn_gz(float u, float gy, float sc, float sh, int act, float slope) {
-    if (!act) return gy;
-    return fmaf(u, sc, sh) > 0.f ? gy : gy * slope;
-}
-
 // sums[c] = sum g_z, sums[C + c] = sum g_z xhat over N, H, W of channel c = blockIdx.x: fp64, a fixed tree
-__global__ __launch_bounds__(RT) void bn_bwd_sums_kernel(const float* __restrict__ u, long long ubs, const float* __restrict__ gy,
+__global__ __launch_bounds__(BN_RT) void bn_bwd_sums_kernel(const float* __restrict__ u, long long ubs, const float* __restrict__ gy,
                                                          long long gybs, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, const float* __restrict__ mean,
                                                          const float* __restrict__ rstd, double* __restrict__ sums, int N, int C,
                                                          int HW, int act, float slope) {
-    __shared__ double red[2 * RT / 64];
+    __shared__ double red[2 * BN_RT / 64];
     const int c = blockIdx.x;
     const float sc = scale[c], sh = shift[c], mu = mean[c], rs = rstd[c];
     double s1 = 0.0, s2 = 0.0;
     for (int n = 0; n < N; ++n) {
         const float* up = u + (long long)n * ubs + (long long)c * HW;
         const float* gp = gy + (long long)n * gybs + (long long)c * HW;
-        for (int i = threadIdx.x; i < HW; i += RT) {
+        for (int i = threadIdx.x; i < HW; i += BN_RT) {
             const float uv = up[i];
             const float gz = bn_gz(uv, gp[i], sc, sh, act, slope);
             const float xh = (uv - mu) * rs;
@@ -304,7 +259,9 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ u, long long ubs, 
     gu[(long long)n * gubs + off] = sc * gz;
 }
 
-bool elementwise_shape_ok(int n, int c, int h, int w, long long* total) {
+}  // namespace
+
+bool bn_shape_ok(int n, int c, int h, int w, long long* total) {
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return false;
     const long long hw = (long long)h * w;
     if (hw > 0x7fffffffLL || (long long)n * c > 0x7fffffffLL) return false;
@@ -312,7 +269,13 @@ bool elementwise_shape_ok(int n, int c, int h, int w, long long* total) {
     return *total <= 0x7fffffffLL * 256LL;
 }
 
-}  // namespace
+void bn_bwd_sums_launch(const float* u, long long ubs, const float* gy, long long gybs, const float* scale, const float* shift,
+                        const float* mean, const float* rstd, double* sums, int n, int channels, int hw, int act, float slope,
+                        hipStream_t stream) {
+    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3((unsigned)channels), dim3(BN_RT), 0, stream, u, ubs, gy, gybs, scale, shift, mean, rstd,
+                       sums, n, channels, hw, act, slope);
+}
+
 }  // namespace kbn
 
 using namespace kbn;
@@ -404,10 +367,10 @@ extern "C" int kbn_bn_stats_forward(const float* x, long long batch_stride, floa
                                     int height, int width, kbn_stream_t stream) {
     if (!x || !mean || !var) return KBN_ERR_INVALID_ARGUMENT;
     long long total = 0;
-    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    if (!bn_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
     const long long hw = (long long)height * width;
     if (batch_stride < channels * hw && n > 1) return KBN_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)channels), dim3(RT), 0, (hipStream_t)stream, x, batch_stride, mean, var, n,
+    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)channels), dim3(BN_RT), 0, (hipStream_t)stream, x, batch_stride, mean, var, n,
                        (int)hw);
     KBN_CHECK_LAUNCH();
     return KBN_OK;
@@ -418,7 +381,7 @@ extern "C" int kbn_bn_act_forward(const float* u, long long u_batch_stride, cons
                                   float negative_slope, kbn_stream_t stream) {
     if (!u || !scale || !shift || !y) return KBN_ERR_INVALID_ARGUMENT;
     long long total = 0;
-    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    if (!bn_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
     const long long hw = (long long)height * width;
     if (n > 1 && (u_batch_stride < channels * hw || y_batch_stride < channels * hw)) return KBN_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(bn_act_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u, u_batch_stride,
@@ -433,13 +396,13 @@ extern "C" int kbn_bn_act_backward(const float* u, long long u_batch_stride, con
                                    int apply_activation, float negative_slope, int batch_statistics, kbn_stream_t stream) {
     if (!u || !grad_y || !scale || !shift || !mean || !rstd || !sums || !grad_u) return KBN_ERR_INVALID_ARGUMENT;
     long long total = 0;
-    if (!elementwise_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
+    if (!bn_shape_ok(n, channels, height, width, &total)) return KBN_ERR_INVALID_ARGUMENT;
     const long long hw = (long long)height * width;
     if (n > 1 && (u_batch_stride < channels * hw || grad_y_batch_stride < channels * hw || grad_u_batch_stride < channels * hw))
         return KBN_ERR_INVALID_ARGUMENT;
     const int act = apply_activation ? 1 : 0;
-    hipLaunchKernelGGL(bn_bwd_sums_kernel, dim3((unsigned)channels), dim3(RT), 0, (hipStream_t)stream, u, u_batch_stride, grad_y,
-                       grad_y_batch_stride, scale, shift, mean, rstd, sums, n, channels, (int)hw, act, negative_slope);
+    bn_bwd_sums_launch(u, u_batch_stride, grad_y, grad_y_batch_stride, scale, shift, mean, rstd, sums, n, channels, (int)hw, act,
+                       negative_slope, (hipStream_t)stream);
     KBN_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u,
                        u_batch_stride, grad_y, grad_y_batch_stride, scale, shift, mean, rstd, sums, grad_u, grad_u_batch_stride,

@@ -8,7 +8,8 @@ This replaces the reference's three `torch.nn.DataParallel` wrappers
 and per forward inside a single process.
 
 Training takes the same form (`GradientAverager`): the weights resident on every rank, each rank differentiating its own frames,
-and one all-reduce of all gradients, packed into one flat buffer, per step.
+and one all-reduce of all gradients, packed into one flat buffer, per step.  The pose networks' BatchNorm layers in 'batch' mode are
+the one place where frames are not independent: `BatchNormGroup` gathers their statistics over the ranks.
 
 Works with backend "nccl" (= RCCL on ROCm) on GPUs and "gloo" on CPU (tests).
 """
@@ -273,7 +274,8 @@ class GradientAverager:
     back by the same op, which bumps the parameters' version counters (the packed-weight caches follow them); the buffer is zeroed
     again afterwards.  The modules' floating-point BUFFERS -- BatchNorm running statistics -- are not broadcast: they stay per rank,
     and rank 0's are the ones a checkpoint holds, which is what the reference's DataParallel does (replica statistics are dropped,
-    device 0's module keeps its own).
+    device 0's module keeps its own).  With per-rank statistics in 'batch' mode the reduced gradient of a pose network is NOT the
+    whole batch's: `BatchNormGroup` below, through the pose models' sync_batch_norm, is what makes it so.
 
     With world == 1 and no `reduce_single` no collective runs (as in ShardedRunner) and broadcast_parameters does nothing;
     `reduce_single=True` runs the collectives on a one-rank group, for tests.  Any initialised backend that moves device tensors
@@ -374,6 +376,51 @@ class GradientAverager:
             for p, v, m in zip(self.params, self.views, bound):
                 if m:
                     p.grad = v
+
+
+def every_rank_has_frames(n_global: int, world: int) -> bool:
+    """Does `shard_bounds` give every rank at least one of `n_global` frames?  The same answer on every rank: a training loop
+    whose pose networks run synchronised BatchNorm skips a short last batch for which it is False (a rank without frames runs no
+    forward and cannot join BatchNormGroup's collectives)."""
+    return int(n_global) >= int(world)
+
+
+class BatchNormGroup:
+    """The ranks whose frames one BatchNorm2d layer in 'batch' mode normalises over: what PoseNetModel.sync_batch_norm and
+    ResNetPoseNetModel.sync_batch_norm take, next to GradientAverager in the data-parallel training step.
+
+        group = kb.dist.BatchNormGroup(rank, world)
+        pose_model.requires_grad_(True).set_batch_norm("batch").sync_batch_norm(group)
+
+    Without it each rank normalises with the statistics of its own shard (the reference's torch.nn.DataParallel does the same,
+    src/kbnet_model.py:408-415), and the all-reduced gradient is that of another function than the one a single process
+    differentiates on the whole batch.  With it every layer's forward gathers the ranks' fp64 (count, mean, M2) records and every
+    backward the ranks' two fp64 per-channel sums (ops.batch_norm_act_sync): `gather` below, one all_gather_into_tensor each, enqueued
+    without a host synchronisation.  The merges run in rank order on every rank, so the result does not depend on the backend.
+
+    Every rank must hold at least one frame (`every_rank_has_frames`) and make the same forward -- and backward -- calls in the same
+    order; a mismatch waits in a collective until the backend's timeout.  With world == 1 and no `reduce_single` no collective runs
+    (as in GradientAverager); `reduce_single=True` runs them on a one-rank group, for tests and timings.  Backends: "nccl" (RCCL),
+    and "gloo" with device tensors (ranks that share a device)."""
+
+    def __init__(self, rank: int, world: int, reduce_single: bool = False):
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise KbnError(f"BatchNormGroup: rank {rank} of world {world}")
+        if world > 1 and not (dist.is_initialized() and dist.get_world_size() == world and dist.get_rank() == rank):
+            raise KbnError(f"BatchNormGroup: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init)")
+        self.rank, self.world = rank, world
+        self.collective = world > 1 or (bool(reduce_single) and dist.is_initialized())
+
+    def gather(self, vector: torch.Tensor) -> torch.Tensor:
+        """world x len(vector): row r is rank r's `vector` (a dense fp64 device vector of the same length on every rank)."""
+        if vector.dtype is not torch.float64 or vector.dim() != 1 or not vector.is_cuda or not vector.is_contiguous():
+            raise KbnError(f"BatchNormGroup.gather: a dense float64 CUDA/HIP vector, got {vector.dtype} {tuple(vector.shape)} on {vector.device}")
+        if not self.collective:
+            return vector.unsqueeze(0)
+        out = torch.empty(self.world * vector.numel(), dtype=torch.float64, device=vector.device)      # flat: gloo chunks it by rank
+        dist.all_gather_into_tensor(out, vector)
+        return out.view(self.world, vector.numel())
 
 
 def barrier():

@@ -1845,6 +1845,163 @@ def batch_norm_act_backward(u: torch.Tensor, grad_y: torch.Tensor, gamma: torch.
     return grad_u, sums[c:].float(), sums[:c].float()
 
 
+# ---- BatchNorm on the statistics of a batch spread over several ranks (csrc/bn_sync.hip) ----
+# Everything between the ranks is an fp64 device vector; the four operators take the GATHERED buffers as arguments (row r: rank
+# r's vector), so one process can stack the partial results of several shards and run the whole algebra without a collective.
+def _gathered(fn: str, t, name: str, width: int) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64:
+        raise KbnError(f"{fn}: {name} must be a float64 CUDA/HIP tensor")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] != width or not t.is_contiguous():
+        raise KbnError(f"{fn}: {name} must be a contiguous ranks x {width} tensor, got {tuple(t.shape)} with strides {t.stride()}")
+    return t
+
+
+@_on_tensor_device
+def batch_norm_moments(x: torch.Tensor) -> torch.Tensor:
+    """This rank's record of an N x C x H x W tensor: 2 C + 1 doubles (N H W, the C means, the C sums of centred squares) -- the
+    two fp64 passes of batch_norm_stats, not rounded to fp32 (kbn_bn_moments_forward)."""
+    lib = _lib.load()
+    ptr, bs = _planes(x, "x")
+    n, c, h, w = x.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"batch_norm_moments: empty input {tuple(x.shape)}")
+    record = torch.empty(2 * c + 1, device=x.device, dtype=torch.float64)
+    check(_launch("bn_moments", 0.0, lambda: lib.kbn_bn_moments_forward(ptr, bs, record.data_ptr(), n, c, h, w, _stream()),
+                  nbytes=8.0 * n * c * h * w), "kbn_bn_moments_forward")
+    return record
+
+
+@_on_tensor_device
+def batch_norm_moments_merge(gathered: torch.Tensor):
+    """(mean, biased variance, unbiased variance), C floats each, of the frames of every rank from the ranks x (2 C + 1) records of
+    batch_norm_moments: merged pairwise in row order in fp64 and rounded once (kbn_bn_moments_merge).  With one row, mean and
+    biased variance are batch_norm_stats's.  The unbiased variance of a batch of one value per channel is not finite."""
+    lib = _lib.load()
+    if not isinstance(gathered, torch.Tensor) or gathered.dim() != 2 or gathered.shape[1] < 3 or gathered.shape[1] % 2 == 0:
+        raise KbnError("batch_norm_moments_merge: gathered must be a ranks x (2 C + 1) tensor")
+    world, c = gathered.shape[0], (gathered.shape[1] - 1) // 2
+    g = _gathered("batch_norm_moments_merge", gathered, "gathered", 2 * c + 1)
+    mean, var, unbiased = (torch.empty(c, device=g.device, dtype=torch.float32) for _ in range(3))
+    check(_launch("bn_moments_merge", 0.0, lambda: lib.kbn_bn_moments_merge(g.data_ptr(), world, c, mean.data_ptr(), var.data_ptr(),
+                                                                            unbiased.data_ptr(), _stream()),
+                  nbytes=8.0 * g.numel()), "kbn_bn_moments_merge")
+    return mean, var, unbiased
+
+
+def _bn_backward_args(fn: str, u, grad_y):
+    uptr, ubs = _planes(u.detach() if isinstance(u, torch.Tensor) else u, "u")
+    n, c, h, w = u.shape
+    if n < 1 or c < 1 or h < 1 or w < 1:
+        raise KbnError(f"{fn}: empty input {tuple(u.shape)}")
+    if not isinstance(grad_y, torch.Tensor) or tuple(grad_y.shape) != (n, c, h, w):
+        raise KbnError(f"{fn}: grad_y must be {(n, c, h, w)} like u, got "
+                       f"{tuple(grad_y.shape) if isinstance(grad_y, torch.Tensor) else type(grad_y).__name__}")
+    gptr, gbs = _planes(grad_y.detach(), "grad_y")
+    return uptr, ubs, gptr, gbs, n, c, h, w
+
+
+@_on_tensor_device
+def batch_norm_act_backward_sums(u: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor,
+                                 var: torch.Tensor, eps: float = 1e-5, negative_slope: Optional[float] = 0.2) -> torch.Tensor:
+    """The first launch of batch_norm_act_backward alone (kbn_bn_act_backward_sums): 2 C doubles, sum g_z (this rank's gradient
+    of beta) then sum g_z xhat (of gamma) over this rank's frames, xhat on the given -- merged -- statistics."""
+    lib = _lib.load()
+    uptr, ubs, gptr, gbs, n, c, h, w = _bn_backward_args("batch_norm_act_backward_sums", u, grad_y)
+    scale, shift, m, rstd = _bn_affine("batch_norm_act_backward_sums", c, gamma, beta, mean, var, eps)
+    sums = torch.empty(2 * c, device=u.device, dtype=torch.float64)
+    check(_launch("bn_act_backward_sums", 0.0,
+                  lambda: lib.kbn_bn_act_backward_sums(uptr, ubs, gptr, gbs, scale.data_ptr(), shift.data_ptr(), m.data_ptr(),
+                                                       rstd.data_ptr(), sums.data_ptr(), n, c, h, w, *_act_args(negative_slope), _stream()),
+                  nbytes=8.0 * n * c * h * w), "kbn_bn_act_backward_sums")
+    return sums
+
+
+@_on_tensor_device
+def batch_norm_act_backward_sync(u: torch.Tensor, grad_y: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor,
+                                 var: torch.Tensor, gathered_sums: torch.Tensor, gathered_moments: torch.Tensor, rank: int,
+                                 eps: float = 1e-5, negative_slope: Optional[float] = 0.2) -> torch.Tensor:
+    """grad_u of rank `rank` (kbn_bn_act_backward_sync_apply): scale (g_z - (S1 + xhat S2) / c_rank) with S the sum of the rows of
+    `gathered_sums` (ranks x 2 C, from batch_norm_act_backward_sums) weighted c_r / M in row order; the counts are column 0 of
+    `gathered_moments` (ranks x (2 C + 1), what the forward merged).  The divisor is the rank's own count: with per-rank losses
+    that are means over the rank's frames, GradientAverager's n_r / n weights then give the gradient of the global mean."""
+    lib = _lib.load()
+    fn = "batch_norm_act_backward_sync"
+    uptr, ubs, gptr, gbs, n, c, h, w = _bn_backward_args(fn, u, grad_y)
+    gs = _gathered(fn, gathered_sums, "gathered_sums", 2 * c)
+    gm = _gathered(fn, gathered_moments, "gathered_moments", 2 * c + 1)
+    world, rank = gs.shape[0], int(rank)
+    if gm.shape[0] != world or not 0 <= rank < world:
+        raise KbnError(f"{fn}: rank {rank} with {world} rows of sums and {gm.shape[0]} of moments")
+    scale, shift, m, rstd = _bn_affine(fn, c, gamma, beta, mean, var, eps)
+    grad_u = torch.empty((n, c, h, w), device=u.device, dtype=torch.float32)
+    check(_launch("bn_act_backward_sync_apply", 0.0,
+                  lambda: lib.kbn_bn_act_backward_sync_apply(uptr, ubs, gptr, gbs, scale.data_ptr(), shift.data_ptr(), m.data_ptr(),
+                                                             rstd.data_ptr(), gs.data_ptr(), gm.data_ptr(), world, rank,
+                                                             grad_u.data_ptr(), c * h * w, n, c, h, w, *_act_args(negative_slope),
+                                                             _stream()),
+                  nbytes=12.0 * n * c * h * w), "kbn_bn_act_backward_sync_apply")
+    return grad_u
+
+
+def _bn_act_sync_forward(u, gamma, beta, group, eps, negative_slope):
+    gathered = group.gather(batch_norm_moments(u))
+    mean, var, unbiased = batch_norm_moments_merge(gathered)
+    scale, shift, _, _ = _bn_affine("batch_norm_act_sync", u.shape[1], gamma, beta, mean, var, eps)
+    return _bn_act_launch(u, scale, shift, negative_slope), mean, var, unbiased, gathered
+
+
+class _BatchNormActSync(torch.autograd.Function):
+    """_BatchNormAct on the statistics of every rank's frames: one collective in the forward (the records), one in the backward
+    (the sums).  Saved: u, gamma, beta, the merged statistics and the gathered records (the counts)."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, beta, group, eps, negative_slope):
+        y, mean, var, unbiased, gathered = _bn_act_sync_forward(u.detach(), gamma, beta, group, eps, negative_slope)
+        ctx.save_for_backward(u, gamma, beta, mean, var, gathered)
+        ctx.args = (group, eps, negative_slope)
+        ctx.mark_non_differentiable(mean, var, unbiased)
+        return y, mean, var, unbiased
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, *_):
+        u, gamma, beta, mean, var, gathered = ctx.saved_tensors
+        group, eps, negative_slope = ctx.args
+        c = u.shape[1]
+        grad_y = grad_y.contiguous()
+        sums = batch_norm_act_backward_sums(u, grad_y, gamma, beta, mean, var, eps, negative_slope)
+        need = ctx.needs_input_grad
+        grad_u = None
+        if need[0] or group.collective:      # every rank takes part in the collective, whatever it needs itself
+            gathered_sums = group.gather(sums)
+        if need[0]:
+            grad_u = batch_norm_act_backward_sync(u, grad_y, gamma, beta, mean, var, gathered_sums, gathered, group.rank, eps, negative_slope)
+        return (grad_u if need[0] else None, sums[c:].float() if need[1] else None, sums[:c].float() if need[2] else None, None, None, None)
+
+
+@_on_tensor_device
+def batch_norm_act_sync(u: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, group, eps: float = 1e-5,
+                        negative_slope: Optional[float] = 0.2, return_stats: bool = False):
+    """batch_norm_act(batch=True) on the statistics of the frames of EVERY rank of `group` (a kb.dist.BatchNormGroup): each rank's
+    fp64 moments are gathered and merged in rank order, so all ranks normalise with the same bits and compute what one process
+    computes on the whole batch.  Differentiable with respect to u, gamma and beta (one node, no double backward); the backward
+    gathers the ranks' two per-channel sums.  grad_gamma and grad_beta are this rank's own sums, and grad_u is in the units of
+    this rank's loss: GradientAverager.average(n_local, n_global) completes them.  Every rank must make the same calls in the same
+    order -- in the backward too -- and hold at least one frame.  `return_stats`: (y, mean, biased variance, unbiased variance),
+    the merged statistics a running-statistics update needs."""
+    _require(u, "u", 4)
+    if u.shape[0] < 1 or u.shape[1] < 1 or u.shape[2] < 1 or u.shape[3] < 1:
+        raise KbnError(f"batch_norm_act_sync: empty input {tuple(u.shape)} (a rank without frames cannot join the collectives)")
+    for t, name in ((gamma, "gamma"), (beta, "beta")):
+        _channel_vector("batch_norm_act_sync", t, name, u.shape[1])
+    _planes(u, "u")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (u, gamma, beta)):
+        out = _BatchNormActSync.apply(u, gamma, beta, group, float(eps), negative_slope)
+    else:
+        out = _bn_act_sync_forward(u.detach(), gamma, beta, group, float(eps), negative_slope)[:4]
+    return out if return_stats else out[0]
+
+
 _UNIT_AFFINE = {}
 
 

@@ -68,6 +68,8 @@ class PoseConv2d(torch.nn.Module):
     one launch (ops.conv2d_s2_affine).  The packed weight (a modules._PackedBlob) and the scale / shift vectors are cached and
     rebuilt when a parameter or buffer changes (in place, replaced or moved)."""
 
+    sync_group = None     # a kb.dist.BatchNormGroup once the model's sync_batch_norm has set one: 'batch' mode spans its ranks
+
     def __init__(self, in_channels, out_channels, kernel_size, weight_initializer, slope):
         super().__init__()
         self.in_channels, self.out_channels, self.kernel_size, self.stride = in_channels, out_channels, kernel_size, 2
@@ -123,16 +125,26 @@ class PoseConv2d(torch.nn.Module):
         """The layer as conv, [batch statistics], BatchNorm + activation: what the fused launch of `run` cannot be when the
         backward needs the conv's output or the statistics are the batch's own.  Recorded for autograd when grad mode is on and
         a parameter requires grad.  `batch`: normalise with the statistics of this batch and update the running ones as
-        torch.nn.BatchNorm2d does in train mode (src/net_utils.py:103-104); the module's `training` flag stays False."""
+        torch.nn.BatchNorm2d does in train mode (src/net_utils.py:103-104); the module's `training` flag stays False.  With a
+        `sync_group` the batch is the frames of every rank of the group (ops.batch_norm_act_sync)."""
         u = self.conv_recorded(inputs)
         bn = getattr(self, "batch_norm", None)
         if bn is None:       # (posenet_resnet.ResNetConv2d without batch norm: the projection)
             return u
+        group = self.sync_group
         if batch:
             count = u.shape[0] * u.shape[2] * u.shape[3]
-            if count <= 1:
+            if count <= 1 and (group is None or group.world == 1):      # (more ranks, a frame each: the global count is 2 or more)
                 raise KbnError(f"set_batch_norm('batch'): a {tuple(u.shape)} map has one value per channel, no batch statistics "
                                "(torch.nn.BatchNorm2d raises there too)")
+        if batch and group is not None:      # the statistics of every rank's frames (PoseModelBase.sync_batch_norm)
+            y, mean, _, unbiased = ops.batch_norm_act_sync(u, bn.weight, bn.bias, group, bn.eps, self.slope, return_stats=True)
+            with torch.no_grad():
+                bn.running_mean.mul_(1.0 - bn.momentum).add_(mean, alpha=bn.momentum)
+                bn.running_var.mul_(1.0 - bn.momentum).add_(unbiased, alpha=bn.momentum)
+                bn.num_batches_tracked.add_(1)
+            return y
+        if batch:
             mean, var = ops.batch_norm_stats(u.detach())
             with torch.no_grad():
                 momentum = bn.momentum
@@ -263,6 +275,25 @@ class PoseModelBase(object):
         if mode not in ("running", "batch"):
             raise KbnError(f"{type(self).__name__}.set_batch_norm: 'running' or 'batch', got {mode!r}")
         self.batch_norm_mode = mode
+        return self
+
+    def sync_batch_norm(self, group=None):
+        """`group` (a kb.dist.BatchNormGroup): in 'batch' mode every BatchNorm layer normalises with the statistics of the frames
+        of ALL the group's ranks, its backward sums over them, and the running statistics follow the merged values, equal on every
+        rank -- data-parallel training then computes what one process computes on the whole batch (the reference's DataParallel
+        replicas each use their own shard's statistics).  Two small collectives a layer and pass; every rank must hold a frame and
+        make the same forward and backward calls in the same order.  None (default): this rank's own frames, as before.  No effect
+        in 'running' mode."""
+        if not self._has_backward:
+            raise KbnError(f"{type(self).__name__}.sync_batch_norm: this model has no backward pass (ResNetPoseNetModel: build it "
+                           "with trainable=True)")
+        from .dist import BatchNormGroup
+        if group is not None and not isinstance(group, BatchNormGroup):
+            raise KbnError(f"{type(self).__name__}.sync_batch_norm: a kb.dist.BatchNormGroup or None, got {type(group).__name__}")
+        for net in self.modules():
+            for layer in net.modules():
+                if isinstance(layer, PoseConv2d):
+                    layer.sync_group = group
         return self
 
     def train(self):

@@ -678,6 +678,32 @@ int kbn_bn_act_backward(const float* u, long long u_batch_stride, const float* g
                         float* grad_u, long long grad_u_batch_stride, int n, int channels, int height, int width,
                         int apply_activation, float negative_slope, int batch_statistics, kbn_stream_t stream);
 
+/* The same BatchNorm2d (src/net_utils.py:103-104, 128-141) on the statistics of a batch that is spread over several ranks, in
+ * place of the per-replica statistics of torch.nn.DataParallel (src/kbnet_model.py:408-415): rank r holds n_r frames,
+ * c_r = n_r H W values per channel, M = sum c_r.  Between the ranks travel fp64 records that the caller gathers; every sum over
+ * ranks runs in rank order, so all ranks form the same bits.
+ * kbn_bn_moments_forward: record[0] = c_r, record[1 + c] = the mean of channel c over the rank's frames, record[1 + channels + c]
+ *   = its sum of centred squares: kbn_bn_stats_forward's two fp64 passes, not rounded to fp32 (2 channels + 1 doubles).
+ * kbn_bn_moments_merge: `records` (world x (2 channels + 1), rank order) merged pairwise from rank 0 on,
+ *   d = m_B - m_A; m = m_A + d c_B / (c_A + c_B); q = q_A + q_B + d^2 c_A c_B / (c_A + c_B), then rounded to fp32 once:
+ *   mean, var = q / M (normalises) and var_unbiased = q / (M - 1) (the running variance's update).
+ * kbn_bn_act_backward_sums: launch (1) of kbn_bn_act_backward alone, on the merged statistics: the rank's sums (2 channels doubles).
+ * kbn_bn_act_backward_sync_apply: S = sum_r (c_r / M) gathered_sums[r] in rank order (world x 2 channels; the counts c_r are
+ *   gathered_records[r][0]), then grad_u = scale[c] (g_z - (S[c] + xhat S[channels + c]) / c_rank): the divisor is the rank's own
+ *   count, which keeps grad_u in the units of a loss that is the mean over the rank's own frames. */
+int kbn_bn_moments_forward(const float* x, long long batch_stride, double* record, int n, int channels, int height, int width,
+                           kbn_stream_t stream);
+int kbn_bn_moments_merge(const double* records, int world, int channels, float* mean, float* var, float* var_unbiased,
+                         kbn_stream_t stream);
+int kbn_bn_act_backward_sums(const float* u, long long u_batch_stride, const float* grad_y, long long grad_y_batch_stride,
+                             const float* scale, const float* shift, const float* mean, const float* rstd, double* sums, int n,
+                             int channels, int height, int width, int apply_activation, float negative_slope, kbn_stream_t stream);
+int kbn_bn_act_backward_sync_apply(const float* u, long long u_batch_stride, const float* grad_y, long long grad_y_batch_stride,
+                                   const float* scale, const float* shift, const float* mean, const float* rstd,
+                                   const double* gathered_sums, const double* gathered_records, int world, int rank, float* grad_u,
+                                   long long grad_u_batch_stride, int n, int channels, int height, int width, int apply_activation,
+                                   float negative_slope, kbn_stream_t stream);
+
 /* ------------------------------------------------- ResNet pose networks (eval mode) ----
  * PoseNetModel(encoder_type='resnet18' | 'resnet34')   reference src/posenet_model.py:55-87 (what src/kbnet.py:221-226 trains)
  *   networks.ResNetEncoder                             reference src/networks.py:674-996

@@ -255,7 +255,10 @@ SIGNATURES = {
     "kbn_depth_to_u16_forward": (_I, [_P, _P, _L, _P]),
     "kbn_png_encode_gray16_bound": (C.c_size_t, [_I, _I]),
     "kbn_png_encode_gray16": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
-    "kbn_unpack_frames_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "kbn_export_pack_forward": (_I, [_P, _F, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "kbn_png_encode_rgb8_bound": (C.c_size_t, [_I, _I]),
+    "kbn_png_encode_rgb8": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
+    "kbn_unpack_frames_forward":(_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "kbn_unpack_train_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(TrainFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 

@@ -255,25 +255,17 @@ size_t put_chunk(unsigned char* out, const char type[4], const unsigned char* da
     return (size_t)n + 12;
 }
 
-int png_encode_gray16_impl(const unsigned short* pixels, int width, int height, unsigned char* out, size_t out_capacity,
-                           size_t* out_bytes, int level) {
-    if (!pixels || !out || !out_bytes || width < 1 || height < 1 || level < -1 || level > 9) return KBN_ERR_INVALID_ARGUMENT;
-    const size_t row = 1 + 2 * (size_t)width, raw = row * height;
-    if (raw > 0xffffffffull) return KBN_ERR_UNSUPPORTED;
-    std::vector<unsigned char> lines(raw);
-    for (int y = 0; y < height; ++y) {
-        unsigned char* l = lines.data() + row * y;
-        l[0] = 0;   // filter type None
-        const unsigned short* src = pixels + (size_t)width * y;
-        for (int x = 0; x < width; ++x) { l[1 + 2 * x] = (unsigned char)(src[x] >> 8); l[2 + 2 * x] = (unsigned char)(src[x] & 0xff); }
-    }
+// signature, IHDR, ONE IDAT holding the deflated `lines` (height scanlines, each a filter byte and its samples), IEND
+int png_emit(const std::vector<unsigned char>& lines, int width, int height, int bit_depth, int color_type, unsigned char* out,
+             size_t out_capacity, size_t* out_bytes, int level) {
+    const size_t raw = lines.size();
     uLongf zn = compressBound((uLong)raw);
-    if (8 + 25 + 12 + (size_t)zn + 12 > out_capacity) return KBN_ERR_WORKSPACE;   // kbn_png_encode_gray16_bound says how much
+    if (8 + 25 + 12 + (size_t)zn + 12 > out_capacity) return KBN_ERR_WORKSPACE;   // kbn_png_encode_*_bound says how much
     unsigned char* p = out;
     memcpy(p, kSignature, 8); p += 8;
     unsigned char ihdr[13];
     put_be32(ihdr, (uint32_t)width); put_be32(ihdr + 4, (uint32_t)height);
-    ihdr[8] = 16; ihdr[9] = 0; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    ihdr[8] = (unsigned char)bit_depth; ihdr[9] = (unsigned char)color_type; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     p += put_chunk(p, "IHDR", ihdr, 13);
     if (compress2(p + 8, &zn, lines.data(), (uLong)raw, level) != Z_OK) return KBN_ERR_LAUNCH;
     if (zn > 0x7fffffffUL) return KBN_ERR_UNSUPPORTED;
@@ -286,6 +278,37 @@ int png_encode_gray16_impl(const unsigned short* pixels, int width, int height, 
     p += put_chunk(p, "IEND", nullptr, 0);
     *out_bytes = (size_t)(p - out);
     return KBN_OK;
+}
+
+int png_encode_gray16_impl(const unsigned short* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                           size_t* out_bytes, int level) {
+    if (!pixels || !out || !out_bytes || width < 1 || height < 1 || level < -1 || level > 9) return KBN_ERR_INVALID_ARGUMENT;
+    const size_t row = 1 + 2 * (size_t)width, raw = row * height;
+    if (raw > 0xffffffffull) return KBN_ERR_UNSUPPORTED;
+    std::vector<unsigned char> lines(raw);
+    for (int y = 0; y < height; ++y) {
+        unsigned char* l = lines.data() + row * y;
+        l[0] = 0;   // filter type None
+        const unsigned short* src = pixels + (size_t)width * y;
+        for (int x = 0; x < width; ++x) { l[1 + 2 * x] = (unsigned char)(src[x] >> 8); l[2 + 2 * x] = (unsigned char)(src[x] & 0xff); }
+    }
+    return png_emit(lines, width, height, 16, 0, out, out_capacity, out_bytes, level);
+}
+
+// 8-bit RGB (colour type 2): the image run_kbnet.py --save_outputs stores beside its depth maps (reference src/kbnet.py:1014-1016,
+// Image.fromarray of an H x W x 3 uint8 array).  `pixels`: height x width x 3, interleaved.
+int png_encode_rgb8_impl(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                         size_t* out_bytes, int level) {
+    if (!pixels || !out || !out_bytes || width < 1 || height < 1 || level < -1 || level > 9) return KBN_ERR_INVALID_ARGUMENT;
+    const size_t stride = 3 * (size_t)width, row = 1 + stride, raw = row * height;
+    if (raw > 0xffffffffull) return KBN_ERR_UNSUPPORTED;
+    std::vector<unsigned char> lines(raw);
+    for (int y = 0; y < height; ++y) {
+        unsigned char* l = lines.data() + row * y;
+        l[0] = 0;   // filter type None
+        memcpy(l + 1, pixels + stride * y, stride);
+    }
+    return png_emit(lines, width, height, 8, 2, out, out_capacity, out_bytes, level);
 }
 
 }  // namespace
@@ -303,6 +326,22 @@ int kbn_png_encode_gray16(const unsigned short* pixels, int width, int height, u
                           size_t* out_bytes, int level) {
     try {
         return png_encode_gray16_impl(pixels, width, height, out, out_capacity, out_bytes, level);
+    } catch (...) {
+        return KBN_ERR_WORKSPACE;
+    }
+}
+
+size_t kbn_png_encode_rgb8_bound(int width, int height) {
+    if (width < 1 || height < 1) return 0;
+    const unsigned long long raw = (1ull + 3ull * (unsigned long long)width) * (unsigned long long)height;
+    if (raw > 0xffffffffull) return 0;
+    return 8 + 25 + 12 + (size_t)compressBound((uLong)raw) + 12;
+}
+
+int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                        size_t* out_bytes, int level) {
+    try {
+        return png_encode_rgb8_impl(pixels, width, height, out, out_capacity, out_bytes, level);
     } catch (...) {
         return KBN_ERR_WORKSPACE;
     }

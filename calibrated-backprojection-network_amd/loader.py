@@ -21,11 +21,18 @@ src/datasets.py:161-228, src/kbnet.py:134-144) takes the same road with all thre
 different raw sizes in one batch and the reference's random crop: `draw_crop` makes the reference's np.random
 decisions on the host, `kbn_unpack_train_frames_forward` cuts every frame's crop out of its raw bytes on the device.
 `random_crop` is the reference-named NumPy function on top of `draw_crop`.
+
+The output side (`run_kbnet.py --save_outputs`, reference src/kbnet.py:986-1026): `save_depth` / `save_depth_batch` for one tensor,
+and `OutputWriter` for the whole export of a run -- `ops.export_pack` makes the pixels of a batch's files in one launch, a side
+stream copies them to pinned slots, host threads encode and write while the next batch runs (kb.inference.run drives it).
+`read_paths`, `write_paths` and `load_depth_with_validity_map` are the reference's data_utils functions of those names.
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import os
+import threading
 from concurrent.futures import Future, ThreadPoolExecutor
 from typing import List, Optional, Sequence, Tuple
 
@@ -126,19 +133,75 @@ def load_depth(path: str, data_format: str = "HW") -> np.ndarray:
     return z
 
 
+def load_depth_with_validity_map(path: str, data_format: str = "HW"):
+    """reference src/data_utils.py:87-121: (depth, validity map) of a 16-bit PNG -- sample / 256, and 1 where that is positive --
+    as float32 H x W ('HW'), 1 x H x W ('CHW') or H x W x 1 ('HWC')."""
+    z = load_depth(path, data_format="HW")
+    v = z.astype(np.float32)
+    v[z > 0] = 1.0
+    if data_format == "HW":
+        pass
+    elif data_format == "CHW":
+        z, v = np.expand_dims(z, axis=0), np.expand_dims(v, axis=0)
+    elif data_format == "HWC":
+        z, v = np.expand_dims(z, axis=-1), np.expand_dims(v, axis=-1)
+    else:
+        raise ValueError("Unsupported data format: {}".format(data_format))
+    return z, v
+
+
+def read_paths(filepath: str) -> List[str]:
+    """reference src/data_utils.py:21-41: the lines of a newline-delimited file of paths, up to the first empty line."""
+    path_list = []
+    with open(filepath) as f:
+        while True:
+            path = f.readline().rstrip("\n")
+            if path == "":      # nothing more to read, or an empty line: the reference stops at either
+                break
+            path_list.append(path)
+    return path_list
+
+
+def write_paths(filepath: str, paths: Sequence[str]) -> None:
+    """reference src/data_utils.py:43-56: one path a line."""
+    with open(filepath, "w") as o:
+        for idx in range(len(paths)):
+            o.write(paths[idx] + "\n")
+
+
 # ---------------------------------------------------------------------- output side
+_scratch = threading.local()    # one encode buffer per host thread, grown as needed: an OutputWriter worker allocates nothing per file
+
+
+def _encode_png(kind: str, pixels: np.ndarray, width: int, height: int, level: int) -> memoryview:
+    """The PNG file image of C-contiguous pixels, as a view of the calling thread's scratch buffer: valid until that thread encodes
+    again.  kind: 'gray16' (H x W uint16) or 'rgb8' (H x W x 3 uint8).  ctypes drops the interpreter lock around the encoder."""
+    lib = _lib.load()
+    cap = getattr(lib, f"kbn_png_encode_{kind}_bound")(width, height)
+    buf = getattr(_scratch, "buf", None)
+    if buf is None or len(buf) < cap:
+        buf = _scratch.buf = (C.c_ubyte * cap)()
+    n = C.c_size_t()
+    check(getattr(lib, f"kbn_png_encode_{kind}")(pixels.ctypes.data_as(C.c_void_p), width, height, buf, len(buf), C.byref(n), int(level)),
+          f"kbn_png_encode_{kind}")
+    return memoryview(buf)[:n.value]
+
+
+def encode_image_png(rgb_u8: np.ndarray, level: int = 6) -> bytes:
+    """H x W x 3 uint8 pixels -> the bytes of an 8-bit RGB PNG (kbn_png_encode_rgb8): the file `Image.fromarray(rgb_u8).save(path)`
+    stands for in reference src/kbnet.py:1015-1016 (the same pixels; the file's bytes are not PIL's)."""
+    a = np.ascontiguousarray(rgb_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise KbnError(f"encode_image_png: expected an H x W x 3 uint8 array, got {a.dtype} {a.shape}")
+    return bytes(_encode_png("rgb8", a, a.shape[1], a.shape[0], level))
+
+
 def encode_depth_png(samples: np.ndarray, level: int = 6) -> bytes:
     """H x W uint16 samples (depth * 256) -> the bytes of a 16-bit grayscale PNG (kbn_png_encode_gray16)."""
-    lib = _lib.load()
     a = np.ascontiguousarray(samples, dtype=np.uint16)
     if a.ndim != 2:
         raise KbnError("encode_depth_png: expected an H x W array")
-    h, w = a.shape
-    cap = lib.kbn_png_encode_gray16_bound(w, h)
-    buf = (C.c_ubyte * cap)()
-    n = C.c_size_t()
-    check(lib.kbn_png_encode_gray16(a.ctypes.data_as(C.c_void_p), w, h, buf, cap, C.byref(n), int(level)), "kbn_png_encode_gray16")
-    return bytes(memoryview(buf)[:n.value])
+    return bytes(_encode_png("gray16", a, a.shape[1], a.shape[0], level))
 
 
 def depth_samples(z) -> np.ndarray:
@@ -178,6 +241,173 @@ def save_depth_batch(z: torch.Tensor, paths: Sequence[str], threads: int = 8) ->
 
     with ThreadPoolExecutor(max_workers=max(1, int(threads))) as ex:
         list(ex.map(one, range(len(paths))))
+
+
+OUTPUT_DIRECTORIES = ("image", "output_depth", "sparse_depth", "ground_truth")     # reference src/kbnet.py:991-1001
+
+
+def image_export_affine(normalized_image_range) -> Tuple[float, float]:
+    """(scale, shift) that turn an image normalised to this range (ops.preprocess) back into 0..255: [0, 1] -> (255, 0), the
+    reference's `255 * image`; [-1, 1] -> (127.5, 127.5); [0, 255] -> (1, 0).  For the last two the reference still multiplies by
+    255 and casts what no longer fits a uint8; its files hold garbage there.  Any other range: ValueError, as ops.preprocess."""
+    rng = [float(v) for v in normalized_image_range]
+    if rng == [0.0, 1.0]:
+        return 255.0, 0.0
+    if rng == [-1.0, 1.0]:
+        return 127.5, 127.5
+    if rng == [0.0, 255.0]:
+        return 1.0, 0.0
+    raise ValueError("Unsupported normalization range: {}".format(list(normalized_image_range)))
+
+
+class OutputWriter:
+    """The files run_kbnet.py --save_outputs stores (reference src/kbnet.py:986-1026), written WHILE the run proceeds: per frame
+    image/<name> (8-bit RGB), output_depth/<name>, sparse_depth/<name> and, where given, ground_truth/<name> (16-bit gray,
+    depth * 256) under `output_path`.  All four directories are made on construction, ground_truth too when it stays empty, as in
+    the reference.
+
+    submit() costs the caller one kernel launch and no wait for the device:
+      1. ONE ops.export_pack launch on torch's current stream turns the three float tensors (20 bytes a pixel) into the files'
+         pixels (7 bytes a pixel) in a device buffer of the writer's own;
+      2. an event is recorded there; the writer's side stream waits for it and copies the 7 bytes a pixel into one of `in_flight`
+         pinned host slots;
+      3. `threads` (at most 16) host threads wait for the slot's copy, encode (kbn_png_encode_rgb8 / _gray16: ctypes drops the
+         interpreter lock) and write the files.
+    A slot -- its device buffer and its pinned buffer -- is used again only after all its files are written; that is the only wait
+    submit() knows, and it is a wait for host threads.
+
+    What was handed to submit() may be freed or overwritten by the caller as soon as it returns: the pack has READ the device
+    tensors in stream order on the stream the caller goes on using (later kernels and the allocator's reuse are ordered behind
+    it), everything downstream reads the writer's own packed buffer, and `ground_truth_samples` is copied into the slot before
+    submit() returns.
+
+    close() waits for everything and raises the first error a thread met; the object is a context manager.  One writer is driven
+    by one thread."""
+
+    def __init__(self, output_path: str, threads: int = 8, in_flight: int = 2, level: int = 6, normalized_image_range=(0, 1)):
+        self.scale, self.shift = image_export_affine(normalized_image_range)
+        if not -1 <= int(level) <= 9:
+            raise KbnError(f"OutputWriter: zlib level {level} (-1 .. 9)")
+        self.level = int(level)
+        self.output_path = output_path
+        self.dirpaths = {name: os.path.join(output_path, name) for name in OUTPUT_DIRECTORIES}
+        for dirpath in self.dirpaths.values():
+            if not os.path.exists(dirpath):
+                os.makedirs(dirpath)
+        self.threads = max(1, min(16, int(threads)))
+        self.pool = ThreadPoolExecutor(max_workers=self.threads)
+        self._slots = [{"key": None, "files": []} for _ in range(max(1, int(in_flight)))]
+        self._serial = 0
+        self._error: Optional[BaseException] = None
+        self._copy_stream = None
+        self._closed = False
+
+    # -- a slot: [rgb | samples of the output | samples of the sparse depth] on the device and pinned, + ground truth (host only) --
+    def _slot(self, device, n: int, h: int, w: int) -> dict:
+        slot = self._slots[self._serial % len(self._slots)]
+        self._serial += 1
+        self._drain(slot)
+        key = (device, n, h, w)
+        if slot["key"] is None or slot["key"][0] != device or slot["key"][2:] != (h, w) or slot["key"][1] < n:
+            px = n * h * w
+            at_a = _align16(3 * px)
+            at_b = _align16(at_a + 2 * px)
+            slot.update(key=key, at=(at_a, at_b), device=torch.empty(at_b + 2 * px, dtype=torch.uint8, device=device),
+                        host=torch.empty(at_b + 2 * px, dtype=torch.uint8).pin_memory(), truth=np.empty((n, h, w), dtype=np.uint16))
+            slot["device"].record_stream(self._copy_stream)      # the allocator learns that the side stream reads it
+        return slot
+
+    def _drain(self, slot: dict) -> None:
+        for f in slot["files"]:
+            e = f.exception()
+            if e is not None and self._error is None:
+                self._error = e
+        slot["files"] = []
+
+    def _views(self, slot: dict, n: int, h: int, w: int, which: str):
+        capacity = slot["key"][1]
+        px = capacity * h * w
+        at_a, at_b = slot["at"]
+        flat = slot[which]
+        return (flat[:3 * px].view(capacity, h, w, 3)[:n], flat[at_a:at_a + 2 * px].view(torch.int16).view(capacity, h, w)[:n],
+                flat[at_b:at_b + 2 * px].view(torch.int16).view(capacity, h, w)[:n])
+
+    def submit(self, filenames: Sequence[str], image, output_depth, sparse_depth, ground_truth_samples=None) -> None:
+        """One batch: image N x 3 x H x W as ops.preprocess normalised it, output_depth and sparse_depth N x 1 x H x W (device,
+        fp32); filenames: N base names; ground_truth_samples: host uint16 N x H x W, the PNG samples as they are, or None."""
+        if self._closed:
+            raise KbnError("OutputWriter: submit() after close()")
+        for name, t in (("image", image), ("output_depth", output_depth), ("sparse_depth", sparse_depth)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise KbnError(f"OutputWriter: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+        n, h, w = int(image.shape[0]), int(image.shape[-2]), int(image.shape[-1])
+        if len(filenames) != n:
+            raise KbnError(f"OutputWriter: {n} frames, {len(filenames)} file names")
+        truth = None
+        if ground_truth_samples is not None:
+            truth = np.asarray(ground_truth_samples)
+            if truth.dtype != np.uint16 or truth.shape != (n, h, w):
+                raise KbnError(f"OutputWriter: ground_truth_samples is {truth.dtype} {truth.shape}, expected uint16 {(n, h, w)}")
+        device = image.device
+        with torch.cuda.device(device):
+            if self._copy_stream is None or self._copy_stream.device != device:
+                self._copy_stream = torch.cuda.Stream(device=device)
+            slot = self._slot(device, n, h, w)
+            packed = self._views(slot, n, h, w, "device")
+            ops.export_pack(image, output_depth, sparse_depth, scale=self.scale, shift=self.shift, out=packed)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(device))
+            self._copy_stream.wait_event(ready)
+            used = slot["at"][1] + 2 * slot["key"][1] * h * w if n == slot["key"][1] else None
+            with torch.cuda.stream(self._copy_stream):
+                if used is not None:      # a full slot: its three parts are one range, one copy
+                    slot["host"][:used].copy_(slot["device"][:used], non_blocking=True)
+                else:                     # a short batch in a larger slot: the used head of each part
+                    for dst, src in zip(self._views(slot, n, h, w, "host"), packed):
+                        dst.copy_(src, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+        if truth is not None:
+            np.copyto(slot["truth"][:n], truth)
+        rgb, out_s, sparse_s = (t.numpy() for t in self._views(slot, n, h, w, "host"))
+        jobs = []
+        for i, filename in enumerate(filenames):
+            jobs.append(("rgb8", rgb[i], self.dirpaths["image"], filename))
+            jobs.append(("gray16", out_s[i].view(np.uint16), self.dirpaths["output_depth"], filename))
+            jobs.append(("gray16", sparse_s[i].view(np.uint16), self.dirpaths["sparse_depth"], filename))
+            if truth is not None:
+                jobs.append(("gray16", slot["truth"][i], self.dirpaths["ground_truth"], filename))
+        slot["files"] = [self.pool.submit(self._write, done, h, w, *job) for job in jobs]
+
+    def _write(self, done, h: int, w: int, kind: str, pixels: np.ndarray, dirpath: str, filename: str) -> None:
+        done.synchronize()      # the slot's copy has landed (returns at once for all but the first file of a batch)
+        data = _encode_png(kind, pixels, w, h, self.level)
+        with open(os.path.join(dirpath, filename), "wb") as f:
+            f.write(data)
+
+    def close(self) -> None:
+        """Waits for every file; raises the first error a thread met (once)."""
+        if not self._closed:
+            self._closed = True
+            for slot in self._slots:
+                self._drain(slot)
+            self.pool.shutdown(wait=True)
+        error, self._error = self._error, None
+        if error is not None:
+            raise error
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:           # the body failed: finish quietly, its exception is the one to see
+            try:
+                self.close()
+            except Exception:      # noqa: BLE001
+                pass
+        return False
 
 
 # ------------------------------------------------------------------- batched device loader

@@ -1262,6 +1262,77 @@ def unpack_frames(image_u8, depth_raw, width: Optional[int] = None, x_offset: in
     return image, depth
 
 
+@_on_tensor_device
+def export_pack(image=None, depth_a=None, depth_b=None, scale: float = 255.0, shift: float = 0.0, out=None):
+    """The pixels of a batch's output files in ONE launch (kbn_export_pack_forward, csrc/export_pack.hip) -> (rgb, samples_a,
+    samples_b), None where the source was None:
+      image N x 3 x H x W fp32 -> rgb N x H x W x 3 uint8, interleaved: clamp(trunc(scale * v + shift), 0, 255), NaN -> 0, product and
+        sum each rounded to fp32.  (255, 0) on a [0, 1] image is the reference's `(255 * image).astype(np.uint8)` (src/kbnet.py:1015);
+        (127.5, 127.5) serves a [-1, 1] image, (1, 0) a [0, 255] one.
+      depth_a, depth_b N x 1 x H x W (or N x H x W) fp32 -> N x H x W int16 holding the uint16 bit patterns min(trunc(z * 256), 65535),
+        NaN and negatives 0 -- loader.depth_samples' values (view the host copy as np.uint16).
+    Inputs are made dense here.  `out`: (rgb, samples_a, samples_b) to write into -- dense device tensors of those shapes and
+    dtypes, views of larger buffers welcome, None where the source is None.  CPU tensors raise KbnError (no CPU fallback), so do
+    shapes that disagree, naming the offender."""
+    fn = "export_pack"
+    given = [("image", image), ("depth_a", depth_a), ("depth_b", depth_b)]
+    if all(t is None for _, t in given):
+        raise KbnError(f"{fn}: nothing to pack")
+    dense, shape = [], None
+    for name, t in given:
+        if t is None:
+            dense.append(None)
+            continue
+        _require(t, f"{fn}: {name}")
+        t = t.detach()
+        if name == "image":
+            if t.dim() != 4 or t.shape[1] != 3:
+                raise KbnError(f"{fn}: image has shape {tuple(t.shape)}, expected N x 3 x H x W")
+            nhw = (t.shape[0], t.shape[2], t.shape[3])
+        else:
+            if t.dim() == 4 and t.shape[1] == 1:
+                nhw = (t.shape[0], t.shape[2], t.shape[3])
+            elif t.dim() == 3:
+                nhw = tuple(t.shape)
+            else:
+                raise KbnError(f"{fn}: {name} has shape {tuple(t.shape)}, expected N x 1 x H x W or N x H x W")
+        if shape is None:
+            shape, first = nhw, name
+        elif nhw != shape:
+            raise KbnError(f"{fn}: {name} has shape {tuple(t.shape)}: its N, H, W {nhw} differ from {first}'s {shape}")
+        dense.append(t.contiguous())
+    n, h, w = (int(v) for v in shape)
+    if n < 1 or h < 1 or w < 1:
+        raise KbnError(f"{fn}: empty batch or frame ({n} x {h} x {w})")
+    device = next(t for t in dense if t is not None).device
+    want = [((n, h, w, 3), torch.uint8), ((n, h, w), torch.int16), ((n, h, w), torch.int16)]
+    if out is None:
+        out = (None, None, None)
+    if len(out) != 3:
+        raise KbnError(f"{fn}: out is (rgb, samples_a, samples_b), got {len(out)} entries")
+    outs = []
+    for (name, _), src, o, (oshape, dtype), oname in zip(given, dense, out, want, ("rgb", "samples_a", "samples_b")):
+        if src is None:
+            if o is not None:
+                raise KbnError(f"{fn}: out has {oname} but no {name} was passed")
+            outs.append(None)
+        elif o is None:
+            outs.append(torch.empty(oshape, device=device, dtype=dtype))
+        else:
+            if not isinstance(o, torch.Tensor) or not o.is_cuda or o.device != device:
+                raise KbnError(f"{fn}: out {oname}: expected a tensor on {device} (the HIP path has no CPU fallback)")
+            if o.dtype != dtype or tuple(o.shape) != oshape or not o.is_contiguous():
+                raise KbnError(f"{fn}: out {oname} is {o.dtype} {tuple(o.shape)}, expected a contiguous {dtype} {oshape}")
+            outs.append(o)
+    ptr = [t.data_ptr() if t is not None else None for t in dense + outs]
+    lib = _lib.load()
+    sources = sum(1 for t in dense[1:] if t is not None)
+    check(_launch("export_pack", 0.0,
+                  lambda: lib.kbn_export_pack_forward(ptr[0], float(scale), float(shift), ptr[1], ptr[2], ptr[3], ptr[4], ptr[5], n, h, w, _stream()),
+                  nbytes=float(n * h * w) * ((15 if dense[0] is not None else 0) + 6 * sources)), "kbn_export_pack_forward")
+    return tuple(outs)
+
+
 _TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
 
 

@@ -1001,6 +1001,29 @@ size_t kbn_png_encode_gray16_bound(int width, int height);
 int kbn_png_encode_gray16(const unsigned short* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                           size_t* out_bytes, int level);
 
+/* The whole export of a batch (src/kbnet.py:1007-1026: the normalised image as an 8-bit RGB PNG, two depth maps as 16-bit PNGs).
+ *   kbn_export_pack_forward  DEVICE, ONE launch for all sources of the batch:
+ *       image    n x 3 x height x width float32, dense, or NULL  ->  rgb n x height x width x 3 uint8, interleaved:
+ *                clamp(trunc(scale * v + shift), 0, 255), NaN -> 0; product and sum each rounded to fp32 (no FMA), so float32 NumPy
+ *                reproduces the bytes.  (255, 0) on an image in [0, 1] is the reference's (255 * image).astype(np.uint8), bit for
+ *                bit; (127.5, 127.5) and (1, 0) give back the picture for the [-1, 1] and [0, 255] ranges (the reference's cast of
+ *                those leaves the uint8 range: its files hold garbage there)
+ *       depth_a, depth_b  n x 1 x height x width float32, dense, either or both NULL  ->  samples_a / samples_b n x height x width
+ *                uint16 by kbn_depth_to_u16_forward's rule
+ *     A thread owns 4 consecutive pixels of a row: 16-byte loads when width % 4 == 0 and all pointers are 16-byte aligned, scalar
+ *     loads and stores otherwise.  Every output byte is written once; nothing but the n*h*w*3 / n*h*w*2 bytes is touched.
+ *     KBN_ERR_INVALID_ARGUMENT, before anything is launched: an output without its source or a source without its output, nothing
+ *     to do at all, n, height or width < 1.
+ *   kbn_png_encode_rgb8      HOST: height x width x 3 interleaved uint8 -> a PNG file image, under kbn_png_encode_gray16's contract
+ *                            (one IDAT, filter 0, level -1 .. 9, thread-safe, no GPU work; KBN_ERR_WORKSPACE when out_capacity <
+ *                            kbn_png_encode_rgb8_bound(width, height)). */
+int kbn_export_pack_forward(const float* image, float scale, float shift, const float* depth_a, const float* depth_b,
+                            unsigned char* rgb, unsigned short* samples_a, unsigned short* samples_b, int n, int height, int width,
+                            kbn_stream_t stream);
+size_t kbn_png_encode_rgb8_bound(int width, int height);
+int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                        size_t* out_bytes, int level);
+
 /* Decoded pixels (device buffers) -> the tensors the reference's dataset returns:
  *   image_u8     N x height x raw_width x image_channels uint8 (1 gray, 3 RGB, 4 RGBA); columns
  *                [x_offset, x_offset + width) are taken (x_offset = width, raw_width = 3 * width for

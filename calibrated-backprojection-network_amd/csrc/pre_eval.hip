@@ -118,8 +118,9 @@ __global__ __launch_bounds__(256) void eval_kernel(const float* __restrict__ pre
         const float gg = g[i];
         if (v[i] > 0.f && gg > dmin && gg < dmax) {
             const float o = p[i];
-            const float e = 1000.0f * o - 1000.0f * gg;          // fp32 like the numpy reference
-            const float ie = 1.0f / (0.001f * gg) - 1.0f / (0.001f * o);
+            // fp32 like the numpy reference: every product rounded before the subtraction, whatever -ffp-contract allows
+            const float e = __fsub_rn(__fmul_rn(1000.0f, o), __fmul_rn(1000.0f, gg));
+            const float ie = __fsub_rn(1.0f / __fmul_rn(0.001f, gg), 1.0f / __fmul_rn(0.001f, o));
             acc[0] += fabsf(e);
             acc[1] += (double)(e * e);
             acc[2] += fabsf(ie);

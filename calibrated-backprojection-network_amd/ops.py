@@ -1402,7 +1402,9 @@ def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, 
 def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate_depth: float,
                  max_evaluate_depth: float):
     """Per-frame (MAE [mm], RMSE [mm], iMAE [1/km], iRMSE [1/km]) as an N x 4 fp64 tensor, computed on
-    the device (reference src/kbnet.py:932-950 does this on the host after a D2H copy)."""
+    the device (reference src/kbnet.py:932-950 does this on the host after a D2H copy).  A frame in which no pixel passes the mask
+    (validity > 0, min < ground truth < max) gives four NaNs, as the reference's np.mean over an empty selection does; a mean over
+    the rows (inference.run, validation.validate) is then NaN exactly where the reference's is."""
     lib = _lib.load()
     o = output_depth.contiguous()
     _require(o, "output_depth")
@@ -1417,8 +1419,7 @@ def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate
     check(lib.kbn_eval_accumulate(o.data_ptr(), g.data_ptr(), v.data_ptr(), sums.data_ptr(), n, h, w,
                                   float(min_evaluate_depth), float(max_evaluate_depth), _stream()),
           "kbn_eval_accumulate")
-    cnt = sums[:, 4:5].clamp_min(1.0)
-    mean = sums[:, :4] / cnt
+    mean = sums[:, :4] / sums[:, 4:5]      # 0 / 0: a frame without an evaluated pixel is NaN, as np.mean of nothing is
     return torch.stack([mean[:, 0], mean[:, 1].sqrt(), mean[:, 2], mean[:, 3].sqrt()], dim=1)
 
 

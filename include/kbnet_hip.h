@@ -547,7 +547,12 @@ int kbn_preprocess_forward(const float* image, const float* sparse_depth, float*
  * over the pixels with ground_truth_validity > 0 and min < ground_truth < max.  ADDS into
  * sums[n*5 + k] (fp64, caller zeroes): k=0 sum|1000(o-g)|, 1 sum(1000(g-o))^2,
  * 2 sum|1/(.001g) - 1/(.001o)|, 3 its square, 4 pixel count.  MAE = s0/s4 (mm),
- * RMSE = sqrt(s1/s4), iMAE = s2/s4 (1/km), iRMSE = sqrt(s3/s4). */
+ * RMSE = sqrt(s1/s4), iMAE = s2/s4 (1/km), iRMSE = sqrt(s3/s4).  The bounds are strict and a NaN validity or
+ * ground truth counts nothing; what a masked-out pixel holds (NaN, inf) is never read into a sum.  Every per-pixel
+ * term is formed in fp32 with each product and the difference rounded on its own (no FMA contraction), as numpy
+ * forms it; only the sums are fp64.  A frame in which no pixel passes the mask leaves s4 = 0: the caller divides
+ * 0 by 0 and reports NaN there, as the reference's np.mean over an empty selection does (ops.eval_metrics does so;
+ * inference.run and validation.validate then report NaN means exactly where the reference's are NaN). */
 int kbn_eval_accumulate(const float* output_depth, const float* ground_truth,
                         const float* ground_truth_validity, double* sums, int n, int height,
                         int width, float min_evaluate_depth, float max_evaluate_depth,

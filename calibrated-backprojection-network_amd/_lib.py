@@ -33,6 +33,7 @@ KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_for
 KBN_SUMMARY_CELL_ZERO, KBN_SUMMARY_CELL_COPY, KBN_SUMMARY_CELL_PHOTO_ERR, KBN_SUMMARY_CELL_DEPTH, KBN_SUMMARY_CELL_REL_ERR = 0, 1, 2, 3, 4
 KBN_SUMMARY_COLORMAP_VIRIDIS, KBN_SUMMARY_COLORMAP_INFERNO = 0, 1
 KBN_SUMMARY_MAX_ROWS = 4   # rows of a kbn_summary_panel_forward panel
+KBN_HISTOGRAM_POSITIVE_EDGES, KBN_HISTOGRAM_BINS, KBN_HISTOGRAM_WORKSPACE_BYTES = 774, 1548, 32768   # kbn_histogram_forward's table, counts, workspace
 ABI_VERSION = 11
 
 
@@ -260,6 +261,8 @@ SIGNATURES = {
     "kbn_png_encode_rgb8": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
     "kbn_unpack_frames_forward":(_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "kbn_unpack_train_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(TrainFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "kbn_histogram_forward": (_I, [_P, _L, _P, _P, _P, _P, C.c_size_t, _P]),
+    "kbn_crc32c": (C.c_uint, [C.c_char_p, C.c_size_t, C.c_uint]),
 }
 
 _lib = None

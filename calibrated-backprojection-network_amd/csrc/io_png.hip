@@ -347,4 +347,32 @@ int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsi
     }
 }
 
+// CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of the records of an event file (kb.summary.EventWriter); zlib's crc32 is
+// the other polynomial.  Eight bytes a step through eight tables built on first use.
+unsigned int kbn_crc32c(const unsigned char* data, size_t bytes, unsigned int crc) {
+    struct Tables {
+        uint32_t t[8][256];
+        Tables() {
+            for (uint32_t i = 0; i < 256; ++i) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0x82F63B78u : 0u);
+                t[0][i] = c;
+            }
+            for (uint32_t i = 0; i < 256; ++i)
+                for (int s = 1; s < 8; ++s) t[s][i] = (t[s - 1][i] >> 8) ^ t[0][t[s - 1][i] & 0xffu];
+        }
+    };
+    static const Tables tables;
+    if (!data) return crc;
+    uint32_t c = ~crc;
+    size_t i = 0;
+    for (; i + 8 <= bytes; i += 8) {
+        const uint32_t lo = c ^ ((uint32_t)data[i] | ((uint32_t)data[i + 1] << 8) | ((uint32_t)data[i + 2] << 16) | ((uint32_t)data[i + 3] << 24));
+        c = tables.t[7][lo & 0xffu] ^ tables.t[6][(lo >> 8) & 0xffu] ^ tables.t[5][(lo >> 16) & 0xffu] ^ tables.t[4][lo >> 24] ^
+            tables.t[3][data[i + 4]] ^ tables.t[2][data[i + 5]] ^ tables.t[1][data[i + 6]] ^ tables.t[0][data[i + 7]];
+    }
+    for (; i < bytes; ++i) c = (c >> 8) ^ tables.t[0][(c ^ data[i]) & 0xffu];
+    return ~c;
+}
+
 }  // extern "C"

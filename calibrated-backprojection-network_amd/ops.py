@@ -3163,3 +3163,55 @@ def summary_colorize(x: torch.Tensor, colormap: str) -> torch.Tensor:
         check(_lib.load().kbn_summary_colorize_forward(part.data_ptr(), part.stride(0), part.stride(2), part.stride(3), part.shape[0], h, w,
                                                        SUMMARY_COLORMAPS[colormap], out[first:].data_ptr(), _stream()), "kbn_summary_colorize_forward")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ TensorBoard's histogram
+HISTOGRAM_BINS = _lib.KBN_HISTOGRAM_BINS
+_HISTOGRAM_EDGES = None
+_HISTOGRAM_TABLES = {}    # device index -> (the positive edges as a float64 device tensor, the workspace)
+
+
+def histogram_edges():
+    """The 1549 bucket edges of SummaryWriter.add_histogram(bins='tensorflow') as a tuple of Python floats: 1e-12 multiplied by 1.1
+    again and again while below 1e20 (float64, repeated multiplication -- not a power), mirrored negative, 0 between."""
+    global _HISTOGRAM_EDGES
+    if _HISTOGRAM_EDGES is None:
+        positive = []
+        v = 1e-12
+        while v < 1e20:
+            positive.append(v)
+            v *= 1.1
+        _HISTOGRAM_EDGES = tuple([-e for e in reversed(positive)] + [0.0] + positive)
+        assert len(positive) == _lib.KBN_HISTOGRAM_POSITIVE_EDGES and len(_HISTOGRAM_EDGES) == HISTOGRAM_BINS + 1
+    return _HISTOGRAM_EDGES
+
+
+@_on_tensor_device
+def histogram_tensorflow(values: torch.Tensor):
+    """TensorBoard's default histogram of an fp32 device tensor (kbn_histogram_forward, csrc/histogram.hip) -> (counts, stats):
+    counts HISTOGRAM_BINS int32 = np.histogram(values.astype(float), bins=histogram_edges())[0], stats 4 float64 = min, max (NaN
+    propagates), sum, sum of squares over all values.  Both are views of ONE device buffer of 6224 bytes (`counts._base`); nothing is
+    copied to the host and nothing waits for the device.  Any view is accepted: a view that is not contiguous is copied to a dense
+    tensor first, a contiguous one is read in place with 16-byte loads from its first 16-byte boundary on.  An empty tensor raises
+    ValueError('The input has no element.') as TensorBoard does, a CPU tensor KbnError (no CPU fallback).  Two calls give the same
+    bits.  The calls of one device share the edge table and a 32 KB workspace: issue them on one stream, torch's current one."""
+    fn = "histogram_tensorflow"
+    _require(values, f"{fn}: values")
+    n = values.numel()
+    if n == 0:
+        raise ValueError("The input has no element.")
+    x = values.detach().contiguous()
+    index = x.device.index
+    if index not in _HISTOGRAM_TABLES:
+        positive = histogram_edges()[_lib.KBN_HISTOGRAM_POSITIVE_EDGES + 1:]
+        _HISTOGRAM_TABLES[index] = (torch.tensor(positive, dtype=torch.float64).to(x.device),
+                                    torch.empty(_lib.KBN_HISTOGRAM_WORKSPACE_BYTES // 8, dtype=torch.float64, device=x.device))
+    table, workspace = _HISTOGRAM_TABLES[index]
+    out = torch.empty(HISTOGRAM_BINS + 8, dtype=torch.int32, device=x.device)
+    counts, stats = out[:HISTOGRAM_BINS], out[HISTOGRAM_BINS:].view(torch.float64)
+    lib = _lib.load()
+    check(_launch("histogram", 0.0,
+                  lambda: lib.kbn_histogram_forward(x.data_ptr(), n, table.data_ptr(), counts.data_ptr(), stats.data_ptr(), workspace.data_ptr(),
+                                                    workspace.numel() * 8, _stream()),
+                  nbytes=4.0 * n), "kbn_histogram_forward")
+    return counts, stats

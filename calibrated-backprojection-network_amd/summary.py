@@ -13,7 +13,11 @@
 The reference copies every tensor to the host, colourises frame by frame through matplotlib, concatenates on the CPU and calls
 torchvision.utils.make_grid.  Here a panel is one kernel launch and stays on the device; the writer -- any object with add_image,
 add_histogram and add_scalar, TensorBoard's SummaryWriter among them -- is handed device tensors and decides when they leave it.
-Neither tensorboard, matplotlib nor torchvision is imported."""
+Neither tensorboard, matplotlib nor torchvision is imported.
+
+    torch.utils.tensorboard.SummaryWriter       EventWriter (events.py): the same event files written by hand; a histogram is a HIP
+                                                kernel over the tensor where it lies (ops.histogram_tensorflow), an image one pack
+                                                launch, and what leaves the device is copied behind the caller's stream"""
 
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import os
 import torch
 
 from . import ops
+from .events import EventWriter  # noqa: F401  (events.py: the writer kb.training.train opens)
 
 COLORMAPS = tuple(ops.SUMMARY_COLORMAPS)   # the maps log_summary uses: 'viridis' (depths) and 'inferno' (errors)
 

@@ -1073,6 +1073,30 @@ int kbn_unpack_train_frames_forward(const unsigned char* images, size_t image_by
                                     const kbn_train_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
                                     float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
 
+/* TensorBoard's default histogram of an fp32 device tensor -- what SummaryWriter.add_histogram(bins='tensorflow') computes on the
+ * host, np.histogram(values.astype(float), bins=edges) with min, max, sum and values.dot(values) -- in one pass (csrc/histogram.hip).
+ *   x               n float32, dense, 4-byte aligned (16-byte loads from the first 16-byte boundary on)
+ *   positive_edges  DEVICE: the KBN_HISTOGRAM_POSITIVE_EDGES positive edges as float64, increasing -- v = 1e-12; while v < 1e20:
+ *                   append v, v *= 1.1 in float64, by repeated multiplication.  The edges are these, mirrored negative, 0 between:
+ *                   E[774] = 0, E[775 + k] = P[k], E[773 - k] = -P[k]
+ *   counts          KBN_HISTOGRAM_BINS int32: bin i counts the x, widened to float64, with E[i] <= x < E[i + 1]; the last bin is
+ *                   closed on the right; x outside [E[0], E[1548]], NaN and +-inf are counted in no bin
+ *   stats           4 float64: min, max (NaN propagates, as np.min / np.max), sum, sum of squares, all over ALL n values
+ *   workspace       KBN_HISTOGRAM_WORKSPACE_BYTES device bytes, 8-byte aligned (one record a workgroup)
+ * Two launches behind a memset of `counts`: integer LDS atomics, one integer global add per non-empty bin and workgroup, the float64
+ * sums as per-workgroup records folded by the second launch in a fixed order -- two runs give the same bits.
+ * KBN_ERR_INVALID_ARGUMENT, before anything is launched: a NULL or misaligned pointer, n < 1; KBN_ERR_WORKSPACE: a short
+ * workspace; KBN_ERR_UNSUPPORTED: n > 2^31 - 1 (the counts are 32-bit). */
+#define KBN_HISTOGRAM_POSITIVE_EDGES 774
+#define KBN_HISTOGRAM_BINS 1548
+#define KBN_HISTOGRAM_WORKSPACE_BYTES 32768
+int kbn_histogram_forward(const float* x, long long n, const double* positive_edges, int* counts, double* stats, void* workspace,
+                          size_t workspace_bytes, kbn_stream_t stream);
+
+/* HOST: CRC-32C (Castagnoli) of `bytes` bytes, continued from `crc` (0 to begin): the checksum of an event file's records
+ * (kb.summary.EventWriter).  kbn_crc32c("123456789", 9, 0) == 0xE3069283.  Thread-safe, no GPU work. */
+unsigned int kbn_crc32c(const unsigned char* data, size_t bytes, unsigned int crc);
+
 #ifdef __cplusplus
 }
 #endif

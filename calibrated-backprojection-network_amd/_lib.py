@@ -248,6 +248,7 @@ SIGNATURES = {
     "kbn_multi_tensor_scale_copy": (_I, [C.POINTER(CopyTensor), _I, _F, _P]),
     "kbn_augment_workspace_bytes": (C.c_size_t, [C.POINTER(AugmentTensor), _I, _I, _I, _I]),
     "kbn_augment_forward": (_I, [C.POINTER(AugmentTensor), _I, C.c_char_p, _I, _I, _I, _P, _P, C.c_size_t, _I, _I, _F, C.c_ulonglong, C.c_uint, _I, _P]),
+    "kbn_augment_forward_at": (_I, [C.POINTER(AugmentTensor), _I, C.c_char_p, _I, _I, _I, _P, _P, C.c_size_t, _I, _I, _F, C.c_ulonglong, C.c_uint, C.c_uint, _I, _P]),
     "kbn_summary_panel_forward": (_I, [C.POINTER(SummaryRow), _I, _I, _I, _I, _F, _P, _P]),
     "kbn_summary_colorize_forward": (_I, [_P, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
     "kbn_png_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),

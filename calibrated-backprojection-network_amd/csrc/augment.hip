@@ -3,6 +3,9 @@
 // removal of a fraction of the positive points of the range maps, noise on their remaining points -- with the per-frame decisions
 // made by the caller (a nibble a frame: bit 0 horizontal flip, 1 vertical flip, 2 remove, 3 noise) and every random draw taken
 // from Philox4x32-10 keyed by (seed, element, frame, call, purpose | map << 8), so that a host oracle computes the same bits.
+// `frame` is frame_base + the index in the batch the launch was given (kbn_augment_forward_at): a rank that augments frames
+// [first, first + n) of a global batch passes frame_base = first and draws what one process draws for those frames.  Addressing
+// -- the source and destination frames, the flags nibble, densities[b], the workspace record -- uses the index in the batch.
 //
 // Two launches.
 //   select_kernel   one workgroup of 1024 threads per (frame with the remove flag, range map).  The candidates are the elements
@@ -63,6 +66,7 @@ struct AugParams {
     unsigned flags[KBN_AUGMENT_MAX_FRAMES / 8];   // a nibble a frame of this launch
     const float* densities;                       // N, indexed by the frame's index in the batch
     int frame0;                                   // the batch index of the launch's first frame
+    unsigned frame_base;                          // the batch's first frame in the GLOBAL batch: the Philox frame word is frame_base + b
     int height, width;
     int normalization, noise_type;
     float noise_spread;
@@ -83,10 +87,10 @@ __device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsig
     return {c0, c1, c2, c3};
 }
 __device__ __forceinline__ unsigned removal_key(const AugParams& p, const AugSlot& s, unsigned element, unsigned frame) {
-    return philox4x32_10(element, frame, p.call, 0u | ((unsigned)s.map_index << 8), p.seed_lo, p.seed_hi).w0;
+    return philox4x32_10(element, p.frame_base + frame, p.call, 0u | ((unsigned)s.map_index << 8), p.seed_lo, p.seed_hi).w0;
 }
 __device__ __forceinline__ float noise_draw(const AugParams& p, const AugSlot& s, unsigned element, unsigned frame) {
-    const Philox4 r = philox4x32_10(element, frame, p.call, 1u | ((unsigned)s.map_index << 8), p.seed_lo, p.seed_hi);
+    const Philox4 r = philox4x32_10(element, p.frame_base + frame, p.call, 1u | ((unsigned)s.map_index << 8), p.seed_lo, p.seed_hi);
     if (p.noise_type == KBN_AUGMENT_NOISE_UNIFORM) return __fsub_rn((float)(r.w0 >> 8) * 0x1p-24f, 0.5f);
     const float u1 = (float)((r.w0 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r.w1 >> 8) * 0x1p-24f;
     return __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(u1))), cosf(__fmul_rn(6.283185307179586f, u2)));
@@ -295,11 +299,13 @@ size_t kbn_augment_workspace_bytes(const kbn_augment_tensor* tensors, int count,
     return bytes;
 }
 
-int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
-                        const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
-                        float noise_spread, unsigned long long seed, unsigned call, int stages, kbn_stream_t stream) {
+int kbn_augment_forward_at(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
+                           const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
+                           float noise_spread, unsigned long long seed, unsigned call, unsigned frame_base, int stages,
+                           kbn_stream_t stream) {
     using namespace kbn;
     if (!tensors || !flags || count < 1 || n < 1 || height < 1 || width < 1) return KBN_ERR_INVALID_ARGUMENT;
+    if ((unsigned long long)frame_base + (unsigned long long)n > 0xffffffffull) return KBN_ERR_UNSUPPORTED;   // the frame word is 32 bits
     if (normalization < KBN_AUGMENT_RANGE_0_255 || normalization > KBN_AUGMENT_RANGE_M1_1) return KBN_ERR_INVALID_ARGUMENT;
     if (noise_type < KBN_AUGMENT_NOISE_NONE || noise_type > KBN_AUGMENT_NOISE_UNIFORM) return KBN_ERR_INVALID_ARGUMENT;
     if (!(stages & (KBN_AUGMENT_STAGE_SELECT | KBN_AUGMENT_STAGE_APPLY))) return KBN_ERR_INVALID_ARGUMENT;
@@ -331,6 +337,7 @@ int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsi
     p.height = height; p.width = width;
     p.normalization = normalization; p.noise_type = noise_type; p.noise_spread = noise_spread;
     p.seed_lo = (unsigned)seed; p.seed_hi = (unsigned)(seed >> 32); p.call = call;
+    p.frame_base = frame_base;
     // the workspace: the records of all range maps (16 bytes a frame, in the order of the range maps), then their candidate lists
     auto fill = [&](AugSlot& s, const kbn_augment_tensor& t, int range_ordinal) {
         s.src = t.src; s.dst = t.dst;
@@ -396,6 +403,13 @@ int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsi
     }
     KBN_CHECK_LAUNCH();
     return KBN_OK;
+}
+
+int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
+                        const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
+                        float noise_spread, unsigned long long seed, unsigned call, int stages, kbn_stream_t stream) {
+    return kbn_augment_forward_at(tensors, count, flags, n, height, width, densities, workspace, workspace_bytes, normalization, noise_type,
+                                  noise_spread, seed, call, 0u, stages, stream);
 }
 
 }  // extern "C"

@@ -465,3 +465,57 @@ def mean_metrics_over_ranks(per_frame: torch.Tensor) -> torch.Tensor:
     acc[4] = per_frame.shape[0]
     sum_over_ranks(acc)
     return acc[:4] / acc[4].clamp_min(1.0)
+
+
+# ------------------------------------------------------------------------------------ what kb.training.train_ranks(rank, world) adds
+def broadcast_rng_state(src: int = 0) -> None:
+    """Rank `src`'s random state becomes everybody's: NumPy's global state, torch's CPU generator and the generator of the current
+    HIP device (where one is visible), in one broadcast_object_list.  After it the ranks draw the same np.random and torch.rand
+    numbers -- what Transforms.transform(shard=...) and TrainingFrameLoader(crops="global") need to build, between them, the batch
+    one process builds.  torch.initial_seed() is not part of a generator's state: pass rank `src`'s Transforms.seed explicitly
+    (kb.training.train_ranks does).  Nothing happens without a process group."""
+    if not dist.is_initialized():
+        return
+    import numpy as np
+    on_device = torch.cuda.is_available()
+    state = [None]
+    if dist.get_rank() == int(src):
+        state = [(np.random.get_state(), torch.get_rng_state(), torch.cuda.get_rng_state() if on_device else None)]
+    dist.broadcast_object_list(state, src=int(src))
+    if dist.get_rank() != int(src):
+        numpy_state, cpu_state, device_state = state[0]
+        np.random.set_state(numpy_state)
+        torch.set_rng_state(cpu_state)
+        if on_device and device_state is not None:
+            torch.cuda.set_rng_state(device_state)
+
+
+def broadcast_object(value, src: int = 0):
+    """Rank `src`'s picklable `value` on every rank (itself without a process group)."""
+    if not dist.is_initialized():
+        return value
+    box = [value if dist.get_rank() == int(src) else None]
+    dist.broadcast_object_list(box, src=int(src))
+    return box[0]
+
+
+def gather_frames(tensor: torch.Tensor, n_global: int, rank: int, world: int) -> torch.Tensor:
+    """This rank's `shard_bounds` frames of a global batch -> all n_global frames, in rank order -- which is batch order, the shards
+    being contiguous -- on every rank: one all_gather_into_tensor through slots of the largest shard's size.  For the summaries of
+    kb.training.train_ranks, every n_summary steps; not a hot path.  `tensor` itself (detached) when world == 1."""
+    tensor = tensor.detach()
+    if int(world) == 1:
+        return tensor
+    lo, hi = shard_bounds(int(n_global), int(rank), int(world))
+    if tensor.shape[0] != hi - lo:
+        raise KbnError(f"gather_frames: rank {rank} holds {tensor.shape[0]} frames, shard_bounds gives {hi - lo} of {n_global}")
+    per = -(-int(n_global) // int(world))
+    slot = torch.zeros((per,) + tuple(tensor.shape[1:]), device=tensor.device, dtype=tensor.dtype)
+    slot[:hi - lo] = tensor
+    out = torch.empty((int(world) * per,) + tuple(tensor.shape[1:]), device=tensor.device, dtype=tensor.dtype)
+    dist.all_gather_into_tensor(out.view(-1), slot.view(-1))      # flat: gloo chunks it by rank
+    parts = []
+    for r in range(int(world)):
+        lo, hi = shard_bounds(int(n_global), r, int(world))
+        parts.append(out[r * per:r * per + (hi - lo)])
+    return torch.cat(parts, dim=0)

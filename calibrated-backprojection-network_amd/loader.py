@@ -541,6 +541,14 @@ def draw_crop(o_height: int, o_width: int, shape, crop_type=("none",)) -> Tuple[
     return int(y_start), int(x_start)
 
 
+def draw_crops(sizes, shape, crop_type=("none",), keep=None) -> List[Tuple[int, int]]:
+    """draw_crop for every (height, width) of `sizes`, in order: the crops of one batch.  `keep` (first, last): all of them are
+    drawn -- np.random advances as for the whole batch -- and those of sizes[first:last] are returned: what a rank of a
+    data-parallel run keeps of its global batch's draws (TrainingFrameLoader(crops="global"))."""
+    starts = [draw_crop(hh, ww, shape, crop_type) for hh, ww in sizes]
+    return starts if keep is None else starts[int(keep[0]):int(keep[1])]
+
+
 def _crop_intrinsics(intrinsics: np.ndarray, y_start: int, x_start: int) -> np.ndarray:
     """The reference's expression (src/datasets.py:152-154), evaluated as NumPy evaluates it there (the list becomes a float64
     array; adding 0.0 to the other seven entries turns a -0.0 into 0.0); the caller casts to float32."""
@@ -599,14 +607,25 @@ class TrainingFrameLoader:
     Data-parallel training (`rank`, `world`; kb.dist.GradientAverager): every rank iterates the same `len()` GLOBAL batches and is
     handed its shard of each (`shard_batches`), `global_batch_size(b)` frames in all.  The epoch's order is drawn as above on every
     rank and, when a process group exists, replaced by rank 0's (one broadcast_object_list an epoch), so the ranks need no equally
-    seeded generators.  The crops are drawn for the rank's own samples only.  A rank whose shard of a short last batch is empty is
-    handed the five tensors with zero frames; nothing is launched for them."""
+    seeded generators.  A rank whose shard of a short last batch is empty is handed the five tensors with zero frames; nothing is
+    launched for them.
+
+    `crops`: whose crops a rank draws.  "own" (the default): those of its own samples only -- the ranks' batches are then not the
+    one-process batch under any seeds.  "global": the iterating thread calls `draw_crop` for EVERY sample of the global batch, in
+    batch order, and keeps its own (the other samples cost their two 33-byte PNG headers, read once); a rank with an empty shard
+    draws too.  Ranks that start from one np.random state then draw the same crops, and their batches concatenate, in rank order,
+    to the batch one process builds under that state: kb.training.train_ranks(rank, world) uses it.  np.random is shared with whatever
+    else the thread draws between two batches (Transforms.draw), and `prefetch` decides how many batches' crops are drawn ahead
+    of those draws, so the ranks AND the one-process run they are compared with must use the same `prefetch`."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str], intrinsics_paths: Sequence[str],
                  shape=None, random_crop_type=["none"], batch_size: int = 8, shuffle: bool = True,
                  device: Optional[torch.device] = None, workers: int = 8, prefetch: int = 4, generator=None, rank: int = 0,
-                 world: int = 1):
+                 world: int = 1, crops: str = "own"):
         what = "TrainingFrameLoader"
+        if crops not in ("own", "global"):
+            raise KbnError(f"{what}: crops {crops!r}: 'own' or 'global'")
+        self.crops = crops
         if int(world) < 1 or not 0 <= int(rank) < int(world):
             raise KbnError(f"{what}: rank {rank} of world {world}")
         self.rank, self.world = int(rank), int(world)
@@ -658,8 +677,9 @@ class TrainingFrameLoader:
             self._headers[i] = tuple(heads)
         return self._headers[i]
 
-    def _plan(self, idx: Sequence[int]):
-        """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped."""
+    def _plan(self, idx: Sequence[int], keep=None):
+        """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped.
+        `keep` (first, last): `idx` is a global batch, checked and drawn for as a whole; the list holds samples idx[first:last]."""
         heads = [self._header(i) for i in idx]
         (_, _, c, bits), (_, _, cd, dbits) = heads[0]
         if bits != 8 or cd != 1:
@@ -676,7 +696,7 @@ class TrainingFrameLoader:
             sizes.append((hraw, wraw // 3))
         if self.do_random_crop:
             shape = (int(self.shape[0]), int(self.shape[1]))
-            starts = [draw_crop(hh, ww, shape, self.random_crop_type) for hh, ww in sizes]
+            starts = draw_crops(sizes, shape, self.random_crop_type)
         else:
             shape = sizes[0]
             for i, size in zip(idx, sizes):
@@ -684,7 +704,8 @@ class TrainingFrameLoader:
                     raise KbnError(f"TrainingFrameLoader: without a crop shape the frames of a batch must have one size: {self.image_paths[i]} is "
                                    f"{size[0]} x {size[1]}, {self.image_paths[idx[0]]} is {shape[0]} x {shape[1]}")
             starts = [(0, 0)] * len(idx)
-        return [(i, hh, ww, y, x) for i, (hh, ww), (y, x) in zip(idx, sizes, starts)], shape, c, dbits, self.do_random_crop
+        frames = [(i, hh, ww, y, x) for i, (hh, ww), (y, x) in zip(idx, sizes, starts)]
+        return frames if keep is None else frames[keep[0]:keep[1]], shape, c, dbits, self.do_random_crop
 
     # -- on a driver thread: read, decode into pinned memory, async H2D + unpack on the copy stream --
     def _staging(self, slot: int, image_bytes: int, depth_bytes: int, frames: int):
@@ -730,9 +751,16 @@ class TrainingFrameLoader:
         st["done"] = done
         return batch, done
 
-    def _enqueue(self, idx: Sequence[int]):
-        """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn."""
-        if not idx:      # this rank's shard of a short last batch: zero frames, no staging set, nothing launched
+    def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0):
+        """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn.
+        `batch`, `first`: with crops="global" the global batch and where `idx` starts in it."""
+        plan = error = None
+        if batch is not None:      # the whole batch's draws, on every rank, before anything else: an empty shard draws too
+            try:
+                plan = self._plan(batch, (first, first + len(idx)))
+            except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
+                error = e
+        if not idx and error is None:      # this rank's shard of a short last batch: zero frames, no staging set, nothing launched
             h, w = (int(self.shape[0]), int(self.shape[1])) if self.do_random_crop else (0, 0)
             empty: Future = Future()
             empty.set_result((tuple(torch.empty(s, dtype=torch.float32, device=self.device)
@@ -740,11 +768,14 @@ class TrainingFrameLoader:
             return empty
         slot = self._serial % (self.prefetch + 1)
         self._serial += 1
-        try:
-            plan = self._plan(idx)
-        except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
+        if plan is None and error is None:
+            try:
+                plan = self._plan(idx)
+            except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
+                error = e
+        if error is not None:
             failed: Future = Future()
-            failed.set_exception(e)
+            failed.set_exception(error)
             return failed
         return self._driver.submit(self._submit, slot, *plan)
 
@@ -760,12 +791,17 @@ class TrainingFrameLoader:
             torch.distributed.broadcast_object_list(shared, src=0)
             order = shared[0]
         batches = shard_batches(order, self.batch_size, self.rank, self.world)
-        self._pending = pending = [self._enqueue(batches[b]) for b in range(min(self.prefetch, len(batches)))]
+        if self.crops == "global":      # (shard, global batch, the shard's place in it)
+            batches = [(shard, list(order[b * self.batch_size:(b + 1) * self.batch_size]),
+                        shard_bounds(self.global_batch_size(b), self.rank, self.world)[0]) for b, shard in enumerate(batches)]
+        else:
+            batches = [(shard,) for shard in batches]
+        self._pending = pending = [self._enqueue(*batches[b]) for b in range(min(self.prefetch, len(batches)))]
         return self._epoch(batches, pending)
 
     def _epoch(self, batches, pending):
         for b in range(len(batches)):
             batch, done = pending.pop(0).result()
             if b + self.prefetch < len(batches):
-                pending.append(self._enqueue(batches[b + self.prefetch]))
+                pending.append(self._enqueue(*batches[b + self.prefetch]))
             yield batch if done is None else _hand_over(self.device, done, batch)

@@ -2923,7 +2923,7 @@ _AUGMENT_NOISES = {"none": _lib.KBN_AUGMENT_NOISE_NONE, "gaussian": _lib.KBN_AUG
 
 def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], validity_maps: Sequence[torch.Tensor], flags: Sequence[int],
             densities: Optional[torch.Tensor], *, normalized_image_range=(0, 255), noise_type: str = "none", noise_spread: float = 0.0,
-            seed: int = 0, call: int = 0):
+            seed: int = 0, call: int = 0, frame_base: int = 0):
     """The device part of the reference's Transforms.transform (src/transforms.py:61-183) over three lists of N x C x H x W fp32
     tensors (kbn_augment_forward, csrc/augment.hip).  Returns (images, range_maps, validity_maps) as lists of NEW dense tensors; no
     input is written (the reference flips in place).
@@ -2935,6 +2935,11 @@ def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], 
     removal: out = (v + noise_spread * noise) * (v > 0), noise_type 'gaussian' or 'uniform' (anything else ValueError once a frame
     has the bit).  Every random word is Philox4x32-10 of (seed; element, frame, call, purpose | map index << 8): the same
     arguments give the same bits, and tests/transforms_oracle.py computes them on the host.
+
+    frame_base: the tensors are frames [frame_base, frame_base + N) of a larger batch (a rank's shard of a data-parallel step), and
+    the counter's frame word is frame_base + the frame's index here (kbn_augment_forward_at).  With the slices of the larger batch's
+    flags and densities the outputs are, bit for bit, the slices of what one call over the larger batch returns.  0: the frames
+    are the batch.  KbnError when frame_base is negative or frame_base + N exceeds 2^32 - 1.
 
     densities: an fp32 DEVICE tensor of N, needed when a frame has AUGMENT_REMOVE and there is a range map, else None.  It is read
     on the device: the count and k never reach the host.  Inputs may be any views (a view that is not 16-byte aligned or whose rows
@@ -2968,6 +2973,9 @@ def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], 
     flags = [int(f) for f in flags]
     if len(flags) != n or any(f < 0 or f > 15 for f in flags):
         raise KbnError(f"{fn}: flags must hold one value in 0..15 for each of the {n} frames, got {flags}")
+    frame_base = int(frame_base)
+    if frame_base < 0 or frame_base + n > 0xFFFFFFFF:
+        raise KbnError(f"{fn}: frame_base {frame_base} with {n} frames: the frame word of the random counter is 32 bits")
     any_remove = any(f & AUGMENT_REMOVE for f in flags) and bool(lists[1])
     any_noise = any(f & AUGMENT_NOISE for f in flags) and bool(lists[1])
     if noise_type not in ("gaussian", "uniform"):
@@ -3007,16 +3015,16 @@ def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], 
         stream = _stream()
 
         def run(stages):
-            return lib.kbn_augment_forward(table, used, bytes(flags), n, h, w, densities.data_ptr() if any_remove else None,
-                                           workspace.data_ptr() if any_remove else None, workspace.numel() * 8 if any_remove else 0,
-                                           _AUGMENT_RANGES[rng], _AUGMENT_NOISES[noise_type], float(noise_spread),
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, stages, stream)
+            return lib.kbn_augment_forward_at(table, used, bytes(flags), n, h, w, densities.data_ptr() if any_remove else None,
+                                              workspace.data_ptr() if any_remove else None, workspace.numel() * 8 if any_remove else 0,
+                                              _AUGMENT_RANGES[rng], _AUGMENT_NOISES[noise_type], float(noise_spread),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, frame_base, stages, stream)
         if PROFILE is None:
-            check(run(_lib.KBN_AUGMENT_STAGE_SELECT | _lib.KBN_AUGMENT_STAGE_APPLY), "kbn_augment_forward")
+            check(run(_lib.KBN_AUGMENT_STAGE_SELECT | _lib.KBN_AUGMENT_STAGE_APPLY), "kbn_augment_forward_at")
         else:    # one entry-point call a stage, so that each record times one stage
             if any_remove:
-                check(_launch("augment_select", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_SELECT)), "kbn_augment_forward")
-            check(_launch("augment_apply", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_APPLY), nbytes=8.0 * elements), "kbn_augment_forward")
+                check(_launch("augment_select", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_SELECT)), "kbn_augment_forward_at")
+            check(_launch("augment_apply", 0.0, lambda: run(_lib.KBN_AUGMENT_STAGE_APPLY), nbytes=8.0 * elements), "kbn_augment_forward_at")
     return tuple(outs)
 
 

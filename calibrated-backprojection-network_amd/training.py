@@ -12,24 +12,69 @@ around it.
     validate() at batch 1 through a DataLoader              validation.validate over loader.InferenceFrameLoader(val_batch_size)
     loss.item() at every checkpoint                         the same: the loop's only wait for the device
 
-One process, one GPU.  The data-parallel loop stays the documented one (kb.dist.GradientAverager)."""
+    torch.nn.DataParallel over every visible device      train_ranks(rank=, world=): one process per GPU over kb.dist.GradientAverager and
+                                                            BatchNormGroup, the ranks building between them the batch one process
+                                                            builds; launch(n_gpus, ...) starts the processes
+
+train() has the reference's signature and drives one GPU; train_ranks() is the same function with rank, world and
+sync_batch_norm -- train() is train_ranks(world=1).  DESIGN section 8p has the design of the data-parallel form."""
 
 from __future__ import annotations
 
+import hashlib
+import inspect
 import os
+import pickle
+import socket
+import subprocess
+import sys
 import time
 
 import numpy as np
 import torch
 
-from . import loader, optim, summary, transforms, validation
+from . import dist, loader, optim, summary, transforms, validation
 from ._lib import KbnError
 from .modules import KBNetModel, ResNetPoseNetModel
 
 
-def n_train_steps(n_train_sample: int, n_batch: int, learning_schedule) -> int:
-    """reference src/kbnet.py:131-132: the last epoch of the schedule times the batches of an epoch, the last one short or not."""
-    return int(learning_schedule[-1] * np.ceil(n_train_sample / n_batch).astype(np.int32))
+def n_train_steps(n_train_sample: int, n_batch: int, learning_schedule, world: int = 1) -> int:
+    """reference src/kbnet.py:131-132: the last epoch of the schedule times the batches of an epoch, the last one short or not.
+    With `world` ranks a batch of fewer frames than ranks is no step (train_ranks() skips it on every rank), so only the batches that
+    give every rank a frame (dist.every_rank_has_frames) count."""
+    if int(world) == 1:
+        return int(learning_schedule[-1] * np.ceil(n_train_sample / n_batch).astype(np.int32))
+    full, short = divmod(int(n_train_sample), int(n_batch))
+    steps = (full if dist.every_rank_has_frames(n_batch, world) else 0) + (1 if short and dist.every_rank_has_frames(short, world) else 0)
+    return int(learning_schedule[-1] * steps)
+
+
+def replica_digest(models, optimizer) -> str:
+    """SHA-256 over everything a replica of a data-parallel run holds: every parameter and buffer of `models` (their modules'
+    state_dict, BatchNorm running statistics included) and the optimizer's state (steps and moments) and groups, names and bits.
+    Equal on every rank when the replicas are bit-identical; launch() compares the ranks' values."""
+    h = hashlib.sha256()
+
+    def feed(value):
+        if torch.is_tensor(value):
+            t = value.detach().cpu().contiguous()
+            h.update(f"{t.dtype}{tuple(t.shape)}".encode())
+            h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes())
+        elif isinstance(value, dict):
+            for key in value:
+                h.update(repr(key).encode())
+                feed(value[key])
+        elif isinstance(value, (list, tuple)):
+            for item in value:
+                feed(item)
+        else:
+            h.update(repr(value).encode())
+
+    for model in models:
+        for module in model.modules():
+            feed(module.state_dict())
+    feed(optimizer.state_dict())
+    return h.hexdigest()
 
 
 def scheduled(epoch: int, position: int, schedule, values, frozen: bool = False):
@@ -41,7 +86,7 @@ def scheduled(epoch: int, position: int, schedule, values, frozen: bool = False)
     return position, values[position], False
 
 
-def train(train_image_path,
+def train_ranks(train_image_path,
           train_sparse_depth_path,
           train_intrinsics_path,
           val_image_path,
@@ -109,32 +154,55 @@ def train(train_image_path,
           workers=None,
           val_batch_size=1,
           summary_writer_factory=summary.EventWriter,
-          return_results=False):
-    """The reference's train() (src/kbnet.py:31-518): its arguments, names, order and defaults (src/global_constants.py), then
-    keyword-only workers (host threads of the two loaders; None: n_thread), val_batch_size (frames a validation forward),
-    summary_writer_factory (called with event_path + '-train' and event_path + '-val'; any object with add_scalar, add_histogram,
-    add_image and close fits) and return_results.
+          return_results=False,
+          rank=0,
+          world=1,
+          sync_batch_norm=True):
+    """train() with three more keyword-only arguments -- rank, world, sync_batch_norm -- and everything train()'s docstring says.
 
-    The four path arguments of each set are newline-delimited files of paths (loader.read_paths); a validation argument that is
-    None switches validation off.  Writes checkpoint_path/results.txt (the two path blocks, the six settings blocks, a line every
-    n_checkpoint steps, validate()'s lines), checkpoint_path/depth_model-<step>.pth and pose_model-<step>.pth every n_checkpoint
-    steps and after the last epoch, and the two event directories checkpoint_path/events-train and events-val.
-
-    Returns None, as the reference; with return_results a tuple: {'train_step', 'best_results'}, the list of (step, loss) logged at
-    the checkpoints, and the checkpoint paths written, depth and pose model alternating.
-
-    The loop waits for the device where the reference logs the loss, at a checkpoint (loss.item()), and in validate(); between
-    checkpoints nothing does.  Differences from the reference, on purpose: the shuffle order and the augmentation draws
-    (loader.TrainingFrameLoader, transforms.Transforms); validation runs val_batch_size frames a forward; device 'cpu' and path
-    lists of different lengths raise KbnError; a configuration the backward pass does not serve (deconv_type='transpose') raises
-    before anything is written; restore_model's and the writers' errors propagate; neither model's train() / eval() is called
-    (KBNetModel has one mode, the pose model's batch statistics are set_batch_norm('batch')).
-
-    One process, one GPU: the multi-GPU loop is the documented one over kb.dist.GradientAverager."""
+    Data-parallel training: `rank` of `world` processes, one a GPU, each calling train_ranks() with the same arguments inside an
+    initialised process group (kb.dist.init; KbnError otherwise, before anything is written) on its current device -- launch()
+    below starts them ("On several GPUs").  n_batch stays the GLOBAL batch.  With the ranks started from one set of seeds, the tensors every rank feeds
+    its networks are, bit for bit, its dist.shard_bounds slice of the batch a one-process train() builds under those seeds -- crop,
+    flips, removed points and noise -- and the logged loss, the summaries, results.txt and the checkpoints are those of the
+    global batch, written once, by rank 0.  In this order:
+      * rank 0's random state becomes everybody's before anything is drawn (dist.broadcast_rng_state), and rank 0's
+        torch.initial_seed() every rank's Transforms.seed;
+      * both models are built, and restored, on every rank; GradientAverager.broadcast_parameters(); the pose model's BatchNorm
+        layers normalise over the frames of all ranks (sync_batch_norm(BatchNormGroup)) unless sync_batch_norm=False, which gives
+        the reference's DataParallel behaviour -- every replica normalises with its own shard's statistics, the reduced gradient
+        is then not the whole batch's, and the checkpoint holds rank 0's running statistics;
+      * the loader shards every global batch and draws the crops of all of it (crops="global"), Transforms draws for all of it
+        (shard=); a global batch of fewer frames than ranks is skipped on every rank and is no step (n_train_steps(world=));
+      * every step: the forwards and the backward on the rank's frames, GradientAverager.average(n_local, n_global), the optimizer's
+        step on the reduced gradients -- no collective besides the averager's and BatchNorm's;
+      * at a checkpoint or summary step, where the loop waits anyway, the ranks' per-frame loss terms are summed (one all-reduce
+        of four fp64 numbers): Loss= and the scalars are the global batch's, sum over ranks of n_local / n_global x the rank's;
+      * at a summary step the tensors log_summary takes are gathered in rank order, which is batch order, and rank 0 makes the one
+        call: histograms and panels are the whole batch's;
+      * writers (summary_writer_factory is not called elsewhere), results.txt and checkpoints are rank 0's alone; a barrier follows
+        the last save_model;
+      * validate() runs on every rank over the whole validation set -- the replicas are bit-identical, so are the numbers and
+        best_results; only rank 0 has a writer and a log.  Sharding the validation set is not built.
+    With return_results every rank returns the same values; the dict has one more key, 'digest': replica_digest() of the rank's
+    final parameters, buffers and optimizer state, equal on every rank while the replicas are bit-identical (they are with
+    sync_batch_norm=True; with False the BatchNorm running statistics are per rank).  world=1 is the one-process path, bit for bit."""
     if device == "cuda" or device == "gpu":
         device = torch.device("cuda")
     else:
         raise KbnError(f"train: device {device!r}: the HIP path has no CPU fallback (the reference trains on the CPU for anything but 'cuda' / 'gpu')")
+    rank, world = int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise KbnError(f"train_ranks: rank {rank} of world {world}")
+    if world > 1 and not (torch.distributed.is_available() and torch.distributed.is_initialized()
+                          and torch.distributed.get_world_size() == world and torch.distributed.get_rank() == rank):
+        raise KbnError(f"train_ranks: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init, or "
+                       "kb.training.launch, which starts the ranks)")
+    main = rank == 0      # the rank that writes
+    transforms_seed = None
+    if world > 1:      # before anything is drawn: the weights' initialisation, the epoch's order, the crops, the augmentation
+        dist.broadcast_rng_state(src=0)
+        transforms_seed = dist.broadcast_object(torch.initial_seed(), src=0)
     workers = int(n_thread if workers is None else workers)
     if int(val_batch_size) < 1:
         raise KbnError(f"train: val_batch_size {val_batch_size}")
@@ -156,7 +224,7 @@ def train(train_image_path,
             raise KbnError(f"train: {n_train_sample} training image paths, {len(paths)} {name} paths")
     if n_train_sample < 1:
         raise KbnError(f"train: {train_image_path} lists no frame")
-    n_train_step = n_train_steps(n_train_sample, n_batch, learning_schedule)
+    n_train_step = n_train_steps(n_train_sample, n_batch, learning_schedule, world=world)
 
     validation_available = val_image_path is not None and val_sparse_depth_path is not None and \
         val_intrinsics_path is not None and val_ground_truth_path is not None
@@ -194,17 +262,25 @@ def train(train_image_path,
     if pose_model_restore_path is not None and pose_model_restore_path != "":
         pose_model.restore_model(pose_model_restore_path)
 
-    if not os.path.exists(checkpoint_path):
+    averager = None
+    if world > 1:
+        averager = dist.GradientAverager(parameters_depth_model + parameters_pose_model, rank, world)      # the list the optimizer steps
+        averager.broadcast_parameters()
+        if sync_batch_norm:
+            pose_model.sync_batch_norm(dist.BatchNormGroup(rank, world))
+
+    if main and not os.path.exists(checkpoint_path):
         os.makedirs(checkpoint_path)
 
     # ---- the loaders ----
+    sharding = {} if world == 1 else {"rank": rank, "world": world, "crops": "global"}
     train_loader = loader.TrainingFrameLoader(train_image_paths, train_sparse_depth_paths, train_intrinsics_paths,
                                               shape=(n_height, n_width), random_crop_type=augmentation_random_crop_type,
-                                              batch_size=n_batch, shuffle=True, device=device, workers=workers)
+                                              batch_size=n_batch, shuffle=True, device=device, workers=workers, **sharding)
     train_transforms = transforms.Transforms(normalized_image_range=normalized_image_range, random_flip_type=augmentation_random_flip_type,
                                              random_remove_points=augmentation_random_remove_points,
                                              random_noise_type=augmentation_random_noise_type,
-                                             random_noise_spread=augmentation_random_noise_spread)
+                                             random_noise_spread=augmentation_random_noise_spread, seed=transforms_seed)
     if validation_available:
         ground_truths = []
         for path in val_ground_truth_paths:
@@ -215,12 +291,15 @@ def train(train_image_path,
 
     train_summary_writer = val_summary_writer = None
     logged, checkpoints = [], []
+    if not main:      # rank 0 alone writes: the other ranks open no writer and keep no log
+        log_path = None
     try:
-        train_summary_writer = summary_writer_factory(event_path + "-train")
-        val_summary_writer = summary_writer_factory(event_path + "-val")
+        if main:
+            train_summary_writer = summary_writer_factory(event_path + "-train")
+            val_summary_writer = summary_writer_factory(event_path + "-val")
 
         # ---- the head of results.txt ----
-        log = summary.log
+        log = summary.log if main else (lambda s, filepath=None, to_console=True: None)
         log("Training input paths:", log_path)
         for path in (train_image_path, train_sparse_depth_path, train_intrinsics_path):
             log(path, log_path)
@@ -229,33 +308,34 @@ def train(train_image_path,
         for path in (val_image_path, val_sparse_depth_path, val_intrinsics_path, val_ground_truth_path):
             log(path, log_path)
         log("", log_path)
-        summary.log_input_settings(
-            log_path, n_batch=n_batch, n_height=n_height, n_width=n_width, input_channels_image=input_channels_image,
-            input_channels_depth=input_channels_depth, normalized_image_range=normalized_image_range,
-            outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold)
-        summary.log_network_settings(
-            log_path, min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
-            max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
-            n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
-            n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
-            resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
-            min_predict_depth=min_predict_depth, max_predict_depth=max_predict_depth, weight_initializer=weight_initializer,
-            activation_func=activation_func, parameters_depth_model=parameters_depth_model, parameters_pose_model=parameters_pose_model)
-        summary.log_training_settings(
-            log_path, n_batch=n_batch, n_train_sample=n_train_sample, n_train_step=n_train_step, learning_rates=learning_rates,
-            learning_schedule=learning_schedule, augmentation_probabilities=augmentation_probabilities,
-            augmentation_schedule=augmentation_schedule, augmentation_random_crop_type=augmentation_random_crop_type,
-            augmentation_random_flip_type=augmentation_random_flip_type, augmentation_random_remove_points=augmentation_random_remove_points,
-            augmentation_random_noise_type=augmentation_random_noise_type, augmentation_random_noise_spread=augmentation_random_noise_spread)
-        summary.log_loss_func_settings(
-            log_path, w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness,
-            w_weight_decay_depth=w_weight_decay_depth, w_weight_decay_pose=w_weight_decay_pose)
-        summary.log_evaluation_settings(log_path, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth)
-        summary.log_system_settings(
-            log_path, checkpoint_path=checkpoint_path, n_checkpoint=n_checkpoint, summary_event_path=event_path, n_summary=n_summary,
-            n_summary_display=n_summary_display, validation_start_step=validation_start_step,
-            depth_model_restore_path=depth_model_restore_path, pose_model_restore_path=pose_model_restore_path, device=device,
-            n_thread=n_thread)
+        if main:
+            summary.log_input_settings(
+                log_path, n_batch=n_batch, n_height=n_height, n_width=n_width, input_channels_image=input_channels_image,
+                input_channels_depth=input_channels_depth, normalized_image_range=normalized_image_range,
+                outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold)
+            summary.log_network_settings(
+                log_path, min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
+                max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
+                n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
+                n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
+                resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
+                min_predict_depth=min_predict_depth, max_predict_depth=max_predict_depth, weight_initializer=weight_initializer,
+                activation_func=activation_func, parameters_depth_model=parameters_depth_model, parameters_pose_model=parameters_pose_model)
+            summary.log_training_settings(
+                log_path, n_batch=n_batch, n_train_sample=n_train_sample, n_train_step=n_train_step, learning_rates=learning_rates,
+                learning_schedule=learning_schedule, augmentation_probabilities=augmentation_probabilities,
+                augmentation_schedule=augmentation_schedule, augmentation_random_crop_type=augmentation_random_crop_type,
+                augmentation_random_flip_type=augmentation_random_flip_type, augmentation_random_remove_points=augmentation_random_remove_points,
+                augmentation_random_noise_type=augmentation_random_noise_type, augmentation_random_noise_spread=augmentation_random_noise_spread)
+            summary.log_loss_func_settings(
+                log_path, w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness,
+                w_weight_decay_depth=w_weight_decay_depth, w_weight_decay_pose=w_weight_decay_pose)
+            summary.log_evaluation_settings(log_path, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth)
+            summary.log_system_settings(
+                log_path, checkpoint_path=checkpoint_path, n_checkpoint=n_checkpoint, summary_event_path=event_path, n_summary=n_summary,
+                n_summary_display=n_summary_display, validation_start_step=validation_start_step,
+                depth_model_restore_path=depth_model_restore_path, pose_model_restore_path=pose_model_restore_path, device=device,
+                n_thread=n_thread)
 
         # ---- the optimizer and the schedules ----
         learning_schedule_pos, learning_rate = 0, learning_rates[0]
@@ -274,11 +354,17 @@ def train(train_image_path,
             augmentation_schedule_pos, augmentation_probability, _ = scheduled(
                 epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
 
-            for image0, image1, image2, sparse_depth0, intrinsics in train_loader:
+            for batch, (image0, image1, image2, sparse_depth0, intrinsics) in enumerate(train_loader):
+                shard = None
+                if world > 1:
+                    n_global = train_loader.global_batch_size(batch)
+                    if not dist.every_rank_has_frames(n_global, world):      # the same answer on every rank: no step
+                        continue
+                    shard = (dist.shard_bounds(n_global, rank, world)[0], n_global)
                 train_step = train_step + 1
                 image0, image1, image2, sparse_depth0, filtered_sparse_depth0, filtered_validity_map_depth0 = transforms.train_inputs(
                     train_transforms, image0, image1, image2, sparse_depth0, augmentation_probability,
-                    kernel_size=outlier_removal_kernel_size, threshold=outlier_removal_threshold)
+                    kernel_size=outlier_removal_kernel_size, threshold=outlier_removal_threshold, shard=shard)
                 output_depth0 = depth_model.forward(image=image0, sparse_depth=sparse_depth0,
                                                     validity_map_depth=filtered_validity_map_depth0, intrinsics=intrinsics)
                 pose01 = pose_model.forward(image0, image1)
@@ -289,15 +375,28 @@ def train(train_image_path,
                     w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness)
                 optimizer.zero_grad()
                 loss.backward()
+                if averager is not None:
+                    averager.average(image0.shape[0], n_global)
                 optimizer.step()
+
+                if world > 1 and ((train_step % n_summary) == 0 or (train_step % n_checkpoint) == 0):
+                    # the global batch's loss, only where the loop waits anyway: the frames' four terms summed over the ranks
+                    # in fp64, then compute_loss's own expressions
+                    terms = dist.sum_over_ranks(loss_info["per_frame"].sum(dim=0)) / n_global
+                    color, structure, sparse, smooth = terms.float().unbind(0)
+                    loss = w_color * color + w_structure * structure + w_sparse_depth * sparse + w_smoothness * smooth
+                    loss_info.update(loss_color=color, loss_structure=structure, loss_sparse_depth=sparse, loss_smoothness=smooth, loss=loss)
 
                 if (train_step % n_summary) == 0:
                     image01, image02 = loss_info.pop("image01"), loss_info.pop("image02")
                     loss_info.pop("per_frame")      # N x 4, this package's addition: a writer's add_scalar wants one number
-                    depth_model.log_summary(summary_writer=train_summary_writer, tag="train", step=train_step, image0=image0,
-                                            image01=image01, image02=image02, output_depth0=output_depth0.detach(),
-                                            sparse_depth0=filtered_sparse_depth0, validity_map0=filtered_validity_map_depth0,
-                                            pose01=pose01, pose02=pose02, scalars=loss_info, n_display=min(n_batch, n_summary_display))
+                    shown = dict(image0=image0, image01=image01, image02=image02, output_depth0=output_depth0.detach(),
+                                 sparse_depth0=filtered_sparse_depth0, validity_map0=filtered_validity_map_depth0, pose01=pose01, pose02=pose02)
+                    if world > 1:      # rank order is batch order; every n_summary steps, so its cost is not a concern
+                        shown = {name: dist.gather_frames(t, n_global, rank, world) for name, t in shown.items()}
+                    if main:
+                        depth_model.log_summary(summary_writer=train_summary_writer, tag="train", step=train_step, scalars=loss_info,
+                                                n_display=min(n_batch, n_summary_display), **shown)
 
                 if (train_step % n_checkpoint) == 0:
                     value = loss.item()      # the loop's wait for the device, where the reference logs the loss
@@ -314,13 +413,19 @@ def train(train_image_path,
                             outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold,
                             normalized_image_range=normalized_image_range)
                     for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-                        model.save_model(pattern.format(train_step), train_step, optimizer)
+                        if main:
+                            model.save_model(pattern.format(train_step), train_step, optimizer)
                         checkpoints.append(pattern.format(train_step))
 
         for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-            model.save_model(pattern.format(train_step), train_step, optimizer)
+            if main:
+                model.save_model(pattern.format(train_step), train_step, optimizer)
             if pattern.format(train_step) not in checkpoints:
                 checkpoints.append(pattern.format(train_step))
+        digest = None
+        if world > 1:
+            digest = replica_digest((depth_model, pose_model), optimizer)
+            dist.barrier()      # no rank leaves, and nobody reads the checkpoints, before rank 0 has written them
     except BaseException:
         for writer in (train_summary_writer, val_summary_writer):
             if writer is not None:
@@ -329,10 +434,191 @@ def train(train_image_path,
                 except Exception:      # noqa: BLE001  (the run's own exception is the one to see)
                     pass
         raise
-    try:
-        train_summary_writer.close()
-    finally:
-        val_summary_writer.close()
+    if main:
+        try:
+            train_summary_writer.close()
+        finally:
+            val_summary_writer.close()
     if not return_results:
         return None
-    return {"train_step": train_step, "best_results": best_results}, logged, checkpoints
+    results = {"train_step": train_step, "best_results": best_results}
+    if world > 1:
+        results["digest"] = digest      # of this rank's replica: the one value that may differ between ranks, and must not
+    return results, logged, checkpoints
+
+
+def train(*arguments, **keywords):
+    """The reference's train() (src/kbnet.py:31-518): its arguments, names, order and defaults (src/global_constants.py), then
+    keyword-only workers (host threads of the two loaders; None: n_thread), val_batch_size (frames a validation forward),
+    summary_writer_factory (called with event_path + '-train' and event_path + '-val'; any object with add_scalar, add_histogram,
+    add_image and close fits) and return_results.
+
+    The four path arguments of each set are newline-delimited files of paths (loader.read_paths); a validation argument that is
+    None switches validation off.  Writes checkpoint_path/results.txt (the two path blocks, the six settings blocks, a line every
+    n_checkpoint steps, validate()'s lines), checkpoint_path/depth_model-<step>.pth and pose_model-<step>.pth every n_checkpoint
+    steps and after the last epoch, and the two event directories checkpoint_path/events-train and events-val.
+
+    Returns None, as the reference; with return_results a tuple: {'train_step', 'best_results'}, the list of (step, loss) logged at
+    the checkpoints, and the checkpoint paths written, depth and pose model alternating.
+
+    The loop waits for the device where the reference logs the loss, at a checkpoint (loss.item()), and in validate(); between
+    checkpoints nothing does.  Differences from the reference, on purpose: the shuffle order and the augmentation draws
+    (loader.TrainingFrameLoader, transforms.Transforms); validation runs val_batch_size frames a forward; device 'cpu' and path
+    lists of different lengths raise KbnError; a configuration the backward pass does not serve (deconv_type='transpose') raises
+    before anything is written; restore_model's and the writers' errors propagate; neither model's train() / eval() is called
+    (KBNetModel has one mode, the pose model's batch statistics are set_batch_norm('batch')).
+
+    One process, one GPU: train_ranks() below is this function run by one process a GPU ("On several GPUs"), and
+    launch() starts those processes."""
+    bound = _TRAIN_SIGNATURE.bind(*arguments, **keywords)      # TypeError for rank, world, sync_batch_norm: they are train_ranks()'s
+    return train_ranks(*bound.args, **bound.kwargs)
+
+
+# train()'s signature is the reference's and stays it: train_ranks()'s without its three last arguments, written once
+_TRAIN_SIGNATURE = inspect.signature(train_ranks)
+_TRAIN_SIGNATURE = _TRAIN_SIGNATURE.replace(parameters=[p for p in _TRAIN_SIGNATURE.parameters.values()
+                                                        if p.name not in ("rank", "world", "sync_batch_norm")])
+train.__signature__ = _TRAIN_SIGNATURE
+
+
+# ------------------------------------------------------------------------------------------------ one process per GPU
+MAX_RANKS = 16
+ARGUMENTS_FILE, RESULTS_FILE = "launch-arguments.pkl", "launch-results.pkl"
+
+
+def _free_port() -> int:
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _tail(path: str, lines: int = 20) -> str:
+    try:
+        with open(path, errors="replace") as f:
+            return "".join(f.readlines()[-lines:])
+    except OSError:
+        return ""
+
+
+def launch(n_gpus, *, backend="nccl", devices=None, timeout=None, **train_arguments):
+    """train_ranks() on `n_gpus` GPUs of this host: starts one fresh child process a rank (subprocess; no process's program is ever
+    replaced), waits for them, and returns rank 0's return_results tuple.  The calling process does not need the GPU and does not
+    touch it.
+
+    train_arguments: train()'s arguments by name (the seven path arguments too), without rank, world and return_results.  They
+    travel to the children through a file, checkpoint_path/launch-arguments.pkl, so they must pickle (a summary_writer_factory
+    that is a class or a module-level function does).  With them travels the caller's random state: the children start from
+    NumPy's global state and torch's CPU generator as they are here, and from torch.manual_seed(torch.initial_seed()) for the
+    device generators -- so launch() under a seed trains as train() called in its place under that seed would.
+
+    Each child gets RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR=127.0.0.1 and MASTER_PORT (a free port) in its environment, selects
+    its device, runs kb.dist.init(backend) and then train_ranks(..., rank=rank, world=n_gpus).  devices: the device index of every rank;
+    None: rank r on device r.  Ranks may share a device under backend="gloo" ([0, 0]: two ranks on one GPU, the tests' form);
+    "nccl" (RCCL) needs a device a rank.  Host thread counts come from n_thread / workers alone.  The children's output goes to
+    checkpoint_path/rank<r>.out and rank<r>.err, never to pipes: a rank whose pipe is full would keep the others waiting in a
+    collective.  Every rank also leaves checkpoint_path/rank<r>.digest, replica_digest() of what it holds at the end.
+
+    1 <= n_gpus <= 16 and len(devices) == n_gpus, else KbnError before anything is started or written.  The first child to exit
+    with a non-zero status, or `timeout` seconds for the whole run (None: no limit), ends the others; launch then raises KbnError
+    with that rank's last lines of stderr."""
+    what = "launch"
+    if isinstance(n_gpus, bool) or not isinstance(n_gpus, (int, np.integer)) or not 1 <= int(n_gpus) <= MAX_RANKS:
+        raise KbnError(f"{what}: n_gpus {n_gpus!r}: 1 to {MAX_RANKS} ranks")
+    world = int(n_gpus)
+    if devices is None:
+        devices = list(range(world))
+    devices = [int(d) for d in devices]
+    if len(devices) != world or any(d < 0 for d in devices):
+        raise KbnError(f"{what}: devices {devices}: one device index for each of the {world} ranks")
+    if backend not in ("nccl", "gloo"):
+        raise KbnError(f"{what}: backend {backend!r}: 'nccl' (RCCL) or 'gloo'")
+    if backend == "nccl" and len(set(devices)) != world:
+        raise KbnError(f"{what}: devices {devices}: RCCL needs a device a rank (ranks share one under backend='gloo')")
+    for name in ("rank", "world", "return_results"):
+        if name in train_arguments:
+            raise KbnError(f"{what}: {name} is set by launch itself")
+    if timeout is not None and not float(timeout) > 0:
+        raise KbnError(f"{what}: timeout {timeout!r}")
+    checkpoint_path = train_arguments.get("checkpoint_path", "trained_kbnet")
+    threads = train_arguments.get("workers")
+    threads = max(1, int(train_arguments.get("n_thread", 8) if threads is None else threads))
+
+    os.makedirs(checkpoint_path, exist_ok=True)
+    arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
+    if os.path.exists(results_path):
+        os.remove(results_path)
+    with open(arguments_path, "wb") as f:
+        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
+                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed())}, f)
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    program = ("import sys; sys.path.insert(0, sys.argv[1]); import kbnet_amd; kbnet_amd.training._rank_main(sys.argv[2])")
+    command = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", program, root, arguments_path]
+    port = _free_port()
+    children, logs = [], []
+    try:
+        for rank in range(world):
+            env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(devices[rank]), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                       MASTER_PORT=str(port))
+            env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL between processes needs it (as bench.py sets it)
+            env.setdefault("OMP_NUM_THREADS", str(threads))
+            out = open(os.path.join(checkpoint_path, f"rank{rank}.out"), "w")
+            err = open(os.path.join(checkpoint_path, f"rank{rank}.err"), "w")
+            logs += [out, err]
+            children.append(subprocess.Popen(command, stdin=subprocess.DEVNULL, stdout=out, stderr=err, env=env))
+        deadline = None if timeout is None else time.monotonic() + float(timeout)
+        failed = None      # (rank, why)
+        while failed is None and any(c.poll() is None for c in children):
+            for rank, child in enumerate(children):
+                if child.poll() is not None and child.returncode != 0:
+                    failed = (rank, f"exited with status {child.returncode}")
+                    break
+            else:
+                if deadline is not None and time.monotonic() > deadline:
+                    rank = next(r for r, c in enumerate(children) if c.poll() is None)
+                    failed = (rank, f"was still running after the timeout of {float(timeout):g} s")
+                else:
+                    time.sleep(0.05)
+        if failed is None:
+            failed = next(((r, f"exited with status {c.returncode}") for r, c in enumerate(children) if c.returncode != 0), None)
+    finally:
+        for child in children:
+            if child.poll() is None:
+                child.kill()
+                child.wait()
+        for f in logs:
+            f.close()
+    if failed is not None:
+        rank, why = failed
+        raise KbnError(f"{what}: rank {rank} of {world} {why}; the end of {os.path.join(checkpoint_path, f'rank{rank}.err')}:\n"
+                       + _tail(os.path.join(checkpoint_path, f"rank{rank}.err")))
+    if not os.path.exists(results_path):
+        raise KbnError(f"{what}: every rank exited with status 0, but rank 0 left no {results_path}")
+    with open(results_path, "rb") as f:
+        return pickle.load(f)
+
+
+def _rank_main(arguments_path: str) -> None:
+    """What a child of launch() runs: the device, the caller's random state, the process group, train_ranks(), and rank 0's results into
+    a file."""
+    with open(arguments_path, "rb") as f:
+        arguments = pickle.load(f)
+    rank, _, world = dist.env_world()
+    torch.set_num_threads(arguments["threads"])
+    torch.cuda.set_device(arguments["devices"][rank])
+    numpy_state, cpu_state, seed = arguments["random"]
+    torch.manual_seed(seed)      # every generator, the device's too, and torch.initial_seed()
+    torch.set_rng_state(cpu_state)
+    np.random.set_state(numpy_state)
+    if world > 1:
+        dist.init(arguments["backend"])
+    results = train_ranks(**arguments["train"], rank=rank, world=world, return_results=True)
+    if world > 1:
+        with open(os.path.join(os.path.dirname(arguments["results"]), f"rank{rank}.digest"), "w") as f:
+            f.write(results[0]["digest"] + "\n")
+    if rank == 0:
+        with open(arguments["results"] + ".part", "wb") as f:
+            pickle.dump(results, f)
+        os.replace(arguments["results"] + ".part", arguments["results"])
+    if world > 1:      # after a clean run only: a rank that failed leaves at once, and launch() ends the others
+        torch.distributed.destroy_process_group()

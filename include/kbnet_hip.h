@@ -891,7 +891,15 @@ int kbn_multi_tensor_scale_copy(const kbn_copy_tensor* tensors, int count, float
  * in the kernel arguments: launches only, no copy, no allocation, no synchronisation.  densities and workspace may be NULL when
  * no frame has bit 2 or no tensor is a range map.  KBN_ERR_INVALID_ARGUMENT for NULL pointers, zero sizes, a flag above 15, bit 3
  * with KBN_AUGMENT_NOISE_NONE; KBN_ERR_WORKSPACE for a workspace that is too small; KBN_ERR_UNSUPPORTED for a frame of 2^31
- * elements or more -- all checked before anything is launched. */
+ * elements or more -- all checked before anything is launched.
+ *
+ * kbn_augment_forward_at is the same operation for a SHARD of a larger batch: the n frames given are frames frame_base ..
+ * frame_base + n - 1 of it, and the counter's frame word is frame_base + the frame's index here.  With the same seed, call and
+ * map indices, and with flags[] and densities[] the shard's slices of the larger batch's, the outputs are bit for bit the slices
+ * [frame_base, frame_base + n) of what one call over the larger batch writes: the ranks of a data-parallel run draw, between
+ * them, what one process draws.  Everything that addresses memory -- src, dst, flags[], densities[], the workspace -- is indexed
+ * by the frame's index here, 0 .. n - 1.  KBN_ERR_UNSUPPORTED when frame_base + n exceeds 2^32 - 1 (the word is 32 bits);
+ * otherwise the arguments, checks and launches of kbn_augment_forward, which is kbn_augment_forward_at with frame_base 0. */
 #define KBN_AUGMENT_ROLE_IMAGE 0
 #define KBN_AUGMENT_ROLE_RANGE 1
 #define KBN_AUGMENT_ROLE_VALIDITY 2
@@ -918,6 +926,10 @@ size_t kbn_augment_workspace_bytes(const kbn_augment_tensor* tensors, int count,
 int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
                         const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
                         float noise_spread, unsigned long long seed, unsigned call, int stages, kbn_stream_t stream);
+int kbn_augment_forward_at(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
+                           const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
+                           float noise_spread, unsigned long long seed, unsigned call, unsigned frame_base, int stages,
+                           kbn_stream_t stream);
 
 /* ------------------------------------------------- the training loop's image summaries ----
  *   depth_model.log_summary(summary_writer, tag, step, image0, image01, image02, output_depth0, ...)   reference src/kbnet.py:455-472

@@ -616,7 +616,11 @@ class TrainingFrameLoader:
     draws too.  Ranks that start from one np.random state then draw the same crops, and their batches concatenate, in rank order,
     to the batch one process builds under that state: kb.training.train_ranks(rank, world) uses it.  np.random is shared with whatever
     else the thread draws between two batches (Transforms.draw), and `prefetch` decides how many batches' crops are drawn ahead
-    of those draws, so the ranks AND the one-process run they are compared with must use the same `prefetch`."""
+    of those draws, so the ranks AND the one-process run they are compared with must use the same `prefetch`.
+
+    For the same reason an epoch that is left between two batches and continued elsewhere (kb.training.train_resumable) needs more
+    than np.random's state: `state_dict()` holds the epoch's order, the next batch's index and the plans -- crops included -- of the
+    batches already in flight, and after `load_state_dict(state)` the next `iter()` yields the rest of that epoch (one process)."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str], intrinsics_paths: Sequence[str],
                  shape=None, random_crop_type=["none"], batch_size: int = 8, shuffle: bool = True,
@@ -653,6 +657,10 @@ class TrainingFrameLoader:
         self._headers: List[Optional[tuple]] = [None] * self.n_sample
         self._pending: list = []
         self._serial = 0                                         # batches submitted so far: picks the staging set
+        self._order: Optional[list] = None                       # the running epoch's order, the batch iter() hands out next and the
+        self._next = 0                                           # plans of the batches enqueued beyond it: what state_dict() holds
+        self._plans: list = []
+        self._resume: Optional[dict] = None                      # load_state_dict()'s state, for the next iter()
 
     @property
     def do_random_crop(self) -> bool:
@@ -751,11 +759,17 @@ class TrainingFrameLoader:
         st["done"] = done
         return batch, done
 
-    def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0):
+    def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0, plan=None):
         """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn.
-        `batch`, `first`: with crops="global" the global batch and where `idx` starts in it."""
-        plan = error = None
-        if batch is not None:      # the whole batch's draws, on every rank, before anything else: an empty shard draws too
+        `batch`, `first`: with crops="global" the global batch and where `idx` starts in it.  `plan`: what _plan returned for this
+        batch in an earlier session (load_state_dict) -- nothing is drawn."""
+        future = self._enqueue_planned(idx, batch, first, plan)
+        self._plans.append(getattr(future, "plan", None))
+        return future
+
+    def _enqueue_planned(self, idx: Sequence[int], batch, first: int, plan):
+        error = None
+        if batch is not None and plan is None:      # the whole batch's draws, on every rank, before anything else: an empty shard draws too
             try:
                 plan = self._plan(batch, (first, first + len(idx)))
             except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
@@ -777,11 +791,67 @@ class TrainingFrameLoader:
             failed: Future = Future()
             failed.set_exception(error)
             return failed
-        return self._driver.submit(self._submit, slot, *plan)
+        future = self._driver.submit(self._submit, slot, *plan)
+        future.plan = plan
+        return future
+
+    def state_dict(self) -> dict:
+        """Where the running epoch stands, between two batches: the epoch's order, the index of the batch iter() hands out next and
+        the finished plans (_plan's frames with their crop origins, shape and format) of the batches already enqueued beyond it --
+        their crops were drawn from np.random ahead of whatever the iterating thread drew since, so np.random's state alone does not
+        bring them back.  Empty before the first epoch and after an epoch's last batch.  Plain Python numbers only.  One process:
+        a sharded loader (world > 1) raises KbnError."""
+        if self.world > 1:
+            raise KbnError("TrainingFrameLoader: state_dict of a sharded loader (world > 1) is not built")
+        if self._order is None or self._next >= len(self):
+            return {}
+        if any(plan is None for plan in self._plans):
+            raise KbnError("TrainingFrameLoader: state_dict: a batch in flight could not be planned (its error is raised when it is due)")
+        plans = [([tuple(int(v) for v in frame) for frame in frames], [int(shape[0]), int(shape[1])], int(c), int(dbits), bool(cropped))
+                 for frames, shape, c, dbits, cropped in self._plans]
+        return {"order": [int(i) for i in self._order], "next": int(self._next), "plans": plans, "n_sample": self.n_sample,
+                "batch_size": self.batch_size}
+
+    def load_state_dict(self, state: dict) -> None:
+        """The next iter() continues the epoch `state` (a state_dict()) was taken in: the stored order (nothing is drawn from torch's
+        generator), from batch `next` on; the stored plans are submitted as they are and crops are drawn only for the batches beyond
+        them, in the order the uninterrupted iteration draws them.  An empty state: the next iter() is an ordinary one.  KbnError for
+        a state of another path count, batch size or prefetch depth."""
+        what = "TrainingFrameLoader: load_state_dict"
+        if self.world > 1:
+            raise KbnError(f"{what} of a sharded loader (world > 1) is not built")
+        if not state:
+            self._resume = None
+            return
+        order, nxt, plans = [int(i) for i in state["order"]], int(state["next"]), list(state["plans"])
+        if int(state["n_sample"]) != self.n_sample or sorted(order) != list(range(self.n_sample)):
+            raise KbnError(f"{what}: the state orders {state['n_sample']} samples, this loader has {self.n_sample} paths")
+        if int(state["batch_size"]) != self.batch_size:
+            raise KbnError(f"{what}: the state's batch size is {state['batch_size']}, this loader's {self.batch_size}")
+        if not 0 < nxt < len(self):
+            raise KbnError(f"{what}: next batch {nxt} of {len(self)}")
+        if len(plans) != min(self.prefetch, len(self) - nxt):
+            raise KbnError(f"{what}: the state holds the plans of {len(plans)} batches, a prefetch of {self.prefetch} has "
+                           f"{min(self.prefetch, len(self) - nxt)} in flight before batch {nxt} of {len(self)}")
+        for b, (frames, shape, c, dbits, cropped) in enumerate(plans, nxt):
+            if [int(f[0]) for f in frames] != order[b * self.batch_size:(b + 1) * self.batch_size]:
+                raise KbnError(f"{what}: the plan of batch {b} does not hold the samples of the state's order")
+        self._resume = {"order": order, "next": nxt,
+                        "plans": [([tuple(int(v) for v in f) for f in frames], (int(shape[0]), int(shape[1])), int(c), int(dbits), bool(cropped))
+                                  for frames, shape, c, dbits, cropped in plans]}
 
     def __iter__(self):
         for f in self._pending:      # batches of an epoch that was left early still own staging sets
             f.exception()
+        self._plans = []
+        if self._resume is not None:      # the rest of an epoch another session began (load_state_dict): its order, its plans
+            resume, self._resume = self._resume, None
+            self._order, first = resume["order"], resume["next"]
+            batches = [(shard,) for shard in shard_batches(self._order, self.batch_size, 0, 1)]
+            plans = resume["plans"] + [None] * self.prefetch      # a batch without a stored plan is drawn for
+            self._pending = pending = [self._enqueue(*batches[first + j], plan=plans[j])
+                                       for j in range(min(self.prefetch, len(batches) - first))]
+            return self._epoch(batches, pending, first)
         if self.shuffle:
             order = list(torch.utils.data.RandomSampler(range(self.n_sample), generator=self.generator))
         else:
@@ -790,6 +860,7 @@ class TrainingFrameLoader:
             shared = [[int(i) for i in order]]
             torch.distributed.broadcast_object_list(shared, src=0)
             order = shared[0]
+        self._order = order
         batches = shard_batches(order, self.batch_size, self.rank, self.world)
         if self.crops == "global":      # (shard, global batch, the shard's place in it)
             batches = [(shard, list(order[b * self.batch_size:(b + 1) * self.batch_size]),
@@ -799,9 +870,12 @@ class TrainingFrameLoader:
         self._pending = pending = [self._enqueue(*batches[b]) for b in range(min(self.prefetch, len(batches)))]
         return self._epoch(batches, pending)
 
-    def _epoch(self, batches, pending):
-        for b in range(len(batches)):
+    def _epoch(self, batches, pending, first: int = 0):
+        self._next = first
+        for b in range(first, len(batches)):
             batch, done = pending.pop(0).result()
+            self._plans.pop(0)
             if b + self.prefetch < len(batches):
                 pending.append(self._enqueue(*batches[b + self.prefetch]))
+            self._next = b + 1
             yield batch if done is None else _hand_over(self.device, done, batch)

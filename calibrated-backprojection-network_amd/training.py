@@ -17,7 +17,11 @@ around it.
                                                             builds; launch(n_gpus, ...) starts the processes
 
 train() has the reference's signature and drives one GPU; train_ranks() is the same function with rank, world and
-sync_batch_norm -- train() is train_ranks(world=1).  DESIGN section 8p has the design of the data-parallel form."""
+sync_batch_norm -- train() is train_ranks(world=1).  DESIGN section 8p has the design of the data-parallel form.
+
+train_resumable() is train() in sessions: the same call, made in one job slot after another, continues the run from the state the
+last one left in checkpoint_path, bit for bit as the uninterrupted run.  All three entry points run one loop,
+_train_loop."""
 
 from __future__ import annotations
 
@@ -25,9 +29,12 @@ import hashlib
 import inspect
 import os
 import pickle
+import re
+import signal
 import socket
 import subprocess
 import sys
+import threading
 import time
 
 import numpy as np
@@ -86,7 +93,196 @@ def scheduled(epoch: int, position: int, schedule, values, frozen: bool = False)
     return position, values[position], False
 
 
-def train_ranks(train_image_path,
+# ------------------------------------------------------------------------------------------------ a run in sessions
+PATH_ARGUMENTS = ("train_image_path", "train_sparse_depth_path", "train_intrinsics_path", "val_image_path", "val_sparse_depth_path",
+                  "val_intrinsics_path", "val_ground_truth_path")
+# what may change from one session of a run to the next: where the files lie, what a fresh start restores, the host's threads, and
+# what is not a setting at all
+UNRECORDED_ARGUMENTS = ("checkpoint_path", "depth_model_restore_path", "pose_model_restore_path", "device", "n_thread", "workers",
+                        "summary_writer_factory", "return_results")
+STATE_FILE = "train_state-{}.pth"
+_STATE_NAME = re.compile(r"^train_state-(\d+)\.pth$")
+
+
+def _plain(value):
+    """Lists for tuples and arrays, Python numbers for NumPy's: values that compare by content and load anywhere."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        return [_plain(v) for v in value]
+    if isinstance(value, (bool, np.bool_)):
+        return bool(value)
+    if isinstance(value, (int, np.integer)):
+        return int(value)
+    if isinstance(value, (float, np.floating)):
+        return float(value)
+    return value
+
+
+def argument_record(arguments: dict, path_contents: dict) -> dict:
+    """Every argument of train() that shapes the trajectory, in train()'s order: all but UNRECORDED_ARGUMENTS, the seven path
+    arguments by the content of their lists (`path_contents`: name -> paths; a validation argument that is None stays None)."""
+    record = {}
+    for name in _TRAIN_SIGNATURE.parameters:
+        if name not in UNRECORDED_ARGUMENTS:
+            record[name] = _plain(path_contents.get(name)) if name in PATH_ARGUMENTS else _plain(arguments[name])
+    return record
+
+
+def check_argument_record(recorded: dict, given: dict) -> None:
+    """KbnError naming the first argument, in train()'s order, whose value is not the one the run was started with."""
+    for name in given:
+        if name not in recorded or recorded[name] != given[name]:
+            was, now = recorded.get(name, "<not recorded>"), given[name]
+            if name in PATH_ARGUMENTS and isinstance(was, list) and isinstance(now, list):
+                was, now = f"{len(was)} paths", f"{len(now)} paths" + ("" if len(was) != len(now) else ", not the same ones")
+            raise KbnError(f"train_resumable: {name} is {now!r}, the run in this checkpoint_path was started with {was!r}: a continuation "
+                           "takes the arguments of the first session (checkpoint_path, the restore paths, device, n_thread and workers "
+                           "may change)")
+
+
+def random_state(device) -> dict:
+    """The three generators a step draws from: NumPy's global one (crops, flags), torch's CPU one (the epoch's order) and the
+    device's (removal densities).  All three are host-side values: nothing waits for the device."""
+    name, keys, position, has_gauss, cached_gaussian = np.random.get_state()
+    return {"numpy": (str(name), torch.from_numpy(keys.astype(np.int64)), int(position), int(has_gauss), float(cached_gaussian)),
+            "torch": torch.get_rng_state(), "device": torch.cuda.get_rng_state(device)}
+
+
+def set_random_state(state: dict, device) -> None:
+    name, keys, position, has_gauss, cached_gaussian = state["numpy"]
+    np.random.set_state((name, keys.numpy().astype(np.uint32), position, has_gauss, cached_gaussian))
+    torch.set_rng_state(state["torch"])
+    torch.cuda.set_rng_state(state["device"], device)
+
+
+def find_state(checkpoint_path: str):
+    """-> (the newest complete training state of `checkpoint_path` or None, a message for every newer one passed over).  A state is
+    complete when its train_state-<step>.pth loads and holds that step, and depth_model-<step>.pth and pose_model-<step>.pth exist
+    beside it -- the state is moved into place after the two, so a job killed while writing leaves an older state the newest."""
+    steps = []
+    if os.path.isdir(checkpoint_path):
+        steps = sorted((int(m.group(1)) for m in map(_STATE_NAME.match, os.listdir(checkpoint_path)) if m), reverse=True)
+    skipped = []
+    for step in steps:
+        path = os.path.join(checkpoint_path, STATE_FILE.format(step))
+        missing = [name for name in (f"depth_model-{step}.pth", f"pose_model-{step}.pth")
+                   if not os.path.isfile(os.path.join(checkpoint_path, name))]
+        if missing:
+            skipped.append(f"Skipping {path}: no {' and no '.join(missing)} beside it")
+            continue
+        try:
+            state = torch.load(path, map_location="cpu")
+            if not isinstance(state, dict) or int(state["step"]) != step:
+                raise ValueError("it does not hold a state of that step")
+        except Exception as e:      # noqa: BLE001  (a truncated or foreign file: whatever the unpickler makes of it)
+            skipped.append(f"Skipping {path}: {type(e).__name__}: {str(e).splitlines()[0] if str(e) else 'unreadable'}")
+            continue
+        return state, skipped
+    return None, skipped
+
+
+def prune_states(checkpoint_path: str, keep_states: int, n_checkpoint: int, n_train_step: int, current=None) -> list:
+    """Removes all but the newest `keep_states` train_state files, and with a removed state the two model checkpoints of its step
+    when that step is a stop's: one off the n_checkpoint grid that is not the run's last.  `current`: the step whose state was just
+    written -- a state of a later step is one find_state passed over (the run went on from an older one); it goes first and does
+    not count, or it would push the states that load out of the `keep_states` kept.  -> the paths removed."""
+    steps = sorted(int(m.group(1)) for m in map(_STATE_NAME.match, os.listdir(checkpoint_path)) if m)
+    stale = [step for step in steps if current is not None and step > int(current)]
+    steps = [step for step in steps if step not in stale]
+    removed = []
+    for step in stale + steps[:max(0, len(steps) - int(keep_states))]:
+        names = [STATE_FILE.format(step)]
+        if step % int(n_checkpoint) != 0 and step != int(n_train_step):
+            names += [f"depth_model-{step}.pth", f"pose_model-{step}.pth"]
+        for name in names:
+            path = os.path.join(checkpoint_path, name)
+            if os.path.exists(path):
+                os.remove(path)
+                removed.append(path)
+    return removed
+
+
+class Budget:
+    """When a session ends before the run does: after `max_steps` steps of this session, once `max_seconds` of host time have
+    passed since the context was entered (`clock`, time.monotonic; read between steps, nothing waits for the device), or when one of
+    `stop_signals` has arrived.  As a context it installs a handler for each signal that sets a flag and does nothing else -- the
+    step in progress completes -- and puts the previous handlers back on the way out, whatever happened inside.  Python installs
+    handlers on the main thread only; on another thread none is installed and the two other limits work alone."""
+
+    def __init__(self, max_steps=None, max_seconds=None, stop_signals=(signal.SIGTERM,), clock=time.monotonic):
+        if max_steps is not None and (isinstance(max_steps, bool) or int(max_steps) != max_steps or max_steps < 1):
+            raise KbnError(f"train_resumable: max_steps {max_steps!r}: None or at least one step a session")
+        if max_seconds is not None and not float(max_seconds) > 0:
+            raise KbnError(f"train_resumable: max_seconds {max_seconds!r}: None or a positive number")
+        self.max_steps = None if max_steps is None else int(max_steps)
+        self.max_seconds = None if max_seconds is None else float(max_seconds)
+        self.stop_signals = tuple(stop_signals or ())
+        self.clock = clock
+        self.steps, self.started, self.signalled, self.installed = 0, clock(), None, {}
+
+    def _flag(self, number, frame):
+        self.signalled = number
+
+    def __enter__(self):
+        self.started = self.clock()
+        if threading.current_thread() is threading.main_thread():
+            try:
+                for number in self.stop_signals:
+                    self.installed[number] = signal.signal(number, self._flag)
+            except BaseException:
+                self.__exit__(None, None, None)
+                raise
+        return self
+
+    def __exit__(self, *exc):
+        while self.installed:
+            number, previous = self.installed.popitem()
+            signal.signal(number, signal.SIG_DFL if previous is None else previous)
+        return False
+
+    def step_done(self):
+        """Counts a step of the session -> why the session ends here ('signal <n>', 'max_steps', 'max_seconds'), or None."""
+        self.steps += 1
+        if self.signalled is not None:
+            return f"signal {int(self.signalled)}"
+        if self.max_steps is not None and self.steps >= self.max_steps:
+            return "max_steps"
+        if self.max_seconds is not None and self.clock() - self.started >= self.max_seconds:
+            return "max_seconds"
+        return None
+
+
+class _Session:
+    """What train_resumable() adds to the loop: the state it continues from, the files written whole, the states pruned."""
+
+    def __init__(self, budget: Budget, keep_states: int):
+        if isinstance(keep_states, bool) or int(keep_states) != keep_states or keep_states < 1:
+            raise KbnError(f"train_resumable: keep_states {keep_states!r}: at least one state is kept")
+        self.budget, self.keep_states = budget, int(keep_states)
+        self.checkpoint_path, self.record, self.skipped = None, None, []
+        self.n_train_step = self.n_checkpoint = None
+
+    def start(self, checkpoint_path, record, n_train_step, n_checkpoint):
+        """-> the state to continue from, or None for a fresh start.  Reads only; KbnError when `record` is not the run's."""
+        self.checkpoint_path, self.record = checkpoint_path, record
+        self.n_train_step, self.n_checkpoint = int(n_train_step), int(n_checkpoint)
+        state, self.skipped = find_state(checkpoint_path)
+        if state is not None:
+            check_argument_record(state["arguments"], record)
+        return state
+
+    def write(self, path, writer):
+        """writer(temporary name), then the move into place: `path` holds the old bytes or the new ones, never a part of them."""
+        part = path + ".part"
+        writer(part)
+        os.replace(part, path)
+
+    def save_state(self, snapshot: dict):
+        snapshot["arguments"] = self.record
+        self.write(os.path.join(self.checkpoint_path, STATE_FILE.format(snapshot["step"])), lambda part: torch.save(snapshot, part))
+        prune_states(self.checkpoint_path, self.keep_states, self.n_checkpoint, self.n_train_step, current=snapshot["step"])
+
+
+def _train_loop(train_image_path,
           train_sparse_depth_path,
           train_intrinsics_path,
           val_image_path,
@@ -157,36 +353,11 @@ def train_ranks(train_image_path,
           return_results=False,
           rank=0,
           world=1,
-          sync_batch_norm=True):
-    """train() with three more keyword-only arguments -- rank, world, sync_batch_norm -- and everything train()'s docstring says.
-
-    Data-parallel training: `rank` of `world` processes, one a GPU, each calling train_ranks() with the same arguments inside an
-    initialised process group (kb.dist.init; KbnError otherwise, before anything is written) on its current device -- launch()
-    below starts them (INTEGRATION.md, "On several GPUs"; DESIGN section 8p).  n_batch stays the GLOBAL batch.  With the ranks started from one set of seeds, the tensors every rank feeds
-    its networks are, bit for bit, its dist.shard_bounds slice of the batch a one-process train() builds under those seeds -- crop,
-    flips, removed points and noise -- and the logged loss, the summaries, results.txt and the checkpoints are those of the
-    global batch, written once, by rank 0.  In this order:
-      * rank 0's random state becomes everybody's before anything is drawn (dist.broadcast_rng_state), and rank 0's
-        torch.initial_seed() every rank's Transforms.seed;
-      * both models are built, and restored, on every rank; GradientAverager.broadcast_parameters(); the pose model's BatchNorm
-        layers normalise over the frames of all ranks (sync_batch_norm(BatchNormGroup)) unless sync_batch_norm=False, which gives
-        the reference's DataParallel behaviour -- every replica normalises with its own shard's statistics, the reduced gradient
-        is then not the whole batch's, and the checkpoint holds rank 0's running statistics;
-      * the loader shards every global batch and draws the crops of all of it (crops="global"), Transforms draws for all of it
-        (shard=); a global batch of fewer frames than ranks is skipped on every rank and is no step (n_train_steps(world=));
-      * every step: the forwards and the backward on the rank's frames, GradientAverager.average(n_local, n_global), the optimizer's
-        step on the reduced gradients -- no collective besides the averager's and BatchNorm's;
-      * at a checkpoint or summary step, where the loop waits anyway, the ranks' per-frame loss terms are summed (one all-reduce
-        of four fp64 numbers): Loss= and the scalars are the global batch's, sum over ranks of n_local / n_global x the rank's;
-      * at a summary step the tensors log_summary takes are gathered in rank order, which is batch order, and rank 0 makes the one
-        call: histograms and panels are the whole batch's;
-      * writers (summary_writer_factory is not called elsewhere), results.txt and checkpoints are rank 0's alone; a barrier follows
-        the last save_model;
-      * validate() runs on every rank over the whole validation set -- the replicas are bit-identical, so are the numbers and
-        best_results; only rank 0 has a writer and a log.  Sharding the validation set is not built.
-    With return_results every rank returns the same values; the dict has one more key, 'digest': replica_digest() of the rank's
-    final parameters, buffers and optimizer state, equal on every rank while the replicas are bit-identical (they are with
-    sync_batch_norm=True; with False the BatchNorm running statistics are per rank).  world=1 is the one-process path, bit for bit."""
+          sync_batch_norm=True,
+          session=None):
+    """The loop of train_ranks() and train_resumable(): train_ranks()'s arguments and `session`, the hooks of a resumable run
+    (_Session; None for train_ranks: nothing of a session is read, written or checked)."""
+    arguments = dict(locals())      # before anything else is bound: what the call was given
     if device == "cuda" or device == "gpu":
         device = torch.device("cuda")
     else:
@@ -239,6 +410,21 @@ def train_ranks(train_image_path,
             if len(paths) != n_val_sample:
                 raise KbnError(f"train: {n_val_sample} validation image paths, {len(paths)} {name} paths")
 
+    # ---- a resumable run: the newest complete state of checkpoint_path, refused or returned before anything is built or written ----
+    state = None
+    if session is not None:
+        contents = dict(zip(PATH_ARGUMENTS, (train_image_paths, train_sparse_depth_paths, train_intrinsics_paths)))
+        if validation_available:
+            contents.update(zip(PATH_ARGUMENTS[3:], (val_image_paths, val_sparse_depth_paths, val_intrinsics_paths, val_ground_truth_paths)))
+        state = session.start(checkpoint_path, argument_record(arguments, contents), n_train_step, n_checkpoint)
+        if state is not None and state["step"] >= n_train_step:      # finished in an earlier session
+            if not return_results:
+                return None
+            return ({"train_step": state["step"], "best_results": state["best_results"], "finished": True, "resumed_from": state["step"],
+                     "digest": state["digest"]}, list(state["logged"]), [])
+        if state is not None:
+            best_results = state["best_results"]
+
     # ---- the models: what KBNetModel(trainable=True) refuses is refused before anything is written ----
     depth_model = KBNetModel(
         input_channels_image=input_channels_image, input_channels_depth=input_channels_depth,
@@ -257,10 +443,11 @@ def train_ranks(train_image_path,
     pose_model.requires_grad_(True).set_batch_norm("batch")      # the reference's pose_model.train()
     parameters_pose_model = pose_model.parameters()
 
-    if depth_model_restore_path is not None and depth_model_restore_path != "":
-        depth_model.restore_model(depth_model_restore_path)
-    if pose_model_restore_path is not None and pose_model_restore_path != "":
-        pose_model.restore_model(pose_model_restore_path)
+    if state is None:      # a continuation restores its own checkpoints, with the optimizer, once that exists
+        if depth_model_restore_path is not None and depth_model_restore_path != "":
+            depth_model.restore_model(depth_model_restore_path)
+        if pose_model_restore_path is not None and pose_model_restore_path != "":
+            pose_model.restore_model(pose_model_restore_path)
 
     averager = None
     if world > 1:
@@ -300,42 +487,43 @@ def train_ranks(train_image_path,
 
         # ---- the head of results.txt ----
         log = summary.log if main else (lambda s, filepath=None, to_console=True: None)
-        log("Training input paths:", log_path)
-        for path in (train_image_path, train_sparse_depth_path, train_intrinsics_path):
-            log(path, log_path)
-        log("", log_path)
-        log("Validation input paths:", log_path)
-        for path in (val_image_path, val_sparse_depth_path, val_intrinsics_path, val_ground_truth_path):
-            log(path, log_path)
-        log("", log_path)
-        if main:
-            summary.log_input_settings(
-                log_path, n_batch=n_batch, n_height=n_height, n_width=n_width, input_channels_image=input_channels_image,
-                input_channels_depth=input_channels_depth, normalized_image_range=normalized_image_range,
-                outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold)
-            summary.log_network_settings(
-                log_path, min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
-                max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
-                n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
-                n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
-                resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
-                min_predict_depth=min_predict_depth, max_predict_depth=max_predict_depth, weight_initializer=weight_initializer,
-                activation_func=activation_func, parameters_depth_model=parameters_depth_model, parameters_pose_model=parameters_pose_model)
-            summary.log_training_settings(
-                log_path, n_batch=n_batch, n_train_sample=n_train_sample, n_train_step=n_train_step, learning_rates=learning_rates,
-                learning_schedule=learning_schedule, augmentation_probabilities=augmentation_probabilities,
-                augmentation_schedule=augmentation_schedule, augmentation_random_crop_type=augmentation_random_crop_type,
-                augmentation_random_flip_type=augmentation_random_flip_type, augmentation_random_remove_points=augmentation_random_remove_points,
-                augmentation_random_noise_type=augmentation_random_noise_type, augmentation_random_noise_spread=augmentation_random_noise_spread)
-            summary.log_loss_func_settings(
-                log_path, w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness,
-                w_weight_decay_depth=w_weight_decay_depth, w_weight_decay_pose=w_weight_decay_pose)
-            summary.log_evaluation_settings(log_path, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth)
-            summary.log_system_settings(
-                log_path, checkpoint_path=checkpoint_path, n_checkpoint=n_checkpoint, summary_event_path=event_path, n_summary=n_summary,
-                n_summary_display=n_summary_display, validation_start_step=validation_start_step,
-                depth_model_restore_path=depth_model_restore_path, pose_model_restore_path=pose_model_restore_path, device=device,
-                n_thread=n_thread)
+        if state is None:      # the path and settings blocks: once, on the fresh start
+            log("Training input paths:", log_path)
+            for path in (train_image_path, train_sparse_depth_path, train_intrinsics_path):
+                log(path, log_path)
+            log("", log_path)
+            log("Validation input paths:", log_path)
+            for path in (val_image_path, val_sparse_depth_path, val_intrinsics_path, val_ground_truth_path):
+                log(path, log_path)
+            log("", log_path)
+            if main:
+                summary.log_input_settings(
+                    log_path, n_batch=n_batch, n_height=n_height, n_width=n_width, input_channels_image=input_channels_image,
+                    input_channels_depth=input_channels_depth, normalized_image_range=normalized_image_range,
+                    outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold)
+                summary.log_network_settings(
+                    log_path, min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
+                    max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
+                    n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
+                    n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
+                    resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
+                    min_predict_depth=min_predict_depth, max_predict_depth=max_predict_depth, weight_initializer=weight_initializer,
+                    activation_func=activation_func, parameters_depth_model=parameters_depth_model, parameters_pose_model=parameters_pose_model)
+                summary.log_training_settings(
+                    log_path, n_batch=n_batch, n_train_sample=n_train_sample, n_train_step=n_train_step, learning_rates=learning_rates,
+                    learning_schedule=learning_schedule, augmentation_probabilities=augmentation_probabilities,
+                    augmentation_schedule=augmentation_schedule, augmentation_random_crop_type=augmentation_random_crop_type,
+                    augmentation_random_flip_type=augmentation_random_flip_type, augmentation_random_remove_points=augmentation_random_remove_points,
+                    augmentation_random_noise_type=augmentation_random_noise_type, augmentation_random_noise_spread=augmentation_random_noise_spread)
+                summary.log_loss_func_settings(
+                    log_path, w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness,
+                    w_weight_decay_depth=w_weight_decay_depth, w_weight_decay_pose=w_weight_decay_pose)
+                summary.log_evaluation_settings(log_path, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth)
+                summary.log_system_settings(
+                    log_path, checkpoint_path=checkpoint_path, n_checkpoint=n_checkpoint, summary_event_path=event_path, n_summary=n_summary,
+                    n_summary_display=n_summary_display, validation_start_step=validation_start_step,
+                    depth_model_restore_path=depth_model_restore_path, pose_model_restore_path=pose_model_restore_path, device=device,
+                    n_thread=n_thread)
 
         # ---- the optimizer and the schedules ----
         learning_schedule_pos, learning_rate = 0, learning_rates[0]
@@ -343,18 +531,54 @@ def train_ranks(train_image_path,
         optimizer = optim.Adam([{"params": parameters_depth_model, "weight_decay": w_weight_decay_depth},
                                 {"params": parameters_pose_model, "weight_decay": w_weight_decay_pose}], lr=learning_rate)
 
-        train_step = 0
-        time_start = time.time()
-        log("Begin training...", log_path)
-        for epoch in range(1, learning_schedule[-1] + 1):
-            learning_schedule_pos, learning_rate, moved = scheduled(epoch, learning_schedule_pos, learning_schedule, learning_rates)
-            if moved:
-                for g in optimizer.param_groups:
-                    g["lr"] = learning_rate
-            augmentation_schedule_pos, augmentation_probability, _ = scheduled(
-                epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
+        def save(model, path):      # a session's files appear whole or not at all
+            if session is None:
+                model.save_model(path, train_step, optimizer)
+            else:
+                session.write(path, lambda part: model.save_model(part, train_step, optimizer))
 
-            for batch, (image0, image1, image2, sparse_depth0, intrinsics) in enumerate(train_loader):
+        def snapshot(digest=None):      # what a continuation needs beyond the two checkpoints; no wait for the device
+            return {"step": train_step, "epoch": epoch, "batch": batch + 1, "loader": train_loader.state_dict(),
+                    "transforms": train_transforms.state_dict(), "random": random_state(device),
+                    "best_results": {k: _plain(v) for k, v in best_results.items()}, "logged": list(logged),
+                    "seconds": seconds_before + time.time() - time_start, "digest": digest}
+
+        train_step, first_epoch, first_batch, seconds_before, stopped = 0, 1, 0, 0.0, False
+        if state is None:
+            log("Begin training...", log_path)
+        else:
+            # the checkpoints of the state's step, the optimizer with them; every schedule position up to the state's epoch,
+            # replayed; the rest of that epoch, or -- after its last batch -- the next one with its own schedule moves
+            for message in session.skipped:
+                log(message, log_path)
+            train_step = state["step"]
+            depth_model.restore_model(depth_model_checkpoint_path.format(train_step), optimizer)
+            pose_model.restore_model(pose_model_checkpoint_path.format(train_step))
+            for epoch in range(1, state["epoch"] + 1):
+                learning_schedule_pos, learning_rate, _ = scheduled(epoch, learning_schedule_pos, learning_schedule, learning_rates)
+                augmentation_schedule_pos, augmentation_probability, _ = scheduled(
+                    epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
+            for g in optimizer.param_groups:
+                g["lr"] = learning_rate
+            first_epoch = state["epoch"] + (0 if state["loader"] else 1)
+            first_batch = state["batch"] if state["loader"] else 0
+            train_loader.load_state_dict(state["loader"])
+            train_transforms.load_state_dict(state["transforms"])
+            logged, seconds_before = list(state["logged"]), float(state["seconds"])
+            set_random_state(state["random"], device)      # last: building the models drew from the generators
+            log("Resuming training from step {}...".format(train_step), log_path)
+        time_start = time.time()
+        for epoch in range(first_epoch, learning_schedule[-1] + 1):
+            if first_batch == 0:      # not in the middle of the epoch a continuation starts in: its moves were replayed above
+                learning_schedule_pos, learning_rate, moved = scheduled(epoch, learning_schedule_pos, learning_schedule, learning_rates)
+                if moved:
+                    for g in optimizer.param_groups:
+                        g["lr"] = learning_rate
+                augmentation_schedule_pos, augmentation_probability, _ = scheduled(
+                    epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
+
+            batches, first_batch = enumerate(train_loader, first_batch), 0
+            for batch, (image0, image1, image2, sparse_depth0, intrinsics) in batches:
                 shard = None
                 if world > 1:
                     n_global = train_loader.global_batch_size(batch)
@@ -400,7 +624,7 @@ def train_ranks(train_image_path,
 
                 if (train_step % n_checkpoint) == 0:
                     value = loss.item()      # the loop's wait for the device, where the reference logs the loss
-                    time_elapse = (time.time() - time_start) / 3600
+                    time_elapse = (seconds_before + time.time() - time_start) / 3600
                     time_remain = (n_train_step - train_step) * time_elapse / train_step
                     log("Step={:6}/{}  Loss={:.5f}  Time Elapsed={:.2f}h  Time Remaining={:.2f}h".format(
                         train_step, n_train_step, value, time_elapse, time_remain), log_path)
@@ -414,18 +638,38 @@ def train_ranks(train_image_path,
                             normalized_image_range=normalized_image_range)
                     for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
                         if main:
-                            model.save_model(pattern.format(train_step), train_step, optimizer)
+                            save(model, pattern.format(train_step))
                         checkpoints.append(pattern.format(train_step))
+                    if session is not None and train_step < n_train_step:      # the last step's state follows the loop
+                        session.save_state(snapshot())
 
-        for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-            if main:
-                model.save_model(pattern.format(train_step), train_step, optimizer)
-            if pattern.format(train_step) not in checkpoints:
-                checkpoints.append(pattern.format(train_step))
+                if session is not None and train_step < n_train_step and session.budget.step_done():
+                    # the session ends here, the step complete: off the checkpoint grid its two checkpoints and its state are
+                    # written now (on the grid they just were), and neither a Step= line nor a validation is
+                    if (train_step % n_checkpoint) != 0:
+                        for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
+                            save(model, pattern.format(train_step))
+                            checkpoints.append(pattern.format(train_step))
+                        session.save_state(snapshot())
+                    stopped = True
+                    break
+            if stopped:
+                break
+
         digest = None
+        if not stopped:
+            for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
+                if main:
+                    save(model, pattern.format(train_step))
+                if pattern.format(train_step) not in checkpoints:
+                    checkpoints.append(pattern.format(train_step))
         if world > 1:
             digest = replica_digest((depth_model, pose_model), optimizer)
             dist.barrier()      # no rank leaves, and nobody reads the checkpoints, before rank 0 has written them
+        if session is not None and (return_results or not stopped):
+            digest = replica_digest((depth_model, pose_model), optimizer)
+        if session is not None and not stopped:
+            session.save_state(snapshot(digest))
     except BaseException:
         for writer in (train_summary_writer, val_summary_writer):
             if writer is not None:
@@ -444,7 +688,43 @@ def train_ranks(train_image_path,
     results = {"train_step": train_step, "best_results": best_results}
     if world > 1:
         results["digest"] = digest      # of this rank's replica: the one value that may differ between ranks, and must not
+    if session is not None:
+        results.update(finished=not stopped, resumed_from=None if state is None else state["step"], digest=digest)
     return results, logged, checkpoints
+
+
+def train_ranks(*arguments, **keywords):
+    """train() with three more keyword-only arguments -- rank, world, sync_batch_norm -- and everything train()'s docstring says.
+
+    Data-parallel training: `rank` of `world` processes, one a GPU, each calling train_ranks() with the same arguments inside an
+    initialised process group (kb.dist.init; KbnError otherwise, before anything is written) on its current device -- launch()
+    below starts them (INTEGRATION.md, "On several GPUs"; DESIGN section 8p).  n_batch stays the GLOBAL batch.  With the ranks started from one set of seeds, the tensors every rank feeds
+    its networks are, bit for bit, its dist.shard_bounds slice of the batch a one-process train() builds under those seeds -- crop,
+    flips, removed points and noise -- and the logged loss, the summaries, results.txt and the checkpoints are those of the
+    global batch, written once, by rank 0.  In this order:
+      * rank 0's random state becomes everybody's before anything is drawn (dist.broadcast_rng_state), and rank 0's
+        torch.initial_seed() every rank's Transforms.seed;
+      * both models are built, and restored, on every rank; GradientAverager.broadcast_parameters(); the pose model's BatchNorm
+        layers normalise over the frames of all ranks (sync_batch_norm(BatchNormGroup)) unless sync_batch_norm=False, which gives
+        the reference's DataParallel behaviour -- every replica normalises with its own shard's statistics, the reduced gradient
+        is then not the whole batch's, and the checkpoint holds rank 0's running statistics;
+      * the loader shards every global batch and draws the crops of all of it (crops="global"), Transforms draws for all of it
+        (shard=); a global batch of fewer frames than ranks is skipped on every rank and is no step (n_train_steps(world=));
+      * every step: the forwards and the backward on the rank's frames, GradientAverager.average(n_local, n_global), the optimizer's
+        step on the reduced gradients -- no collective besides the averager's and BatchNorm's;
+      * at a checkpoint or summary step, where the loop waits anyway, the ranks' per-frame loss terms are summed (one all-reduce
+        of four fp64 numbers): Loss= and the scalars are the global batch's, sum over ranks of n_local / n_global x the rank's;
+      * at a summary step the tensors log_summary takes are gathered in rank order, which is batch order, and rank 0 makes the one
+        call: histograms and panels are the whole batch's;
+      * writers (summary_writer_factory is not called elsewhere), results.txt and checkpoints are rank 0's alone; a barrier follows
+        the last save_model;
+      * validate() runs on every rank over the whole validation set -- the replicas are bit-identical, so are the numbers and
+        best_results; only rank 0 has a writer and a log.  Sharding the validation set is not built.
+    With return_results every rank returns the same values; the dict has one more key, 'digest': replica_digest() of the rank's
+    final parameters, buffers and optimizer state, equal on every rank while the replicas are bit-identical (they are with
+    sync_batch_norm=True; with False the BatchNorm running statistics are per rank).  world=1 is the one-process path, bit for bit."""
+    bound = _RANKS_SIGNATURE.bind(*arguments, **keywords)
+    return _train_loop(*bound.args, **bound.kwargs)
 
 
 def train(*arguments, **keywords):
@@ -474,11 +754,52 @@ def train(*arguments, **keywords):
     return train_ranks(*bound.args, **bound.kwargs)
 
 
-# train()'s signature is the reference's and stays it: train_ranks()'s without its three last arguments, written once
-_TRAIN_SIGNATURE = inspect.signature(train_ranks)
-_TRAIN_SIGNATURE = _TRAIN_SIGNATURE.replace(parameters=[p for p in _TRAIN_SIGNATURE.parameters.values()
+def train_resumable(*arguments, max_steps=None, max_seconds=None, stop_signals=(signal.SIGTERM,), keep_states=2, **keywords):
+    """train() in sessions: train()'s arguments, names, order and defaults, and four more keyword-only ones.  The same call, made
+    in one job slot after another, carries a run to its end, and the run it makes is, bit for bit, the one an uninterrupted
+    train() makes under the seeds of the first session ("Training in job slots").
+
+    A call looks for the newest complete training state in checkpoint_path (find_state).  None: a fresh start, as train()'s, the two
+    restore paths honoured.  One of the last step: the run is finished, the call returns at once and writes nothing.  Otherwise it
+    continues after that state's step: the two checkpoints of the step with the optimizer's state, the loader's place in its epoch
+    with the crops already drawn ahead (TrainingFrameLoader.load_state_dict), Transforms' seed and call count, NumPy's, torch's and
+    the device's generator states, best_results, the logged losses and the time trained so far; the schedule positions are
+    replayed.  Every argument that shapes the trajectory must be what the first session was given (argument_record; KbnError names
+    the first that differs, before anything is written); checkpoint_path, the restore paths, device, n_thread, workers, the
+    writers' factory and return_results may change.
+
+    The session ends early -- the step in progress always completes -- after max_steps steps, after max_seconds of host time
+    since the call began (read between steps; no step waits for the device that does not in train()), or when one of stop_signals
+    arrives (Budget: the handlers set a flag, are installed on the main thread only and are put back on return or error).
+    checkpoint_path/train_state-<step>.pth is written after the two checkpoints of every n_checkpoint-th step, of the step a
+    session stops at (that step's two checkpoints with it when it is off the grid; no Step= line, no validation) and of the last
+    step.  Each of the three files is written under a temporary name and moved into place.  keep_states states are kept; an older
+    one goes, and with it the checkpoints of a stop's step; those of the grid and of the last step stay.
+
+    results.txt: the path and settings blocks once, "Resuming training from step <s>..." where a continuation begins, Time Elapsed
+    over all sessions.  Every session opens its own event files.  With return_results the results dict has three more keys:
+    'finished', 'resumed_from' (a step or None) and 'digest' (replica_digest of what the session ended with); the logged list
+    is the whole run's, the checkpoint paths are this session's.
+
+    One process, one GPU.  Continuing a data-parallel run (train_ranks, launch) is not built."""
+    bound = _TRAIN_SIGNATURE.bind(*arguments, **keywords)
+    budget = Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals)
+    session = _Session(budget, keep_states)
+    with budget:
+        return _train_loop(*bound.args, **bound.kwargs, session=session)
+
+
+# train()'s signature is the reference's and stays it: the loop's without its four last arguments, written once
+_RANKS_SIGNATURE = inspect.signature(_train_loop)
+_RANKS_SIGNATURE = _RANKS_SIGNATURE.replace(parameters=[p for p in _RANKS_SIGNATURE.parameters.values() if p.name != "session"])
+_TRAIN_SIGNATURE = _RANKS_SIGNATURE.replace(parameters=[p for p in _RANKS_SIGNATURE.parameters.values()
                                                         if p.name not in ("rank", "world", "sync_batch_norm")])
+train_ranks.__signature__ = _RANKS_SIGNATURE
 train.__signature__ = _TRAIN_SIGNATURE
+train_resumable.__signature__ = _TRAIN_SIGNATURE.replace(
+    parameters=list(_TRAIN_SIGNATURE.parameters.values()) + [
+        inspect.Parameter(name, inspect.Parameter.KEYWORD_ONLY, default=default)
+        for name, default in (("max_steps", None), ("max_seconds", None), ("stop_signals", (signal.SIGTERM,)), ("keep_states", 2))])
 
 
 # ------------------------------------------------------------------------------------------------ one process per GPU

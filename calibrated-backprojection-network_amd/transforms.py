@@ -51,6 +51,17 @@ class Transforms(object):
         self.seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
         self.calls = 0      # transform() calls so far: a word of every draw's counter
 
+    def state_dict(self) -> dict:
+        """What the removal and noise draws of the next transform() depend on beyond np.random and torch's generators: the key and
+        the count of calls."""
+        return {"seed": int(self.seed), "calls": int(self.calls)}
+
+    def load_state_dict(self, state: dict) -> None:
+        seed, calls = int(state["seed"]), int(state["calls"])
+        if not 0 <= seed <= 0xFFFFFFFFFFFFFFFF or calls < 0:
+            raise ValueError('Transforms state: seed {} calls {}'.format(seed, calls))
+        self.seed, self.calls = seed, calls
+
     def draw(self, n_batch: int, random_transform_probability: float = 0.50) -> List[int]:
         """The host part of transform(): one flags value a frame (ops.AUGMENT_* bits), from np.random.rand(n_batch) drawn in the
         reference's order -- the transform decision, then one more draw for each enabled branch: horizontal flip, vertical flip,

@@ -499,6 +499,38 @@ def broadcast_object(value, src: int = 0):
     return box[0]
 
 
+class StopVote:
+    """How the ranks of a run in sessions (kb.training.train_ranks_resumable) agree to stop on the same step: vote(wish) is True on
+    every rank when any rank wishes -- one all-reduce (MAX) of one integer on a CPU tensor over gloo, so nothing waits for the
+    device.  Signals and clocks differ between ranks, and a rank that left the loop alone would leave the others waiting in the
+    next step's all-reduce; so every rank calls vote() after every step, whether it wishes or not: a collective only some ranks
+    enter is the one way to hang.
+
+    Construction is itself a collective where the default group is not gloo's (RCCL moves device tensors only): every rank makes the
+    gloo group beside it (new_group), in the same place.  Under gloo the default group carries the vote.  With world == 1 no
+    collective runs and vote(wish) is wish."""
+
+    def __init__(self, rank: int, world: int):
+        rank, world = int(rank), int(world)
+        if world < 1 or not 0 <= rank < world:
+            raise KbnError(f"StopVote: rank {rank} of world {world}")
+        if world > 1 and not (dist.is_initialized() and dist.get_world_size() == world and dist.get_rank() == rank):
+            raise KbnError(f"StopVote: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init)")
+        self.rank, self.world = rank, world
+        self.collective = world > 1
+        self.group = None
+        if self.collective and dist.get_backend() != "gloo":
+            self.group = dist.new_group(backend="gloo")
+        self._box = torch.zeros(1, dtype=torch.int64)
+
+    def vote(self, wish) -> bool:
+        if not self.collective:
+            return bool(wish)
+        self._box[0] = 1 if wish else 0
+        dist.all_reduce(self._box, op=dist.ReduceOp.MAX, group=self.group)
+        return bool(int(self._box[0]))
+
+
 def gather_frames(tensor: torch.Tensor, n_global: int, rank: int, world: int) -> torch.Tensor:
     """This rank's `shard_bounds` frames of a global batch -> all n_global frames, in rank order -- which is batch order, the shards
     being contiguous -- on every rank: one all_gather_into_tensor through slots of the largest shard's size.  For the summaries of

@@ -620,7 +620,9 @@ class TrainingFrameLoader:
 
     For the same reason an epoch that is left between two batches and continued elsewhere (kb.training.train_resumable) needs more
     than np.random's state: `state_dict()` holds the epoch's order, the next batch's index and the plans -- crops included -- of the
-    batches already in flight, and after `load_state_dict(state)` the next `iter()` yields the rest of that epoch (one process)."""
+    batches already in flight, and after `load_state_dict(state)` the next `iter()` yields the rest of that epoch.  With `world` ranks
+    and crops="global" (kb.training.train_ranks_resumable) the state is the global one -- the plans of whole global batches, equal
+    on every rank -- and every rank continues from rank 0's, taking its shard of each stored plan."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str], intrinsics_paths: Sequence[str],
                  shape=None, random_crop_type=["none"], batch_size: int = 8, shuffle: bool = True,
@@ -685,9 +687,9 @@ class TrainingFrameLoader:
             self._headers[i] = tuple(heads)
         return self._headers[i]
 
-    def _plan(self, idx: Sequence[int], keep=None):
+    def _plan(self, idx: Sequence[int]):
         """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped.
-        `keep` (first, last): `idx` is a global batch, checked and drawn for as a whole; the list holds samples idx[first:last]."""
+        With crops="global" `idx` is a global batch, checked and drawn for as a whole; _enqueue_planned takes the rank's slice."""
         heads = [self._header(i) for i in idx]
         (_, _, c, bits), (_, _, cd, dbits) = heads[0]
         if bits != 8 or cd != 1:
@@ -713,7 +715,7 @@ class TrainingFrameLoader:
                                    f"{size[0]} x {size[1]}, {self.image_paths[idx[0]]} is {shape[0]} x {shape[1]}")
             starts = [(0, 0)] * len(idx)
         frames = [(i, hh, ww, y, x) for i, (hh, ww), (y, x) in zip(idx, sizes, starts)]
-        return frames if keep is None else frames[keep[0]:keep[1]], shape, c, dbits, self.do_random_crop
+        return frames, shape, c, dbits, self.do_random_crop
 
     # -- on a driver thread: read, decode into pinned memory, async H2D + unpack on the copy stream --
     def _staging(self, slot: int, image_bytes: int, depth_bytes: int, frames: int):
@@ -762,16 +764,19 @@ class TrainingFrameLoader:
     def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0, plan=None):
         """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn.
         `batch`, `first`: with crops="global" the global batch and where `idx` starts in it.  `plan`: what _plan returned for this
-        batch in an earlier session (load_state_dict) -- nothing is drawn."""
+        batch -- the GLOBAL batch with crops="global" -- in an earlier session (load_state_dict): nothing is drawn."""
         future = self._enqueue_planned(idx, batch, first, plan)
         self._plans.append(getattr(future, "plan", None))
         return future
 
     def _enqueue_planned(self, idx: Sequence[int], batch, first: int, plan):
-        error = None
-        if batch is not None and plan is None:      # the whole batch's draws, on every rank, before anything else: an empty shard draws too
+        """The future's `plan` is what state_dict() stores: the plan of the whole global batch with crops="global" -- the same on
+        every rank, an empty shard's included -- of which this rank submits its slice; the plan of `idx` otherwise."""
+        error, whole = None, None
+        if batch is not None:      # the whole batch's draws, on every rank, before anything else: an empty shard draws too
             try:
-                plan = self._plan(batch, (first, first + len(idx)))
+                whole = self._plan(batch) if plan is None else plan
+                plan = (whole[0][first:first + len(idx)],) + tuple(whole[1:])
             except Exception as e:      # noqa: BLE001  (raised again by .result() when the batch is due)
                 error = e
         if not idx and error is None:      # this rank's shard of a short last batch: zero frames, no staging set, nothing launched
@@ -779,6 +784,7 @@ class TrainingFrameLoader:
             empty: Future = Future()
             empty.set_result((tuple(torch.empty(s, dtype=torch.float32, device=self.device)
                                     for s in ((0, 3, h, w), (0, 3, h, w), (0, 3, h, w), (0, 1, h, w), (0, 3, 3))), None))
+            empty.plan = whole
             return empty
         slot = self._serial % (self.prefetch + 1)
         self._serial += 1
@@ -792,17 +798,21 @@ class TrainingFrameLoader:
             failed.set_exception(error)
             return failed
         future = self._driver.submit(self._submit, slot, *plan)
-        future.plan = plan
+        future.plan = plan if whole is None else whole
         return future
 
     def state_dict(self) -> dict:
         """Where the running epoch stands, between two batches: the epoch's order, the index of the batch iter() hands out next and
         the finished plans (_plan's frames with their crop origins, shape and format) of the batches already enqueued beyond it --
         their crops were drawn from np.random ahead of whatever the iterating thread drew since, so np.random's state alone does not
-        bring them back.  Empty before the first epoch and after an epoch's last batch.  Plain Python numbers only.  One process:
-        a sharded loader (world > 1) raises KbnError."""
-        if self.world > 1:
-            raise KbnError("TrainingFrameLoader: state_dict of a sharded loader (world > 1) is not built")
+        bring them back.  Empty before the first epoch and after an epoch's last batch.  Plain Python numbers only.
+
+        A sharded loader (world > 1) with crops="global" holds the GLOBAL state: the plans are those of the whole global batches,
+        so ranks that drew alike return equal dicts (a rank whose shard of a short last batch is empty too), and any rank's state
+        continues every rank.  With crops="own" a sharded loader raises KbnError: its ranks' draws are not one state."""
+        if self.world > 1 and self.crops != "global":
+            raise KbnError("TrainingFrameLoader: state_dict of a sharded loader (world > 1) needs crops='global': with crops='own' every "
+                           "rank draws for its own samples, and no one state continues them all")
         if self._order is None or self._next >= len(self):
             return {}
         if any(plan is None for plan in self._plans):
@@ -816,10 +826,12 @@ class TrainingFrameLoader:
         """The next iter() continues the epoch `state` (a state_dict()) was taken in: the stored order (nothing is drawn from torch's
         generator), from batch `next` on; the stored plans are submitted as they are and crops are drawn only for the batches beyond
         them, in the order the uninterrupted iteration draws them.  An empty state: the next iter() is an ordinary one.  KbnError for
-        a state of another path count, batch size or prefetch depth."""
+        a state of another path count, batch size or prefetch depth.  A sharded loader with crops="global" takes the global state
+        (state_dict) and submits its dist.shard_bounds share of each stored plan; with crops="own" it raises KbnError.  The state does
+        not say at which `world` it was taken: whoever stores it keeps that beside it (kb.training's argument record does)."""
         what = "TrainingFrameLoader: load_state_dict"
-        if self.world > 1:
-            raise KbnError(f"{what} of a sharded loader (world > 1) is not built")
+        if self.world > 1 and self.crops != "global":
+            raise KbnError(f"{what} of a sharded loader (world > 1) needs crops='global'")
         if not state:
             self._resume = None
             return
@@ -847,7 +859,7 @@ class TrainingFrameLoader:
         if self._resume is not None:      # the rest of an epoch another session began (load_state_dict): its order, its plans
             resume, self._resume = self._resume, None
             self._order, first = resume["order"], resume["next"]
-            batches = [(shard,) for shard in shard_batches(self._order, self.batch_size, 0, 1)]
+            batches = self._batches(self._order)
             plans = resume["plans"] + [None] * self.prefetch      # a batch without a stored plan is drawn for
             self._pending = pending = [self._enqueue(*batches[first + j], plan=plans[j])
                                        for j in range(min(self.prefetch, len(batches) - first))]
@@ -861,14 +873,18 @@ class TrainingFrameLoader:
             torch.distributed.broadcast_object_list(shared, src=0)
             order = shared[0]
         self._order = order
-        batches = shard_batches(order, self.batch_size, self.rank, self.world)
-        if self.crops == "global":      # (shard, global batch, the shard's place in it)
-            batches = [(shard, list(order[b * self.batch_size:(b + 1) * self.batch_size]),
-                        shard_bounds(self.global_batch_size(b), self.rank, self.world)[0]) for b, shard in enumerate(batches)]
-        else:
-            batches = [(shard,) for shard in batches]
+        batches = self._batches(order)
         self._pending = pending = [self._enqueue(*batches[b]) for b in range(min(self.prefetch, len(batches)))]
         return self._epoch(batches, pending)
+
+    def _batches(self, order):
+        """_enqueue's arguments for every batch of an epoch in `order`: this rank's shard, and with crops="global" the global
+        batch and the shard's place in it."""
+        batches = shard_batches(order, self.batch_size, self.rank, self.world)
+        if self.crops == "global":
+            return [(shard, list(order[b * self.batch_size:(b + 1) * self.batch_size]),
+                     shard_bounds(self.global_batch_size(b), self.rank, self.world)[0]) for b, shard in enumerate(batches)]
+        return [(shard,) for shard in batches]
 
     def _epoch(self, batches, pending, first: int = 0):
         self._next = first

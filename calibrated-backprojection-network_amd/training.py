@@ -20,8 +20,10 @@ train() has the reference's signature and drives one GPU; train_ranks() is the s
 sync_batch_norm -- train() is train_ranks(world=1).  DESIGN section 8p has the design of the data-parallel form.
 
 train_resumable() is train() in sessions: the same call, made in one job slot after another, continues the run from the state the
-last one left in checkpoint_path, bit for bit as the uninterrupted run.  All three entry points run one loop,
-_train_loop."""
+last one left in checkpoint_path, bit for bit as the uninterrupted run.  train_ranks_resumable() is the same for
+train_ranks() -- the ranks agree on the step a session stops after, rank 0 writes the one state every rank continues from -- and
+launch_resumable() starts its processes and passes the scheduler's signal on to them.  All entry points run one
+loop, _train_loop."""
 
 from __future__ import annotations
 
@@ -100,6 +102,9 @@ PATH_ARGUMENTS = ("train_image_path", "train_sparse_depth_path", "train_intrinsi
 # what is not a setting at all
 UNRECORDED_ARGUMENTS = ("checkpoint_path", "depth_model_restore_path", "pose_model_restore_path", "device", "n_thread", "workers",
                         "summary_writer_factory", "return_results")
+# what train_ranks() adds to train() and the record keeps: how many ranks build the batch, and over which frames the pose network
+# normalises.  The values of a state written before they were recorded: the one-process run's
+RANK_ARGUMENTS = {"world": 1, "sync_batch_norm": True}
 STATE_FILE = "train_state-{}.pth"
 _STATE_NAME = re.compile(r"^train_state-(\d+)\.pth$")
 
@@ -119,17 +124,25 @@ def _plain(value):
 
 def argument_record(arguments: dict, path_contents: dict) -> dict:
     """Every argument of train() that shapes the trajectory, in train()'s order: all but UNRECORDED_ARGUMENTS, the seven path
-    arguments by the content of their lists (`path_contents`: name -> paths; a validation argument that is None stays None)."""
+    arguments by the content of their lists (`path_contents`: name -> paths; a validation argument that is None stays None).  Then
+    train_ranks()'s world and sync_batch_norm, where `arguments` holds them (the loop's do): a run continues with the ranks it began
+    with.  rank is no setting, and launch()'s backend and devices are recorded nowhere: they may change."""
     record = {}
     for name in _TRAIN_SIGNATURE.parameters:
         if name not in UNRECORDED_ARGUMENTS:
             record[name] = _plain(path_contents.get(name)) if name in PATH_ARGUMENTS else _plain(arguments[name])
+    for name in RANK_ARGUMENTS:
+        if name in arguments:
+            record[name] = _plain(arguments[name])
     return record
 
 
 def check_argument_record(recorded: dict, given: dict) -> None:
-    """KbnError naming the first argument, in train()'s order, whose value is not the one the run was started with."""
+    """KbnError naming the first argument, in train()'s order (world and sync_batch_norm after them), whose value is not the one
+    the run was started with."""
     for name in given:
+        if name in RANK_ARGUMENTS and name not in recorded:      # a state from before the two were recorded: a one-process run's
+            recorded = dict(recorded, **{name: RANK_ARGUMENTS[name]})
         if name not in recorded or recorded[name] != given[name]:
             was, now = recorded.get(name, "<not recorded>"), given[name]
             if name in PATH_ARGUMENTS and isinstance(was, list) and isinstance(now, list):
@@ -201,6 +214,12 @@ def prune_states(checkpoint_path: str, keep_states: int, n_checkpoint: int, n_tr
     return removed
 
 
+def _stored_results(state: dict):
+    """What a call returns for a run that an earlier session finished: the last state's values, no checkpoint path."""
+    return ({"train_step": state["step"], "best_results": state["best_results"], "finished": True, "resumed_from": state["step"],
+             "digest": state["digest"]}, list(state["logged"]), [])
+
+
 class Budget:
     """When a session ends before the run does: after `max_steps` steps of this session, once `max_seconds` of host time have
     passed since the context was entered (`clock`, time.monotonic; read between steps, nothing waits for the device), or when one of
@@ -260,15 +279,33 @@ class _Session:
         self.budget, self.keep_states = budget, int(keep_states)
         self.checkpoint_path, self.record, self.skipped = None, None, []
         self.n_train_step = self.n_checkpoint = None
+        self.vote = dist.StopVote(0, 1)      # of one process; the loop of several ranks puts theirs here
 
-    def start(self, checkpoint_path, record, n_train_step, n_checkpoint):
-        """-> the state to continue from, or None for a fresh start.  Reads only; KbnError when `record` is not the run's."""
+    def start(self, checkpoint_path, record, n_train_step, n_checkpoint, rank=0, world=1):
+        """-> the state to continue from, or None for a fresh start.  Reads only; KbnError when `record` is not the run's.  With
+        several ranks rank 0 looks (find_state) and its answer -- a step or none, and the messages -- is everybody's: a file system
+        may show one rank a newest state cut short and another the whole of it.  Every rank then loads that one file, and every
+        rank raises for a record that is not the run's."""
         self.checkpoint_path, self.record = checkpoint_path, record
         self.n_train_step, self.n_checkpoint = int(n_train_step), int(n_checkpoint)
-        state, self.skipped = find_state(checkpoint_path)
+        if world == 1:
+            state, self.skipped = find_state(checkpoint_path)
+        else:
+            state, found = None, None
+            if rank == 0:
+                state, skipped = find_state(checkpoint_path)
+                found = (None if state is None else int(state["step"]), skipped)
+            step, self.skipped = dist.broadcast_object(found, src=0)
+            if step is not None and rank != 0:
+                state = torch.load(os.path.join(checkpoint_path, STATE_FILE.format(step)), map_location="cpu")
         if state is not None:
             check_argument_record(state["arguments"], record)
         return state
+
+    def step_done(self) -> bool:
+        """After every step of the session, on every rank: does the session end here?  This rank's wish (Budget.step_done) goes
+        through the ranks' vote, so the answer is the same everywhere."""
+        return self.vote.vote(self.budget.step_done() is not None)
 
     def write(self, path, writer):
         """writer(temporary name), then the move into place: `path` holds the old bytes or the new ones, never a part of them."""
@@ -416,12 +453,9 @@ def _train_loop(train_image_path,
         contents = dict(zip(PATH_ARGUMENTS, (train_image_paths, train_sparse_depth_paths, train_intrinsics_paths)))
         if validation_available:
             contents.update(zip(PATH_ARGUMENTS[3:], (val_image_paths, val_sparse_depth_paths, val_intrinsics_paths, val_ground_truth_paths)))
-        state = session.start(checkpoint_path, argument_record(arguments, contents), n_train_step, n_checkpoint)
+        state = session.start(checkpoint_path, argument_record(arguments, contents), n_train_step, n_checkpoint, rank, world)
         if state is not None and state["step"] >= n_train_step:      # finished in an earlier session
-            if not return_results:
-                return None
-            return ({"train_step": state["step"], "best_results": state["best_results"], "finished": True, "resumed_from": state["step"],
-                     "digest": state["digest"]}, list(state["logged"]), [])
+            return _stored_results(state) if return_results else None
         if state is not None:
             best_results = state["best_results"]
 
@@ -567,6 +601,8 @@ def _train_loop(train_image_path,
             logged, seconds_before = list(state["logged"]), float(state["seconds"])
             set_random_state(state["random"], device)      # last: building the models drew from the generators
             log("Resuming training from step {}...".format(train_step), log_path)
+        if session is not None and world > 1:      # on every rank, here: making the vote's group is a collective
+            session.vote = dist.StopVote(rank, world)
         time_start = time.time()
         for epoch in range(first_epoch, learning_schedule[-1] + 1):
             if first_batch == 0:      # not in the middle of the epoch a continuation starts in: its moves were replayed above
@@ -640,17 +676,21 @@ def _train_loop(train_image_path,
                         if main:
                             save(model, pattern.format(train_step))
                         checkpoints.append(pattern.format(train_step))
-                    if session is not None and train_step < n_train_step:      # the last step's state follows the loop
+                    if session is not None and main and train_step < n_train_step:      # the last step's state follows the loop
                         session.save_state(snapshot())
 
-                if session is not None and train_step < n_train_step and session.budget.step_done():
+                # every step of a session, on every rank, whatever the step: the ranks' vote is a collective (host-side; no
+                # wait for the device), and the wish of any rank during step s stops them all after step s
+                if session is not None and session.step_done() and train_step < n_train_step:
                     # the session ends here, the step complete: off the checkpoint grid its two checkpoints and its state are
                     # written now (on the grid they just were), and neither a Step= line nor a validation is
                     if (train_step % n_checkpoint) != 0:
                         for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-                            save(model, pattern.format(train_step))
+                            if main:
+                                save(model, pattern.format(train_step))
                             checkpoints.append(pattern.format(train_step))
-                        session.save_state(snapshot())
+                        if main:
+                            session.save_state(snapshot())
                     stopped = True
                     break
             if stopped:
@@ -663,13 +703,12 @@ def _train_loop(train_image_path,
                     save(model, pattern.format(train_step))
                 if pattern.format(train_step) not in checkpoints:
                     checkpoints.append(pattern.format(train_step))
-        if world > 1:
+        if world > 1 or (session is not None and (return_results or not stopped)):
             digest = replica_digest((depth_model, pose_model), optimizer)
-            dist.barrier()      # no rank leaves, and nobody reads the checkpoints, before rank 0 has written them
-        if session is not None and (return_results or not stopped):
-            digest = replica_digest((depth_model, pose_model), optimizer)
-        if session is not None and not stopped:
+        if session is not None and main and not stopped:
             session.save_state(snapshot(digest))
+        if world > 1:
+            dist.barrier()      # no rank leaves, and nobody reads the checkpoints or the state, before rank 0 has written them
     except BaseException:
         for writer in (train_summary_writer, val_summary_writer):
             if writer is not None:
@@ -781,8 +820,41 @@ def train_resumable(*arguments, max_steps=None, max_seconds=None, stop_signals=(
     'finished', 'resumed_from' (a step or None) and 'digest' (replica_digest of what the session ended with); the logged list
     is the whole run's, the checkpoint paths are this session's.
 
-    One process, one GPU.  Continuing a data-parallel run (train_ranks, launch) is not built."""
+    One process, one GPU.  A data-parallel run (train_ranks, launch) is continued by train_ranks_resumable() and
+    launch_resumable() below."""
     bound = _TRAIN_SIGNATURE.bind(*arguments, **keywords)
+    budget = Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals)
+    session = _Session(budget, keep_states)
+    with budget:
+        return _train_loop(*bound.args, **bound.kwargs, session=session)
+
+
+def train_ranks_resumable(*arguments, max_steps=None, max_seconds=None, stop_signals=(signal.SIGTERM,), keep_states=2, **keywords):
+    """train_ranks() in sessions: train_ranks()'s arguments, names, order and defaults (rank, world, sync_batch_norm too) and
+    train_resumable()'s four keyword-only ones, with everything the two docstrings say.  `world` processes, each calling it with
+    the same arguments inside an initialised process group -- launch_resumable() below starts them -- carry one data-parallel run
+    through job slots, and the run they make is, bit for bit, the one an uninterrupted launch() makes under the seeds of the first
+    session ("Training in job slots").  world=1 is train_resumable(), bit for bit.
+
+    What several ranks add to a session:
+      * the stop is agreed.  Signals and clocks differ between ranks, and a rank that left the loop alone would leave the others
+        waiting in the next step's all-reduce.  After EVERY step every rank takes part in one vote (kb.dist.StopVote: a MAX
+        all-reduce of one integer on a CPU tensor over gloo -- a gloo group beside an RCCL default group); the session ends after
+        step s on every rank if any rank's Budget wished so during step s.  The vote is host-side: no step waits for the device
+        that does not in train_ranks();
+      * rank 0 alone writes the two checkpoints and train_state-<step>.pth, under temporary names moved into place, and prunes; the
+        final barrier follows the last state;
+      * rank 0 alone looks for the state (find_state); the step it found and the messages for the states it passed over are
+        broadcast, every rank loads that one file and the two checkpoints of its step.  The state is one process's: the loader's is
+        the global one (TrainingFrameLoader.state_dict with crops="global": the plans of whole global batches, of which every rank
+        takes its shard), the generators are rank 0's, set last on every rank -- the ranks draw alike, as after
+        dist.broadcast_rng_state on a fresh start;
+      * the argument record holds world and sync_batch_norm too: a continuation with another value raises KbnError naming it, on
+        every rank, before anything is written.  A continuation at another world is not built.  The process group's backend and
+        the ranks' devices are not recorded and may change, as device may; a backend that sums in another order then gives
+        other bits from there on.
+    With return_results every rank returns the same values."""
+    bound = _RANKS_SIGNATURE.bind(*arguments, **keywords)
     budget = Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals)
     session = _Session(budget, keep_states)
     with budget:
@@ -796,10 +868,10 @@ _TRAIN_SIGNATURE = _RANKS_SIGNATURE.replace(parameters=[p for p in _RANKS_SIGNAT
                                                         if p.name not in ("rank", "world", "sync_batch_norm")])
 train_ranks.__signature__ = _RANKS_SIGNATURE
 train.__signature__ = _TRAIN_SIGNATURE
-train_resumable.__signature__ = _TRAIN_SIGNATURE.replace(
-    parameters=list(_TRAIN_SIGNATURE.parameters.values()) + [
-        inspect.Parameter(name, inspect.Parameter.KEYWORD_ONLY, default=default)
-        for name, default in (("max_steps", None), ("max_seconds", None), ("stop_signals", (signal.SIGTERM,)), ("keep_states", 2))])
+_SESSION_PARAMETERS = [inspect.Parameter(name, inspect.Parameter.KEYWORD_ONLY, default=default)
+                       for name, default in (("max_steps", None), ("max_seconds", None), ("stop_signals", (signal.SIGTERM,)), ("keep_states", 2))]
+train_resumable.__signature__ = _TRAIN_SIGNATURE.replace(parameters=list(_TRAIN_SIGNATURE.parameters.values()) + _SESSION_PARAMETERS)
+train_ranks_resumable.__signature__ = _RANKS_SIGNATURE.replace(parameters=list(_RANKS_SIGNATURE.parameters.values()) + _SESSION_PARAMETERS)
 
 
 # ------------------------------------------------------------------------------------------------ one process per GPU
@@ -842,7 +914,21 @@ def launch(n_gpus, *, backend="nccl", devices=None, timeout=None, **train_argume
     1 <= n_gpus <= 16 and len(devices) == n_gpus, else KbnError before anything is started or written.  The first child to exit
     with a non-zero status, or `timeout` seconds for the whole run (None: no limit), ends the others; launch then raises KbnError
     with that rank's last lines of stderr."""
-    what = "launch"
+    world, devices, checkpoint_path, threads = _launch_checks("launch", n_gpus, backend, devices, timeout, train_arguments)
+    os.makedirs(checkpoint_path, exist_ok=True)
+    arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
+    if os.path.exists(results_path):
+        os.remove(results_path)
+    with open(arguments_path, "wb") as f:
+        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
+                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed())}, f)
+    _run_children("launch", _child_command(arguments_path), devices, checkpoint_path, threads, timeout)
+    return _launch_results("launch", results_path)
+
+
+def _launch_checks(what, n_gpus, backend, devices, timeout, train_arguments):
+    """What launch() and launch_resumable() refuse before anything is started or written -> (world, devices, checkpoint_path, the
+    children's host threads)."""
     if isinstance(n_gpus, bool) or not isinstance(n_gpus, (int, np.integer)) or not 1 <= int(n_gpus) <= MAX_RANKS:
         raise KbnError(f"{what}: n_gpus {n_gpus!r}: 1 to {MAX_RANKS} ranks")
     world = int(n_gpus)
@@ -857,39 +943,59 @@ def launch(n_gpus, *, backend="nccl", devices=None, timeout=None, **train_argume
         raise KbnError(f"{what}: devices {devices}: RCCL needs a device a rank (ranks share one under backend='gloo')")
     for name in ("rank", "world", "return_results"):
         if name in train_arguments:
-            raise KbnError(f"{what}: {name} is set by launch itself")
+            raise KbnError(f"{what}: {name} is set by {what} itself")
     if timeout is not None and not float(timeout) > 0:
         raise KbnError(f"{what}: timeout {timeout!r}")
     checkpoint_path = train_arguments.get("checkpoint_path", "trained_kbnet")
     threads = train_arguments.get("workers")
     threads = max(1, int(train_arguments.get("n_thread", 8) if threads is None else threads))
+    return world, devices, checkpoint_path, threads
 
-    os.makedirs(checkpoint_path, exist_ok=True)
-    arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
-    if os.path.exists(results_path):
-        os.remove(results_path)
-    with open(arguments_path, "wb") as f:
-        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
-                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed())}, f)
 
+def _child_command(arguments_path: str, stop_signals=()) -> list:
+    """The command line of a rank: a fresh interpreter that imports this package from where it lies and runs _rank_main.  A child
+    of launch_resumable() first gives every stop signal a handler that only notes it: one that arrives while the package is still
+    being imported must not end the rank (_rank_main hands what was noted to the session's Budget)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    program = ("import sys; sys.path.insert(0, sys.argv[1]); import kbnet_amd; kbnet_amd.training._rank_main(sys.argv[2])")
-    command = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", program, root, arguments_path]
+    early = ""
+    if stop_signals:
+        early = (f"import signal; early = []; [signal.signal(number, lambda number, frame: early.append(number)) "
+                 f"for number in {[int(number) for number in stop_signals]!r}]; ")
+    program = ("import sys; " + early + "sys.path.insert(0, sys.argv[1]); import kbnet_amd; kbnet_amd.training._rank_main(sys.argv[2]"
+               + (", early" if stop_signals else "") + ")")
+    return [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", program, root, arguments_path]
+
+
+def _run_children(what, command, devices, checkpoint_path, threads, timeout, session_mark=None, arrivals=None) -> None:
+    """Starts `command` once a rank, waits for all of them, and raises KbnError for the first that exits with a non-zero status or
+    when `timeout` seconds have passed; no child outlives the call.  session_mark: the rank<r>.out / .err files are opened for
+    appending and begin with that line (launch_resumable); None: they are written anew.  arrivals: a list a signal handler of the
+    caller appends signal numbers to; each is sent on, once, to every child still running."""
+    world = len(devices)
     port = _free_port()
-    children, logs = [], []
+    children, logs, forwarded = [], [], 0
     try:
         for rank in range(world):
             env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(devices[rank]), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                        MASTER_PORT=str(port))
             env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL between processes needs it (as bench.py sets it)
             env.setdefault("OMP_NUM_THREADS", str(threads))
-            out = open(os.path.join(checkpoint_path, f"rank{rank}.out"), "w")
-            err = open(os.path.join(checkpoint_path, f"rank{rank}.err"), "w")
+            out = open(os.path.join(checkpoint_path, f"rank{rank}.out"), "w" if session_mark is None else "a")
+            err = open(os.path.join(checkpoint_path, f"rank{rank}.err"), "w" if session_mark is None else "a")
             logs += [out, err]
+            if session_mark is not None:
+                for f in (out, err):
+                    f.write(session_mark + "\n")
+                    f.flush()
             children.append(subprocess.Popen(command, stdin=subprocess.DEVNULL, stdout=out, stderr=err, env=env))
         deadline = None if timeout is None else time.monotonic() + float(timeout)
         failed = None      # (rank, why)
         while failed is None and any(c.poll() is None for c in children):
+            while arrivals is not None and forwarded < len(arrivals):
+                for child in children:
+                    if child.poll() is None:
+                        child.send_signal(arrivals[forwarded])
+                forwarded += 1
             for rank, child in enumerate(children):
                 if child.poll() is not None and child.returncode != 0:
                     failed = (rank, f"exited with status {child.returncode}")
@@ -913,17 +1019,101 @@ def launch(n_gpus, *, backend="nccl", devices=None, timeout=None, **train_argume
         rank, why = failed
         raise KbnError(f"{what}: rank {rank} of {world} {why}; the end of {os.path.join(checkpoint_path, f'rank{rank}.err')}:\n"
                        + _tail(os.path.join(checkpoint_path, f"rank{rank}.err")))
+
+
+def _launch_results(what, results_path):
     if not os.path.exists(results_path):
         raise KbnError(f"{what}: every rank exited with status 0, but rank 0 left no {results_path}")
     with open(results_path, "rb") as f:
         return pickle.load(f)
 
 
-def _rank_main(arguments_path: str) -> None:
+class _Arrivals(Budget):
+    """Budget's handlers -- installed on the main thread only, the previous ones back on every way out -- noting every signal that
+    arrives, in order, for launch_resumable() to send on."""
+
+    def __init__(self, stop_signals):
+        super().__init__(stop_signals=stop_signals)
+        self.arrived = []
+
+    def _flag(self, number, frame):
+        self.arrived.append(number)
+
+
+def launch_resumable(n_gpus, *, backend="nccl", devices=None, timeout=None, max_steps=None, max_seconds=None,
+                     stop_signals=(signal.SIGTERM,), keep_states=2, **train_arguments):
+    """launch() with children that run train_ranks_resumable(): launch()'s arguments and train_resumable()'s four, and everything
+    the three docstrings say.  The same call, made in one job slot after another -- `timeout -k 10 <slot> python job.py` is the
+    intended use -- carries a run on `n_gpus` GPUs to its end ("Training in job slots").
+
+    Before anything is started the launcher itself looks for the run's newest complete state (find_state: host code, no GPU).  A
+    state whose arguments are not this call's -- world and sync_batch_norm among them -- raises KbnError naming the first, and
+    nothing is written.  A state of the run's last step (n_train_steps(..., world=n_gpus)): the run is finished, the call returns
+    the stored results at once, starts no child and writes nothing.
+
+    While it waits the launcher holds handlers for stop_signals that only note the signal (on the main thread; the previous handlers
+    are back on every way out), and its polling loop sends each noted signal on, once, to every child still running.  The children
+    hold handlers of their own from their first line on (their session's Budget), so a scheduler that signals the whole process
+    group ends nobody either: every rank finishes its step, the ranks agree on the stop, rank 0 writes the state, and the call
+    returns that session's results with finished=False.  max_steps and max_seconds are the children's, max_seconds counted from
+    each child's start.  `timeout` keeps launch()'s meaning: it ends the children hard, and the call raises.  A child that raises
+    is ended with the others and reported, as in launch().
+
+    rank<r>.out and rank<r>.err are appended to, each session under a line that marks it; launch-results.pkl is rank 0's result of
+    the last session, rank<r>.digest every rank's replica_digest() of what it held when that session ended.  backend and devices
+    are not part of the run's record and may change between sessions, as device may; with a backend that sums in another order the
+    bits differ from there on."""
+    what = "launch_resumable"
+    world, devices, checkpoint_path, threads = _launch_checks(what, n_gpus, backend, devices, timeout, train_arguments)
+    _Session(Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals), keep_states)      # their refusals
+    stop_signals = [int(number) for number in (stop_signals or ())]
+    state, _ = find_state(checkpoint_path)
+    if state is not None:
+        bound = _RANKS_SIGNATURE.bind(**train_arguments, rank=0, world=world)
+        bound.apply_defaults()
+        given = dict(bound.arguments)
+        contents = {name: loader.read_paths(given[name]) for name in PATH_ARGUMENTS[:3]}
+        if all(given[name] is not None for name in PATH_ARGUMENTS[3:]):
+            contents.update((name, loader.read_paths(given[name])) for name in PATH_ARGUMENTS[3:])
+        check_argument_record(state["arguments"], argument_record(given, contents))
+        if state["step"] >= n_train_steps(len(contents[PATH_ARGUMENTS[0]]), given["n_batch"], given["learning_schedule"], world=world):
+            return _stored_results(state)
+
+    os.makedirs(checkpoint_path, exist_ok=True)
+    arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
+    if os.path.exists(results_path):
+        os.remove(results_path)
+    with open(arguments_path, "wb") as f:
+        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
+                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed()),
+                     "session": {"max_steps": max_steps, "max_seconds": max_seconds, "stop_signals": stop_signals,
+                                 "keep_states": keep_states}}, f)
+    mark = "==== {}: a session {} ====".format(what, "from the start" if state is None else "after step {}".format(state["step"]))
+    with _Arrivals(stop_signals) as arrivals:
+        _run_children(what, _child_command(arguments_path, stop_signals), devices, checkpoint_path, threads, timeout,
+                      session_mark=mark, arrivals=arrivals.arrived)
+    return _launch_results(what, results_path)
+
+
+def _rank_main(arguments_path: str, early=None) -> None:
     """What a child of launch() runs: the device, the caller's random state, the process group, train_ranks(), and rank 0's results into
-    a file."""
+    a file.  A child of launch_resumable() runs train_ranks_resumable()'s body instead, with the session's Budget entered here,
+    before the GPU is touched: its handlers hold from the first line on, and a signal noted before it (`early`, the command line's
+    list) is the Budget's."""
     with open(arguments_path, "rb") as f:
         arguments = pickle.load(f)
+    limits = arguments.get("session")
+    if limits is None:
+        return _rank_run(arguments, None)
+    budget = Budget(max_steps=limits["max_steps"], max_seconds=limits["max_seconds"], stop_signals=limits["stop_signals"])
+    session = _Session(budget, limits["keep_states"])
+    with budget:
+        if early:
+            budget.signalled = early[0]
+        return _rank_run(arguments, session)
+
+
+def _rank_run(arguments: dict, session) -> None:
     rank, _, world = dist.env_world()
     torch.set_num_threads(arguments["threads"])
     torch.cuda.set_device(arguments["devices"][rank])
@@ -933,7 +1123,11 @@ def _rank_main(arguments_path: str) -> None:
     np.random.set_state(numpy_state)
     if world > 1:
         dist.init(arguments["backend"])
-    results = train_ranks(**arguments["train"], rank=rank, world=world, return_results=True)
+    if session is None:
+        results = train_ranks(**arguments["train"], rank=rank, world=world, return_results=True)
+    else:
+        bound = _RANKS_SIGNATURE.bind(**arguments["train"], rank=rank, world=world, return_results=True)
+        results = _train_loop(*bound.args, **bound.kwargs, session=session)
     if world > 1:
         with open(os.path.join(os.path.dirname(arguments["results"]), f"rank{rank}.digest"), "w") as f:
             f.write(results[0]["digest"] + "\n")

@@ -22,6 +22,12 @@ different raw sizes in one batch and the reference's random crop: `draw_crop` ma
 decisions on the host, `kbn_unpack_train_frames_forward` cuts every frame's crop out of its raw bytes on the device.
 `random_crop` is the reference-named NumPy function on top of `draw_crop`.
 
+Packed frames: both loaders take, wherever they take a PNG, a file written by `encode_frame` / `pack_frames` and
+recognised by its magic.  Such a file is not decoded on the host at all: it is read straight into pinned staging, passes the
+structural check `kbn_frame_check` there, crosses PCIe packed, and `ops.unpack_packed_frames` decodes, splits, crops and converts
+on the device -- the same tensors bit for bit.  A batch is all PNG or all packed.  `frame_info`, `encode_frame`, `decode_frame`,
+`check_frame` are the host codec.
+
 The output side (`run_kbnet.py --save_outputs`, reference src/kbnet.py:986-1026): `save_depth` / `save_depth_batch` for one tensor,
 and `OutputWriter` for the whole export of a run -- `ops.export_pack` makes the pixels of a batch's files in one launch, a side
 stream copies them to pinned slots, host threads encode and write while the next batch runs (kb.inference.run drives it).
@@ -90,6 +96,129 @@ def decode_png_batch(files: Sequence[bytes], outs: Sequence[np.ndarray], threads
 def _read(path: str) -> bytes:
     with open(path, "rb") as f:
         return f.read()
+
+
+# ------------------------------------------------------------------ the packed frame store
+FRAME_MAGIC = b"KBNFRM1\0"      # a packed frame's first 8 bytes: the loaders tell it from a PNG by these, not by its name
+FRAME_HEADER_BYTES = 32
+
+
+def is_packed_frame(head: bytes) -> bool:
+    """Whether a file that begins with `head` is a packed frame."""
+    return bytes(head[:8]) == FRAME_MAGIC
+
+
+def frame_info(data: bytes) -> Tuple[int, int, int, int]:
+    """(width, height, channels, bits) of a packed frame; its first 32 bytes are enough."""
+    w, h, c, b = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(_lib.load().kbn_frame_info(bytes(data), len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(b)), "kbn_frame_info")
+    return w.value, h.value, c.value, b.value
+
+
+def check_frame(data) -> None:
+    """kbn_frame_check: raises KbnError unless `data` (bytes, or a C-contiguous uint8 array such as a slice of pinned staging) is a
+    structurally complete packed frame -- the check every file passes before its bytes may reach ops.unpack_packed_frames."""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or not data.flags["C_CONTIGUOUS"]:
+            raise KbnError("check_frame: expected a contiguous uint8 array")
+        check(_lib.load().kbn_frame_check(data.ctypes.data_as(C.c_void_p), data.nbytes), "kbn_frame_check")
+    else:
+        check(_lib.load().kbn_frame_check(bytes(data), len(data)), "kbn_frame_check")
+
+
+def encode_frame(array: np.ndarray) -> bytes:
+    """H x W or H x W x C (C = 1, 3, 4) uint8 / uint16 samples -> the bytes of a packed frame (kbn_frame_encode): lossless, and
+    decodable on the device.  ctypes drops the interpreter lock around the encoder."""
+    a = np.ascontiguousarray(array)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim not in (2, 3):
+        raise KbnError(f"encode_frame: expected an H x W (x C) uint8 or uint16 array, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    c = a.shape[2] if a.ndim == 3 else 1
+    bits = 8 * a.dtype.itemsize
+    lib = _lib.load()
+    cap = lib.kbn_frame_encode_bound(w, h, c, bits)
+    if cap == 0:
+        raise KbnError(f"encode_frame: {h} x {w} x {c} samples of {bits} bits cannot be packed (channels 1, 3 or 4, sizes >= 1)")
+    buf = getattr(_scratch, "frame", None)
+    if buf is None or len(buf) < cap:
+        buf = _scratch.frame = (C.c_ubyte * cap)()
+    n = C.c_size_t()
+    check(lib.kbn_frame_encode(a.ctypes.data_as(C.c_void_p), w, h, c, bits, buf, len(buf), C.byref(n)), "kbn_frame_encode")
+    return bytes(memoryview(buf)[:n.value])
+
+
+def decode_frame(data: bytes, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """The bytes of a packed frame -> H x W x C uint8 / uint16 (H x W for one channel), as decode_png returns a PNG's pixels:
+    the host decoder (kbn_frame_decode; it runs kbn_frame_check first)."""
+    w, h, c, b = frame_info(data[:FRAME_HEADER_BYTES])
+    dtype = np.uint16 if b == 16 else np.uint8
+    if out is None:
+        out = np.empty((h, w) if c == 1 else (h, w, c), dtype=dtype)
+    if out.nbytes < h * w * c * dtype().itemsize or not out.flags["C_CONTIGUOUS"]:
+        raise KbnError("decode_frame: output buffer too small or not contiguous")
+    check(_lib.load().kbn_frame_decode(bytes(data), len(data), out.ctypes.data_as(C.c_void_p), out.nbytes), "kbn_frame_decode")
+    return out
+
+
+def pack_frames(src_png_paths: Sequence[str], dst_paths: Sequence[str], workers: int = 8) -> Tuple[int, int]:
+    """Converts PNG files to packed frames, src_png_paths[i] -> dst_paths[i], on `workers` host threads: decoded with the library's
+    PNG reader (a palette becomes RGB), encoded with kbn_frame_encode, written under a temporary name and moved into place.
+    Returns (PNG bytes read, packed bytes written)."""
+    if len(src_png_paths) != len(dst_paths):
+        raise KbnError(f"pack_frames: {len(src_png_paths)} sources, {len(dst_paths)} destinations")
+
+    def one(pair):
+        src, dst = pair
+        png = _read(src)
+        data = encode_frame(decode_png(png))
+        os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+        tmp = f"{dst}.tmp{os.getpid()}.{threading.get_ident()}"
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, dst)
+        return len(png), len(data)
+
+    with ThreadPoolExecutor(max_workers=max(1, int(workers))) as ex:
+        sizes = list(ex.map(one, zip(src_png_paths, dst_paths)))
+    return sum(s[0] for s in sizes), sum(s[1] for s in sizes)
+
+
+def _image_info(head: bytes) -> Tuple[int, int, int, int]:
+    """png_info or frame_info of a file's first 33 bytes, by its magic."""
+    return frame_info(head[:FRAME_HEADER_BYTES]) if is_packed_frame(head) else png_info(head)
+
+
+def _read_packed_into(pool, jobs: Sequence[tuple]) -> None:
+    """jobs: (path, pinned flat uint8 numpy view, offset, size, (width, height, channels, bits) the batch was planned with).  Each
+    file is read straight into view[offset:offset + size] on the pool's threads, and kbn_frame_check runs on the bytes where they
+    lie: no file's bytes are copied to the device before it has passed."""
+    def one(job):
+        path, flat, at, size, want = job
+        dst = flat[at:at + size]
+        view, got = memoryview(dst), 0
+        with open(path, "rb", buffering=0) as f:
+            while got < size:
+                step = f.readinto(view[got:])
+                if not step:
+                    break
+                got += step
+            more = f.read(1)
+        if got != size or more:
+            raise KbnError(f"{path} changed size while it was read")
+        check_frame(dst)
+        if frame_info(dst[:FRAME_HEADER_BYTES].tobytes()) != tuple(want):
+            raise KbnError(f"{path} is not the {want[1]} x {want[0]} x {want[2]} frame of {want[3]} bits its batch was planned with")
+
+    list(pool.map(one, jobs))
+
+
+def _one_kind(paths: Sequence[str], flags: Sequence[bool], what: str) -> bool:
+    """Whether a batch's files are packed frames (all of them) or PNGs (all of them); a mixed batch raises, naming two paths."""
+    for path, flag in zip(paths, flags):
+        if flag != flags[0]:
+            kind = {True: "a packed frame", False: "a PNG"}
+            raise KbnError(f"{what}: a batch must be all PNG or all packed: {paths[0]} is {kind[flags[0]]}, {path} is {kind[flag]}")
+    return bool(flags[0])
 
 
 # ---------------------------------------------- the reference's loader functions (numpy)
@@ -438,9 +567,70 @@ class InferenceFrameLoader:
         self.prefetch = max(1, int(prefetch))
         self._driver = ThreadPoolExecutor(max_workers=self.prefetch)
         self._stage: List[Optional[dict]] = [None] * (self.prefetch + 1)
+        self._stage_packed: List[Optional[dict]] = [None] * (self.prefetch + 1)
+        self._kind: dict = {}                                    # path -> whether it is a packed frame (its first bytes, read once)
 
     def __len__(self):
         return (self.n_sample + self.batch_size - 1) // self.batch_size
+
+    def _packed(self, path: str) -> bool:
+        if path not in self._kind:
+            with open(path, "rb") as f:
+                self._kind[path] = is_packed_frame(f.read(8))
+        return self._kind[path]
+
+    def _submit_packed(self, b: int, idx, paths):
+        """_submit for a batch of packed frames: the files go as they are into pinned staging, each at a 16-byte-aligned
+        offset, pass kbn_frame_check there, cross PCIe packed, and ONE ops.unpack_packed_frames launch decodes the middle thirds."""
+        if not self.use_image_triplet:
+            raise KbnError("InferenceFrameLoader: packed images are decoded as triplets; use PNG files with use_image_triplet=False")
+        nb = len(idx)
+        heads = []
+        for path in paths:
+            with open(path, "rb") as f:
+                heads.append(frame_info(f.read(FRAME_HEADER_BYTES)))
+        wraw, hraw, c, bits = heads[0]
+        wd, hd, cd, dbits = heads[nb]
+        if bits != 8 or cd != 1:
+            raise KbnError("InferenceFrameLoader: expected 8-bit images and single-channel depth maps")
+        if wraw % 3:
+            raise ValueError("array split does not result in an equal division")     # np.split in the reference's load_image_triplet
+        width = wraw // 3
+        if (hd, wd) != (hraw, width):
+            raise KbnError(f"depth map is {hd} x {wd}, image is {hraw} x {width}")
+        if any(h != heads[0] for h in heads[:nb]) or any(h != heads[nb] for h in heads[nb:]):
+            raise KbnError("InferenceFrameLoader: all frames of a run must have one size and format")
+        sizes = [os.path.getsize(path) for path in paths]
+        at, total = [], [0, 0]
+        for j, size in enumerate(sizes):
+            which = 0 if j < nb else 1
+            at.append(total[which])
+            total[which] = _align16(total[which] + size)
+        slot = b % (self.prefetch + 1)
+        st = self._stage_packed[slot]
+        if st is None:
+            st = self._stage_packed[slot] = {"image": None, "depth": None, "k": torch.empty((self.batch_size, 3, 3), dtype=torch.float32).pin_memory(),
+                                             "done": None}
+        if st["done"] is not None:
+            st["done"].synchronize()      # the copies that last used this staging set
+        for name, need in (("image", total[0]), ("depth", total[1])):
+            if st[name] is None or st[name].numel() < need:
+                st[name] = torch.empty(need + need // 8, dtype=torch.uint8).pin_memory()
+        k_np = st["k"].numpy()
+        for j in range(nb):
+            k_np[j] = np.load(self.intrinsics_paths[idx[j]]).astype(np.float32)
+        views = (st["image"].numpy(), st["depth"].numpy())
+        _read_packed_into(self.pool, [(paths[j], views[0 if j < nb else 1], at[j], sizes[j], heads[j]) for j in range(2 * nb)])
+        frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, width, 0, 0) for j in range(nb)]
+        with torch.cuda.stream(self.copy_stream):
+            img_d = st["image"][:total[0]].to(self.device, non_blocking=True)
+            dep_d = st["depth"][:total[1]].to(self.device, non_blocking=True)
+            k_d = st["k"][:nb].to(self.device, non_blocking=True)
+            image, depth = ops.unpack_packed_frames(img_d, dep_d, frames, (hraw, width), channels=c, depth_bits=dbits, middle_only=True)
+            done = torch.cuda.Event()
+            done.record(self.copy_stream)
+        st["done"] = done
+        return image, depth, k_d, done
 
     # -- one batch: decode on the pool into pinned memory, async H2D + unpack on the copy stream --
     def _staging(self, slot: int, hraw: int, wraw: int, c: int, hd: int, wd: int, depth_dtype):
@@ -458,7 +648,10 @@ class InferenceFrameLoader:
     def _submit(self, b: int):
         lo, hi = b * self.batch_size, min((b + 1) * self.batch_size, self.n_sample)
         idx = list(range(lo, hi))
-        files = list(self.pool.map(_read, [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]))
+        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
+        if _one_kind(paths, [self._packed(path) for path in paths], "InferenceFrameLoader"):
+            return self._submit_packed(b, idx, paths)
+        files = list(self.pool.map(_read, paths))
         img_files, dep_files = files[:len(idx)], files[len(idx):]
         wraw, hraw, c, bits = png_info(img_files[0])
         wd, hd, cd, dbits = png_info(dep_files[0])
@@ -595,12 +788,15 @@ class TrainingFrameLoader:
     `torch.utils.data.RandomSampler(range(n), generator=generator)` yields.  The crops are drawn with `draw_crop` from np.random
     on the ITERATING thread, batch by batch in epoch order and sample by sample inside a batch, just before the batch goes to the
     pool: they do not depend on the pool's timing, and under np.random.seed(s) with shuffle=False the batches are the reference
-    dataset's samples in index order.  Raw sizes come from the PNG headers (the first 33 bytes of a file, read once).
+    dataset's samples in index order.  Raw sizes come from the files' headers (the first 33 bytes of a PNG, the first 32 of a packed
+    frame, read once).
 
     The pipeline is InferenceFrameLoader's: files are read by a thread pool, decoded by the library (`decode_png_batch`) straight
     into PINNED staging -- frames may differ in size, so each sits at its own 16-byte-aligned offset of a flat buffer -- the used
     prefix of each buffer crosses PCIe as raw bytes in one asynchronous copy on a side stream, and `ops.unpack_train_frames`
-    splits, crops and converts there.  `prefetch` batches are in flight.  Without a crop (`shape` None or not positive) the frames of
+    splits, crops and converts there.  A batch of packed frames (module docstring; all of a batch's files or none) skips the decode: the
+    files themselves go to pinned staging, pass `kbn_frame_check` there, and `ops.unpack_packed_frames` decodes them on the device.
+    `prefetch` batches are in flight.  Without a crop (`shape` None or not positive) the frames of
     a batch must have one size.  An error found while a batch is prepared is raised when that batch is due.  One epoch at a time:
     `iter()` first waits for what an epoch that was left early still has in flight.
 
@@ -657,6 +853,7 @@ class TrainingFrameLoader:
         self._driver = ThreadPoolExecutor(max_workers=min(16, self.prefetch))
         self._stage: List[Optional[dict]] = [None] * (self.prefetch + 1)
         self._headers: List[Optional[tuple]] = [None] * self.n_sample
+        self._packed: List[Optional[tuple]] = [None] * self.n_sample   # beside each header: whether the image / the depth file is a packed frame
         self._pending: list = []
         self._serial = 0                                         # batches submitted so far: picks the staging set
         self._order: Optional[list] = None                       # the running epoch's order, the batch iter() hands out next and the
@@ -680,10 +877,13 @@ class TrainingFrameLoader:
     # -- on the iterating thread: the batch's raw sizes, its checks and its crops --
     def _header(self, i: int):
         if self._headers[i] is None:
-            heads = []
+            heads, packed = [], []
             for path in (self.image_paths[i], self.sparse_depth_paths[i]):
                 with open(path, "rb") as f:
-                    heads.append(png_info(f.read(33)))           # signature + IHDR
+                    head = f.read(33)                            # a PNG's signature + IHDR; a packed frame's header is its first 32
+                heads.append(_image_info(head))
+                packed.append(is_packed_frame(head))
+            self._packed[i] = tuple(packed)
             self._headers[i] = tuple(heads)
         return self._headers[i]
 
@@ -734,7 +934,12 @@ class TrainingFrameLoader:
     def _submit(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool):
         nb = len(plan)
         idx = [p[0] for p in plan]
-        files = list(self.pool.map(_read, [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]))
+        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
+        for i in idx:
+            self._header(i)      # read already unless the plan comes from load_state_dict
+        if _one_kind(paths, [self._packed[i][0] for i in idx] + [self._packed[i][1] for i in idx], "TrainingFrameLoader"):
+            return self._submit_packed(slot, plan, shape, c, dbits, cropped, paths)
+        files = list(self.pool.map(_read, paths))
         img_files, dep_files = files[:nb], files[nb:]
         frames, img_at, dep_at = [], 0, 0
         for j, (i, hraw, w, y, x) in enumerate(plan):
@@ -756,6 +961,36 @@ class TrainingFrameLoader:
             dep_d = st["depth"][:dep_at].to(self.device, non_blocking=True)
             k_d = st["k"][:nb].to(self.device, non_blocking=True)
             batch = ops.unpack_train_frames(img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,)
+            done = torch.cuda.Event()
+            done.record(self.copy_stream)
+        st["done"] = done
+        return batch, done
+
+    def _submit_packed(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool, paths):
+        """_submit for a batch of packed frames: nothing is decoded on the host.  Every file is read straight into its
+        16-byte-aligned place of the pinned staging buffer and passes kbn_frame_check there; the packed bytes cross PCIe in one
+        asynchronous copy per buffer, and ONE ops.unpack_packed_frames launch decodes, splits, crops and converts."""
+        nb = len(plan)
+        sizes = [os.path.getsize(path) for path in paths]
+        at, total = [], [0, 0]
+        for j, size in enumerate(sizes):
+            which = 0 if j < nb else 1
+            at.append(total[which])
+            total[which] = _align16(total[which] + size)
+        st = self._staging(slot, total[0], total[1], max(nb, self.batch_size))
+        k_np = st["k"].numpy()
+        for j, (i, hraw, w, y, x) in enumerate(plan):
+            k = np.load(self.intrinsics_paths[i]).astype(np.float32)
+            k_np[j] = (_crop_intrinsics(k, y, x) if cropped else k).astype(np.float32)
+        views = (st["image"].numpy(), st["depth"].numpy())
+        want = [(3 * w, hraw, c, 8) for _, hraw, w, _, _ in plan] + [(w, hraw, 1, dbits) for _, hraw, w, _, _ in plan]
+        _read_packed_into(self.pool, [(paths[j], views[0 if j < nb else 1], at[j], sizes[j], want[j]) for j in range(2 * nb)])
+        frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, w, y, x) for j, (_, hraw, w, y, x) in enumerate(plan)]
+        with torch.cuda.stream(self.copy_stream):
+            img_d = st["image"][:total[0]].to(self.device, non_blocking=True)
+            dep_d = st["depth"][:total[1]].to(self.device, non_blocking=True)
+            k_d = st["k"][:nb].to(self.device, non_blocking=True)
+            batch = ops.unpack_packed_frames(img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,)
             done = torch.cuda.Event()
             done.record(self.copy_stream)
         st["done"] = done

@@ -1398,6 +1398,75 @@ def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, 
     return image0, image1, image2, depth
 
 
+_PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
+
+
+def unpack_packed_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16, middle_only: bool = False):
+    """unpack_train_frames from PACKED files (kb.loader.encode_frame): the same four tensors, bit for bit, decoded on the
+    device from the files' bytes (kbn_unpack_packed_frames_forward, csrc/unpack_packed.hip: one launch per
+    _lib.KBN_UNPACK_TRAIN_MAX_FRAMES frames).
+
+    images_u8 / depths_u8: 1-d uint8 device buffers, 16-byte aligned, that hold the files as they are on disk.  frames: one
+    (image_offset, image_bytes, depth_offset, depth_bytes, H, W, y_start, x_start) a frame -- where its packed H x 3 W x channels
+    triplet and its packed H x W depth map lie (offsets multiples of 16) and where its crop starts inside each third.  Every file
+    must have passed kbn_frame_check (kb.loader.check_frame) on the host before its bytes were copied: that check is what keeps the
+    kernel inside the files.  middle_only: returns (image0, sparse_depth0) and decodes only the middle third.  A raw width 3 W
+    above _lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH raises KbnError (the kernel's LDS budget).  No CPU fallback."""
+    fn = "unpack_packed_frames"
+    h, w = (int(v) for v in shape)
+    channels, depth_bits = int(channels), int(depth_bits)
+    if h < 1 or w < 1:
+        raise KbnError(f"{fn}: the crop shape must be positive, got {h} x {w}")
+    if channels not in (1, 3, 4):
+        raise KbnError(f"{fn}: image channels must be 1, 3 or 4, got {channels}")
+    if depth_bits not in (8, 16):
+        raise KbnError(f"{fn}: depth samples must have 8 or 16 bits, got {depth_bits}")
+    frames = [tuple(int(v) for v in f) for f in frames]
+    n = len(frames)
+    if n < 1:
+        raise KbnError(f"{fn}: no frames")
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise KbnError(f"{fn}: {name}: expected a dense 1-d uint8 tensor")
+    records = bytearray(_PACKED_FRAME_RECORD.size * n)
+    for i, f in enumerate(frames):
+        if len(f) != 8:
+            raise KbnError(f"{fn}: frame {i}: expected (image_offset, image_bytes, depth_offset, depth_bytes, H, W, y_start, x_start), got {f}")
+        io, ib, do, db, H, W, y, x = f
+        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
+            raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
+        if 3 * W > _lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH:
+            raise KbnError(f"{fn}: frame {i}: a packed triplet of {3 * W} columns is wider than the kernel takes ({_lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH})")
+        if y < 0 or y + h > H or x < 0 or x + w > W:
+            raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
+        for what, at, size, buf in (("triplet", io, ib, images_u8), ("depth map", do, db, depths_u8)):
+            if at < 0 or at % 16 or size < 1 or size > 0xffffffff or at + size > buf.numel():
+                raise KbnError(f"{fn}: frame {i}: its packed {what} of {size} bytes at byte {at} is misaligned or leaves its buffer of {buf.numel()} bytes")
+        _PACKED_FRAME_RECORD.pack_into(records, i * _PACKED_FRAME_RECORD.size, io, do, ib, db, H, 3 * W, y, x)
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not t.is_cuda:
+            raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+        if t.data_ptr() % 16:
+            raise KbnError(f"{fn}: {name}: the buffer must be 16-byte aligned")
+    device = images_u8.device
+    if depths_u8.device != device:
+        raise KbnError(f"{fn}: tensors live on different devices ({device} and {depths_u8.device})")
+    image0 = torch.empty((n, 3, h, w), device=device, dtype=torch.float32)
+    image1, image2 = (None, None) if middle_only else (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(2))
+    depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
+    lib = _lib.load()
+    table = (_lib.PackedFrame * n).from_buffer(records)
+    packed_bytes = float(sum(f[1] + f[3] for f in frames))
+    with torch.cuda.device(device):
+        check(_launch("unpack_packed_frames", 0.0,
+                      lambda: lib.kbn_unpack_packed_frames_forward(images_u8.data_ptr(), images_u8.numel(), depths_u8.data_ptr(), depths_u8.numel(),
+                                                                   table, n, h, w, channels, depth_bits, image0.data_ptr(),
+                                                                   None if middle_only else image1.data_ptr(),
+                                                                   None if middle_only else image2.data_ptr(), depth.data_ptr(), _stream()),
+                      nbytes=packed_bytes + float(n * h * w) * (16 if middle_only else 40)), "kbn_unpack_packed_frames_forward")
+    return (image0, depth) if middle_only else (image0, image1, image2, depth)
+
+
 @_on_tensor_device
 def eval_metrics(output_depth, ground_truth, ground_truth_validity, min_evaluate_depth: float,
                  max_evaluate_depth: float):

@@ -1085,6 +1085,54 @@ int kbn_unpack_train_frames_forward(const unsigned char* images, size_t image_by
                                     const kbn_train_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
                                     float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
 
+/* The packed frame store: a lossless container the loaders read in place of PNG files, decoded on the DEVICE.  One file
+ * holds height x width x channels samples (channels 1, 3 or 4; 8 or 16 bits), stored per plane in groups of 8 rows and segments of
+ * 16 samples, every segment with a bit width of its own (version 1; the layout is written down in DESIGN 8t and csrc/frame_pack.h).
+ * HOST functions, thread-safe, no GPU work:
+ *   kbn_frame_info          reads the 32-byte header (file_bytes >= 32 is enough)
+ *   kbn_frame_encode_bound  the capacity kbn_frame_encode needs for these sizes; 0 for sizes it refuses
+ *   kbn_frame_encode        samples: height x width x channels interleaved, uint8 or (bits 16) uint16 in host byte order -> the file
+ *                           image in `out`, *out_bytes its size; KBN_ERR_WORKSPACE when out_capacity < the bound
+ *   kbn_frame_decode        the inverse, after kbn_frame_check; samples_bytes >= height x width x channels x bits / 8
+ *   kbn_frame_check         the complete structural check: magic and version constants, sizes, payload_bytes against file_bytes,
+ *                           zero padding, a table that starts at 0, is monotone and ends at payload_bytes, every header byte <= bits,
+ *                           every (group, plane) payload exactly its header bytes plus the bytes of its segments.  EVERY file
+ *                           passes it before its bytes reach kbn_unpack_packed_frames_forward.
+ * KBN_ERR_INVALID_ARGUMENT: NULL pointers, sizes < 1, a damaged or truncated file, a short output; KBN_ERR_UNSUPPORTED: other
+ * channels / bits / version constants, an image whose encoding could pass 4 GiB (the table's offsets are 32-bit). */
+int kbn_frame_info(const unsigned char* file, size_t file_bytes, int* width, int* height, int* channels, int* bits);
+size_t kbn_frame_encode_bound(int width, int height, int channels, int bits);
+int kbn_frame_encode(const void* samples, int width, int height, int channels, int bits, unsigned char* out, size_t out_capacity,
+                     size_t* out_bytes);
+int kbn_frame_decode(const unsigned char* file, size_t file_bytes, void* samples, size_t samples_bytes);
+int kbn_frame_check(const unsigned char* file, size_t file_bytes);
+
+/* kbn_unpack_train_frames_forward from PACKED files: `images` and `depths` are device buffers that hold the packed files of the
+ * batch's triplets (image_channels planes of 8 bits, raw_width_i = 3 x W_i wide) and depth maps (one plane of depth_bits, W_i wide)
+ * as they are on disk, each at a 16-byte-aligned offset; both buffers are 16-byte aligned.  Outputs, crop and records as there, the
+ * record also carrying the two files' sizes.  image1 and image2 may be NULL: then only the middle third is decoded (inference).
+ * One launch per KBN_UNPACK_TRAIN_MAX_FRAMES frames, one workgroup per (frame, group of 8 rows that the crop touches, plane); integer
+ * work, no atomics, the same bits on every run, and the bits kbn_unpack_train_frames_forward gives for the decoded samples.
+ * The files must have passed kbn_frame_check on the host.  The kernel never reads outside a file: it compares header, table and
+ * header bytes with the record and with each other first, and leaves the outputs of a (frame, group, plane) that disagrees unwritten.
+ * Checked for every record before anything is launched -- KBN_ERR_INVALID_ARGUMENT: a NULL pointer other than image1 / image2,
+ * misaligned buffers, n < 1, height or width < 1, a raw width that is not 3 x W, a crop that leaves its frame, a negative or
+ * misaligned offset, a file too short for its header and table or not inside its buffer; KBN_ERR_UNSUPPORTED: other image_channels /
+ * depth_bits, a raw width above KBN_UNPACK_PACKED_MAX_RAW_WIDTH (a group's segment offsets, 4 bytes each, live in LDS: 32 KB there). */
+#define KBN_UNPACK_PACKED_MAX_RAW_WIDTH 16384
+typedef struct kbn_packed_frame {
+    long long image_offset;   /* bytes, into `images`; a multiple of 16 */
+    long long depth_offset;   /* bytes, into `depths`; a multiple of 16 */
+    unsigned int image_bytes; /* the packed triplet's file size */
+    unsigned int depth_bytes; /* the packed depth map's file size */
+    int height;               /* raw rows of the triplet and of the depth map */
+    int raw_width;            /* raw columns of the triplet: 3 x W */
+    int y_start, x_start;     /* the crop's first row and its first column inside each third */
+} kbn_packed_frame;
+int kbn_unpack_packed_frames_forward(const unsigned char* images, size_t image_bytes, const unsigned char* depths, size_t depth_bytes,
+                                     const kbn_packed_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
+                                     float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
+
 /* TensorBoard's default histogram of an fp32 device tensor -- what SummaryWriter.add_histogram(bins='tensorflow') computes on the
  * host, np.histogram(values.astype(float), bins=edges) with min, max, sum and values.dot(values) -- in one pass (csrc/histogram.hip).
  *   x               n float32, dense, 4-byte aligned (16-byte loads from the first 16-byte boundary on)

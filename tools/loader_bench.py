@@ -2,8 +2,10 @@
 """Throughput of the input pipeline (row f4) on the GPU box: KITTI-shaped PNG files (352 x 3648 RGB image
 triplets, 352 x 1216 16-bit sparse depth) -> InferenceFrameLoader -> preprocess -> graph-replayed forward.
 Prints decode-only, loader-only (decode + H2D + unpack) and end-to-end frames/s, next to the PIL loop the
-reference runs (one worker, one sample at a time).   usage: loader_bench.py [n_files] [workers] [prefetch]"""
-import os, sys, time, tempfile
+reference runs (one worker, one sample at a time).   usage: loader_bench.py [n_files] [workers] [prefetch] [--packed]
+--packed: the files are also converted to packed frames (kb.loader.pack_frames; both total sizes are printed) and every
+loader figure is taken for both forms in this one run, as the median (min, max) of five one-epoch windows."""
+import os, sys, time, tempfile, statistics
 import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +13,8 @@ sys.path.insert(0, ROOT)
 import kbnet_amd as kb
 from PIL import Image
 
+PACKED = "--packed" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--packed"]
 n_files = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 workers = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 prefetch = int(sys.argv[3]) if len(sys.argv) > 3 else 4
@@ -28,6 +32,12 @@ for i in range(n_files):   # smooth scene + sensor noise: compresses like a phot
     p = os.path.join(d, f"k{i}.npy"); np.save(p, np.array([[721.5, 0, 609.6], [0, 721.5, 172.9], [0, 0, 1]])); ks.append(p)
 mb = sum(os.path.getsize(p) for p in imgs + deps) / 1e6
 print(f"{n_files} samples, {mb / n_files:.2f} MB of PNG per sample, {workers} loader threads, {os.cpu_count()} host cores")
+if PACKED:
+    packed_imgs, packed_deps = [p[:-4] + ".kbf" for p in imgs], [p[:-4] + ".kbf" for p in deps]
+    png_bytes, packed_bytes = kb.loader.pack_frames(imgs + deps, packed_imgs + packed_deps, workers=8)
+    raw_bytes = n_files * H * W * (9 + 2)
+    print(f"SYNTHETIC files (no real KITTI frame has been measured): PNG {png_bytes / 1e6:.1f} MB, packed {packed_bytes / 1e6:.1f} MB, raw {raw_bytes / 1e6:.1f} MB; "
+          f"packed / PNG = {packed_bytes / png_bytes:.3f}, packed / raw = {packed_bytes / raw_bytes:.3f}")
 
 dev = torch.device("cuda:0")
 t0 = time.perf_counter()
@@ -40,11 +50,20 @@ for i in range(min(n_files, 16)):   # the reference's loop: PIL, one sample at a
 torch.cuda.synchronize()
 print(f"reference-style PIL loop, 1 worker : {min(n_files, 16) / (time.perf_counter() - t0):8.1f} frames/s")
 
-def run_loader(consume):
+def run_loader(consume, imgs=imgs, deps=deps, windows=None):
     loader = kb.loader.InferenceFrameLoader(imgs, deps, ks, use_image_triplet=True, batch_size=8, device=dev, workers=workers, prefetch=prefetch)
     for batch in loader:   # warm (pinned buffers, page cache)
         consume(*batch)
     torch.cuda.synchronize()
+    if windows:      # one epoch a window
+        rates = []
+        for _ in range(windows):
+            t = time.perf_counter()
+            for batch in loader:
+                consume(*batch)
+            torch.cuda.synchronize()
+            rates.append(n_files / (time.perf_counter() - t))
+        return f"{statistics.median(rates):8.1f} (min {min(rates):.1f}, max {max(rates):.1f})"
     t = time.perf_counter()
     for _ in range(3):
         for batch in loader:
@@ -65,3 +84,7 @@ def step(image, sparse, k):
     else:
         model.forward(img, filt, valid, k)
 print(f"files -> depth maps, end to end    : {run_loader(step):8.1f} frames/s")
+if PACKED:
+    for name, consume in (("loader (read/decode + H2D + unpack)", lambda *b: None), ("files -> depth maps, end to end   ", step)):
+        print(f"{name} PNG    : {run_loader(consume, windows=5)} frames/s")
+        print(f"{name} packed : {run_loader(consume, packed_imgs, packed_deps, windows=5)} frames/s")

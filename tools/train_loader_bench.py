@@ -20,6 +20,12 @@ reports, for batches of 8 cropped to 320 x 768 with the KITTI script's crop type
    3 C + 2 read, 40 written.  The two results are compared bit for bit first.
 3. Bytes that cross PCIe per batch for both loaders, from the shapes.
 
+With --packed the files are first converted to packed frames (kb.loader.pack_frames, DESIGN 8t) and both total sizes are printed;
+the run then compares, in this one process and on this one GPU, TrainingFrameLoader over the packed files with the same loader
+over the PNG files at 2 and at 8 workers (part 1, the reference-style DataLoader is left out), kbn_unpack_packed_frames_forward
+with kbn_unpack_train_frames_forward on the same batch (part 2, results compared bit for bit first), and the host time of
+kbn_frame_check with the inflate it stands in for (one thread, per triplet with its depth map).  The files are synthetic.
+
 One GPU process; nothing is retried."""
 import argparse
 import os
@@ -76,6 +82,10 @@ class ReferenceStyleDataset(torch.utils.data.Dataset):
         k = np.load(self.ks[i]).astype(np.float32)
         [image0, image1, image2, z], k = kb.loader.random_crop([image0, image1, image2, z], self.shape, intrinsics=k, crop_type=self.crop_type)
         return [T.astype(np.float32) for T in (image0, image1, image2, z, k)]
+
+
+class _Done(Exception):
+    """--packed has written its lines: the default parts are not run."""
 
 
 def epochs(run_epoch, count):
@@ -166,9 +176,144 @@ def kernel_part(dev, images, depths, quick):
             f"   torch / kernel = {statistics.median(t_torch) / statistics.median(t_ours):.1f} x"], frames
 
 
+def packed_kernel_part(dev, images, depths, packed_images, packed_depths, frames, quick):
+    """The packed decoder on one batch's files against the raw-byte kernel on the same batch's decoded bytes: same crops, same
+    event windows, the same rotation through output sets."""
+    lib = kb._lib.load()
+    h, w = SHAPE
+    raw = [kb.loader.decode_png(open(p, "rb").read()) for p in images[:BATCH] + depths[:BATCH]]
+    img_host, dep_host = np.zeros(frames[-1][0] + raw[BATCH - 1].nbytes, np.uint8), np.zeros(frames[-1][1] + raw[-1].nbytes, np.uint8)
+    for f, im, z in zip(frames, raw[:BATCH], raw[BATCH:]):
+        img_host[f[0]:f[0] + im.nbytes] = im.reshape(-1)
+        dep_host[f[1]:f[1] + z.nbytes] = z.reshape(-1).view(np.uint8)
+    files = [open(p, "rb").read() for p in packed_images[:BATCH] + packed_depths[:BATCH]]
+    for data in files:
+        kb.loader.check_frame(data)
+    at, total = [], [0, 0]
+    for j, data in enumerate(files):
+        which = 0 if j < BATCH else 1
+        at.append(total[which])
+        total[which] = (total[which] + len(data) + 15) & ~15
+    hosts = [np.zeros(total[0], np.uint8), np.zeros(total[1], np.uint8)]
+    for j, data in enumerate(files):
+        hosts[0 if j < BATCH else 1][at[j]:at[j] + len(data)] = np.frombuffer(data, np.uint8)
+    n_in, n_out = (2, 2) if quick else (4, 8)
+    raw_ins = [(torch.from_numpy(img_host).to(dev), torch.from_numpy(dep_host).to(dev)) for _ in range(n_in)]
+    ins = [(torch.from_numpy(hosts[0]).to(dev), torch.from_numpy(hosts[1]).to(dev)) for _ in range(n_in)]
+    outs = [[torch.empty((BATCH, c, h, w), device=dev) for c in (3, 3, 3, 1)] for _ in range(n_out)]
+    table, raw_table = (kb._lib.PackedFrame * BATCH)(), (kb._lib.TrainFrame * BATCH)()
+    for j, (slot, raw_slot, (io, do, H, W, y, x)) in enumerate(zip(table, raw_table, frames)):
+        slot.image_offset, slot.depth_offset, slot.image_bytes, slot.depth_bytes = at[j], at[BATCH + j], len(files[j]), len(files[BATCH + j])
+        slot.height, slot.raw_width, slot.y_start, slot.x_start = H, 3 * W, y, x
+        raw_slot.image_offset, raw_slot.depth_offset, raw_slot.height, raw_slot.raw_width, raw_slot.y_start, raw_slot.x_start = io, do, H, 3 * W, y, x
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def packed(i):
+        (im, z), o = ins[i % n_in], outs[i % n_out]
+        rc = lib.kbn_unpack_packed_frames_forward(im.data_ptr(), im.numel(), z.data_ptr(), z.numel(), table, BATCH, h, w, 3, 16,
+                                                  o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), stream)
+        assert rc == 0, rc
+
+    def plain(i):
+        (im, z), o = raw_ins[i % n_in], outs[i % n_out]
+        rc = lib.kbn_unpack_train_frames_forward(im.data_ptr(), im.numel(), z.data_ptr(), z.numel(), raw_table, BATCH, h, w, 3, 16,
+                                                 o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), o[3].data_ptr(), stream)
+        assert rc == 0, rc
+
+    packed(0)
+    mine = [t.clone() for t in outs[0]]
+    plain(0)
+    torch.cuda.synchronize()
+    assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(mine, outs[0])), "the two kernels differ"
+    iters = 20 if quick else 400
+    t_plain = windows(plain, iters)
+    t_packed = windows(packed, iters)
+    t_plain_again = windows(plain, iters)
+    us = lambda t: spread([v * 1e3 for v in t])
+    ratio = statistics.median(t_packed) / statistics.median(t_plain + t_plain_again)
+    step_share = statistics.median(t_packed) / STEP_MS * 100
+    return [f"2. kernels: one batch, {BATCH} frames -> {h} x {w}; results equal bit for bit; packed input {(total[0] + total[1]) / 1e6:.1f} MB, raw input "
+            f"{(img_host.nbytes + dep_host.nbytes) / 1e6:.1f} MB, output {BATCH * h * w * 40 / 1e6:.1f} MB",
+            f"   kbn_unpack_train_frames_forward    device {us(t_plain)} us a launch (before), {us(t_plain_again)} us (after)",
+            f"   kbn_unpack_packed_frames_forward   device {us(t_packed)} us a launch",
+            f"   packed / raw-byte = {ratio:.2f} x; the packed launch is {step_share:.3f} % of the {STEP_MS} ms step"]
+
+
+def host_check_part(images, depths, packed_images, packed_depths):
+    """One thread: kbn_frame_check of a packed triplet and its depth map against the inflate (kbn_png_decode) of the PNG pair."""
+    lib = kb._lib.load()
+    n = min(16, len(images))
+    packed = [open(p, "rb").read() for p in packed_images[:n] + packed_depths[:n]]
+    pngs = [open(p, "rb").read() for p in images[:n] + depths[:n]]
+    outs = [np.empty_like(kb.loader.decode_png(f)) for f in pngs]
+    check_ms, inflate_ms = [], []
+    for _ in range(5):
+        t = time.perf_counter()
+        for data in packed:
+            assert lib.kbn_frame_check(data, len(data)) == 0
+        check_ms.append((time.perf_counter() - t) / n * 1e3)
+        t = time.perf_counter()
+        for data, out in zip(pngs, outs):
+            kb.loader.decode_png(data, out)
+        inflate_ms.append((time.perf_counter() - t) / n * 1e3)
+    return [f"4. host, one thread, per triplet with its depth map: kbn_frame_check {spread(check_ms, '{:.3f}')} ms; kbn_png_decode (inflate + filters) "
+            f"{spread(inflate_ms, '{:.2f}')} ms; inflate / check = {statistics.median(inflate_ms) / statistics.median(check_ms):.0f} x"]
+
+
+def packed_run(args, d, images, depths, ks, lines):
+    """--packed: sizes, loader rates packed against PNG at 2 and 8 workers, the two kernels, the host check."""
+    packed_images = [os.path.join(d, "packed", f"im{i}.kbf") for i in range(len(images))]
+    packed_depths = [os.path.join(d, "packed", f"sd{i}.kbf") for i in range(len(images))]
+    png_bytes, packed_bytes = kb.loader.pack_frames(images + depths, packed_images + packed_depths, workers=WORKERS)
+    raw_bytes = sum(RAW_SIZES[i % 2][0] * RAW_SIZES[i % 2][1] * (9 + 2) for i in range(len(images)))
+    lines.append(f"0. sizes of the {len(images)} SYNTHETIC samples (no real KITTI frame has been measured): PNG {png_bytes / 1e6:.1f} MB, packed {packed_bytes / 1e6:.1f} MB, "
+                 f"raw {raw_bytes / 1e6:.1f} MB; packed / PNG = {packed_bytes / png_bytes:.3f}, packed / raw = {packed_bytes / raw_bytes:.3f}, "
+                 f"PNG / raw = {png_bytes / raw_bytes:.3f}")
+    if not torch.cuda.is_available():
+        raise SystemExit("train_loader_bench needs a GPU: a time measured anywhere else says nothing")
+    dev = torch.device("cuda:0")
+    kb._lib.load()
+    lines[0] += f"; {torch.cuda.get_device_name(0)}"
+    need = BATCH / (STEP_MS * 1e-3)
+    lines.append(f"1. TrainingFrameLoader, triplets/s, median (min, max) of the epoch windows (the {STEP_MS} ms step takes {need:.0f} a GPU):")
+    medians = {}
+    for workers in (2, 8):
+        for name, im, de in (("PNG", images, depths), ("packed", packed_images, packed_depths)):
+            loader = kb.loader.TrainingFrameLoader(im, de, ks, shape=SHAPE, random_crop_type=CROP_TYPE, batch_size=BATCH, shuffle=True, device=dev,
+                                                   workers=workers, prefetch=4)
+
+            def epoch():
+                n = 0
+                for _ in range(4):
+                    for inputs in loader:
+                        n += inputs[0].shape[0]
+                torch.cuda.synchronize()
+                return n
+
+            rates = epochs(epoch, 2 if args.quick else 8)
+            medians[(name, workers)] = statistics.median(rates)
+            lines.append(f"   {name:6} workers={workers}   {spread(rates)}")
+    lines.append(f"   packed / PNG at 8 workers = {medians[('packed', 8)] / medians[('PNG', 8)]:.2f}; at 2 workers = {medians[('packed', 2)] / medians[('PNG', 2)]:.2f}; "
+                 f"packed at 2 workers / PNG at 8 workers = {medians[('packed', 2)] / medians[('PNG', 8)]:.2f}")
+    np.random.seed(0)
+    frames, img_at, dep_at = [], 0, 0
+    for i in range(BATCH):
+        H, W = RAW_SIZES[i % 2]
+        y, x = kb.loader.draw_crop(H, W, SHAPE, CROP_TYPE)
+        frames.append((img_at, dep_at, H, W, y, x))
+        img_at, dep_at = (img_at + H * 3 * W * 3 + 15) & ~15, (dep_at + H * W * 2 + 15) & ~15
+    lines += packed_kernel_part(dev, images, depths, packed_images, packed_depths, frames, args.quick)
+    packed_batch = sum(os.path.getsize(p) for p in packed_images[:BATCH] + packed_depths[:BATCH])
+    raw_batch = sum(H * 3 * W * 3 + H * W * 2 for _, _, H, W, _, _ in frames)
+    lines.append(f"3. PCIe bytes a batch: packed {packed_batch / 1e6:.1f} MB, raw bytes {raw_batch / 1e6:.1f} MB; packed / raw = {packed_batch / raw_batch:.2f}")
+    lines += host_check_part(images, depths, packed_images, packed_depths)
+    lines.append("5. multi-GPU effect: not measured (one GPU, one process).")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--packed", action="store_true", help="convert the files to packed frames and compare the packed path with the PNG path")
     ap.add_argument("--quick", action="store_true", help="16 files, short windows: a rehearsal, not a measurement")
     args = ap.parse_args()
     n_files = 16 if args.quick else N_FILES
@@ -182,6 +327,9 @@ def main():
         mb = sum(os.path.getsize(p) for p in images + depths) / 1e6
         lines = [f"train_loader_bench: {n_files} samples, {mb / n_files:.2f} MB of PNG a sample, batch {BATCH}, crop {SHAPE[0]} x {SHAPE[1]} "
                  f"{' '.join(CROP_TYPE)}, {WORKERS} workers"]
+        if args.packed:
+            packed_run(args, d, images, depths, ks, lines)
+            raise _Done
         # (b) first: its worker processes start, and run a whole epoch, before this process touches the GPU
         reference = torch.utils.data.DataLoader(ReferenceStyleDataset(images, depths, ks, SHAPE, CROP_TYPE), batch_size=BATCH, shuffle=True,
                                                 num_workers=WORKERS, drop_last=False, persistent_workers=True, multiprocessing_context="spawn")
@@ -227,6 +375,8 @@ def main():
         ref_bytes = BATCH * (10 * SHAPE[0] * SHAPE[1] * 4 + 36)
         lines += [f"3. PCIe bytes a batch: (a) {ours_bytes / 1e6:.1f} MB (the raw uint8 triplets and uint16 depth, whole frames, + intrinsics)   "
                   f"(b) {ref_bytes / 1e6:.1f} MB (ten float32 planes of the crop a frame + intrinsics)   (a) / (b) = {ours_bytes / ref_bytes:.2f}"]
+    except _Done:
+        pass
     finally:
         shutil.rmtree(d, ignore_errors=True)
     text = "\n".join(lines)

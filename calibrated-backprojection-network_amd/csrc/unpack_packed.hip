@@ -20,7 +20,7 @@
 // and leaves the workgroup's outputs unwritten when they disagree (files kbn_frame_check accepts always agree).  A field is read
 // byte by byte, only the bytes it touches, all of them inside its segment.
 #include "frame_pack.h"
-#include "kbn_common.h"
+#include "unpack_common.h"
 
 namespace kbn {
 
@@ -183,15 +183,7 @@ __global__ __launch_bounds__(UP_THREADS) void unpack_packed_kernel(const UnpackP
                     v[a] = is_depth ? s_f / 256.0f : s_f;
                 }
                 float* o = out + (long long)(g * fp::FP_ROWS + r - f.y_start) * p.width + x;
-                for (int c = 0; c < reps; ++c) {
-                    if constexpr (VEC) {
-                        *reinterpret_cast<f32x4*>(o + c * HW) = v;
-                    } else {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-                            if (a < n_live) o[c * HW + a] = v[a];
-                    }
-                }
+                for (int c = 0; c < reps; ++c) store_quad<VEC>(o + c * HW, v, n_live);
             }
             __syncthreads();
         }
@@ -213,10 +205,7 @@ extern "C" int kbn_unpack_packed_frames_forward(const unsigned char* images, siz
     int widest = 0;
     for (int i = 0; i < n; ++i) {   // every record before anything is launched
         const kbn_packed_frame& f = frames[i];
-        if (f.height < 1 || f.raw_width < 3 || f.raw_width % 3 != 0) return KBN_ERR_INVALID_ARGUMENT;
-        const long long W = f.raw_width / 3;
-        if (f.y_start < 0 || (long long)f.y_start + height > f.height) return KBN_ERR_INVALID_ARGUMENT;
-        if (f.x_start < 0 || (long long)f.x_start + width > W) return KBN_ERR_INVALID_ARGUMENT;
+        if (!crop_in_frame(f.height, f.raw_width, f.y_start, f.x_start, height, width)) return KBN_ERR_INVALID_ARGUMENT;
         if (f.image_offset < 0 || f.depth_offset < 0 || (f.image_offset | f.depth_offset) & 15) return KBN_ERR_INVALID_ARGUMENT;
         const unsigned long long groups = ((unsigned long long)f.height + fp::FP_ROWS - 1) / fp::FP_ROWS;
         if (f.image_bytes < fp::payload_start(groups, (unsigned)C) || f.depth_bytes < fp::payload_start(groups, 1u))
@@ -226,8 +215,7 @@ extern "C" int kbn_unpack_packed_frames_forward(const unsigned char* images, siz
         widest = std::max(widest, f.raw_width);
     }
     if (widest > KBN_UNPACK_PACKED_MAX_RAW_WIDTH) return KBN_ERR_UNSUPPORTED;   // the group's segment offsets must fit the LDS budget
-    const bool vec = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(image0) | reinterpret_cast<uintptr_t>(image1) |
-                                         reinterpret_cast<uintptr_t>(image2) | reinterpret_cast<uintptr_t>(sparse_depth0)) & 15) == 0;
+    const bool vec = outputs_vectorizable(width, image0, image1, image2, sparse_depth0);
     UnpackPackedParams p;
     p.images = images; p.depths = depths;
     p.image0 = image0; p.image1 = image1; p.image2 = image2; p.depth = sparse_depth0;

@@ -14,7 +14,7 @@
 // x_start C of a row: any alignment, so plain byte loads), 3 x 3 + 1 = 10 stores of 16 bytes out when w % 4 == 0 and the outputs are
 // 16-byte aligned (a wave then writes 1 KiB of a row per instruction), float by float otherwise.  3 C + 2 bytes in and 40 bytes out a
 // pixel: store bound.  Exact conversions only (uint8 / uint16 -> fp32, a division by 256).
-#include "kbn_common.h"
+#include "unpack_common.h"
 
 namespace kbn {
 
@@ -63,27 +63,13 @@ __global__ __launch_bounds__(UT_THREADS) void unpack_train_kernel(const UnpackTr
             v[2][i] = C >= 3 ? (in ? (float)s[i * C + 2] : 0.f) : c0;
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            if constexpr (VEC) {
-                *reinterpret_cast<f32x4*>(o + c * HW) = v[c];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < live) o[c * HW + i] = v[c][i];
-            }
-        }
+        for (int c = 0; c < 3; ++c) store_quad<VEC>(o + c * HW, v[c], live);
     }
     float* od = p.depth + b * HW + at;
     f32x4 z;
 #pragma unroll
     for (int i = 0; i < 4; ++i) z[i] = (VEC || i < live) ? (float)sd[i] / 256.0f : 0.f;
-    if constexpr (VEC) {
-        *reinterpret_cast<f32x4*>(od) = z;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < live) od[i] = z[i];
-    }
+    store_quad<VEC>(od, z, live);
 }
 
 template <int C, typename DepthT>
@@ -107,10 +93,8 @@ extern "C" int kbn_unpack_train_frames_forward(const unsigned char* images, size
     const long long sample = depth_bits / 8;
     for (int i = 0; i < n; ++i) {   // every record before anything is launched
         const kbn_train_frame& f = frames[i];
-        if (f.height < 1 || f.raw_width < 3 || f.raw_width % 3 != 0) return KBN_ERR_INVALID_ARGUMENT;
+        if (!crop_in_frame(f.height, f.raw_width, f.y_start, f.x_start, height, width)) return KBN_ERR_INVALID_ARGUMENT;
         const long long W = f.raw_width / 3;
-        if (f.y_start < 0 || (long long)f.y_start + height > f.height) return KBN_ERR_INVALID_ARGUMENT;
-        if (f.x_start < 0 || (long long)f.x_start + width > W) return KBN_ERR_INVALID_ARGUMENT;
         if (f.image_offset < 0 || f.depth_offset < 0 || f.depth_offset % sample != 0) return KBN_ERR_INVALID_ARGUMENT;
         const unsigned long long image_end = (unsigned long long)f.image_offset + (unsigned long long)f.height * f.raw_width * C;
         const unsigned long long depth_end = (unsigned long long)f.depth_offset + (unsigned long long)f.height * W * sample;
@@ -118,8 +102,7 @@ extern "C" int kbn_unpack_train_frames_forward(const unsigned char* images, size
     }
     const long long quads = (long long)height * ((width + 3) >> 2);
     if (quads > 0x7fffffffLL) return KBN_ERR_UNSUPPORTED;
-    const bool vec = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(image0) | reinterpret_cast<uintptr_t>(image1) |
-                                         reinterpret_cast<uintptr_t>(image2) | reinterpret_cast<uintptr_t>(sparse_depth0)) & 15) == 0;
+    const bool vec = outputs_vectorizable(width, image0, image1, image2, sparse_depth0);
     UnpackTrainParams p;
     p.images = images; p.depths = depths;
     p.image0 = image0; p.image1 = image1; p.image2 = image2; p.depth = sparse_depth0;

@@ -28,6 +28,12 @@ structural check `kbn_frame_check` there, crosses PCIe packed, and `ops.unpack_p
 on the device -- the same tensors bit for bit.  A batch is all PNG or all packed.  `frame_info`, `encode_frame`, `decode_frame`,
 `check_frame` are the host codec.
 
+Both loaders stage every batch, PNG or packed, the same way (`_Staging`): one set of flat pinned byte buffers per slot,
+`prefetch + 1` of them, grown with 1/8 of headroom when a batch needs more and never touched before the copies that last used it
+are done.  A submit path lays its files out, fills the set and passes its unpack op to `_Staging.submit`, which copies the used
+prefixes, launches and records the set's event.  A file's kind, size and format come from its first 33 bytes, read once a path
+(`_FileHeaders`); what is read later is checked against them.
+
 The output side (`run_kbnet.py --save_outputs`, reference src/kbnet.py:986-1026): `save_depth` / `save_depth_batch` for one tensor,
 and `OutputWriter` for the whole export of a run -- `ops.export_pack` makes the pixels of a batch's files in one launch, a side
 stream copies them to pinned slots, host threads encode and write while the next batch runs (kb.inference.run drives it).
@@ -219,6 +225,82 @@ def _one_kind(paths: Sequence[str], flags: Sequence[bool], what: str) -> bool:
             kind = {True: "a packed frame", False: "a PNG"}
             raise KbnError(f"{what}: a batch must be all PNG or all packed: {paths[0]} is {kind[flags[0]]}, {path} is {kind[flag]}")
     return bool(flags[0])
+
+
+class _FileHeaders(dict):
+    """path -> ((width, height, channels, bits), whether the file is a packed frame), from its first 33 bytes, read once a path."""
+
+    def __missing__(self, path: str):
+        with open(path, "rb") as f:
+            head = f.read(33)                            # a PNG's signature + IHDR; a packed frame's header is its first 32
+        self[path] = (_image_info(head), is_packed_frame(head))
+        return self[path]
+
+
+def _layout(sizes: Sequence[int]) -> Tuple[List[int], List[int]]:
+    """The files of a batch -- its images, then as many depth maps -- laid out in the two flat staging buffers, each file at a
+    16-byte-aligned offset: the offsets, and the bytes the image and the depth buffer need."""
+    nb = len(sizes) // 2
+    at, total = [], [0, 0]
+    for j, size in enumerate(sizes):
+        at.append(total[j // nb])
+        total[j // nb] = _align16(total[j // nb] + size)
+    return at, total
+
+
+def _places(st: dict, at: Sequence[int], sizes: Sequence[int]) -> List[tuple]:
+    """(flat pinned numpy view, offset, size) of every file of a batch -- images, then depth maps -- in the staging set `st`."""
+    nb = len(at) // 2
+    return list(zip([st["image"].numpy()] * nb + [st["depth"].numpy()] * nb, at, sizes))
+
+
+def _packed_jobs(st: dict, paths, at, sizes, want) -> List[tuple]:
+    """_read_packed_into's jobs for the files `paths`, planned with the headers `want`, at _layout's offsets."""
+    return [(path, view, a, size, w) for path, (view, a, size), w in zip(paths, _places(st, at, sizes), want)]
+
+
+def _load_intrinsics(st: dict, paths: Sequence[str], starts=None) -> None:
+    """The 3 x 3 matrices of `paths` into the set's pinned `k` block, each moved with its crop where `starts` gives the crops'
+    (y_start, x_start)."""
+    k_np = st["k"].numpy()
+    for j, path in enumerate(paths):
+        k = np.load(path).astype(np.float32)
+        k_np[j] = k if starts is None else _crop_intrinsics(k, *starts[j]).astype(np.float32)
+
+
+class _Staging:
+    """The pinned staging sets of a loader, one per slot (prefetch + 1 of them), whatever kind of file a batch holds: flat uint8
+    buffers `image` and `depth`, grown when a batch needs more, a `k` block of max(frames, batch_size) x 3 x 3 floats, and `done`,
+    the event of the copies that last used the set."""
+
+    def __init__(self, slots: int, batch_size: int, device, copy_stream):
+        self.batch_size, self.device, self.copy_stream = batch_size, device, copy_stream
+        self._sets = [{"image": None, "depth": None, "k": None, "done": None} for _ in range(slots)]
+
+    def acquire(self, slot: int, image_bytes: int, depth_bytes: int, frames: int) -> dict:
+        st = self._sets[slot]
+        if st["done"] is not None:
+            st["done"].synchronize()      # the copies that last used this staging set: it is not reused, let alone replaced, before
+        for name, need in (("image", image_bytes), ("depth", depth_bytes)):
+            if st[name] is None or st[name].numel() < need:
+                st[name] = torch.empty(need + need // 8, dtype=torch.uint8).pin_memory()     # some room: the next batch's frames differ a little
+        if st["k"] is None or st["k"].shape[0] < max(frames, self.batch_size):
+            st["k"] = torch.empty((max(frames, self.batch_size), 3, 3), dtype=torch.float32).pin_memory()
+        return st
+
+    def submit(self, st: dict, image_bytes: int, depth_bytes: int, frames: int, unpack):
+        """The set is filled: on the copy stream, the used prefix of each buffer goes to the device in one asynchronous copy,
+        `unpack(images_u8, depths_u8, intrinsics)` makes the batch's tensors of them, and the set's event is recorded.
+        Returns (tensors, event)."""
+        with torch.cuda.stream(self.copy_stream):
+            img_d = st["image"][:image_bytes].to(self.device, non_blocking=True)
+            dep_d = st["depth"][:depth_bytes].to(self.device, non_blocking=True)
+            k_d = st["k"][:frames].to(self.device, non_blocking=True)
+            tensors = unpack(img_d, dep_d, k_d)
+            done = torch.cuda.Event()
+            done.record(self.copy_stream)
+        st["done"] = done
+        return tensors, done
 
 
 # ---------------------------------------------- the reference's loader functions (numpy)
@@ -544,7 +626,9 @@ class InferenceFrameLoader:
     """Iterates `(image N x 3 x H x W in 0..255, sparse_depth N x 1 x H x W, intrinsics N x 3 x 3)` device
     batches over the files `datasets.KBNetInferenceDataset` would read (same constructor arguments,
     reference src/datasets.py:229-257), in order, the last batch possibly short.  All frames must have
-    one size.  Batch i+1 is decoded and copied while the caller works on batch i."""
+    one size.  Batch i+1 is decoded and copied while the caller works on batch i: `prefetch` batches are in flight, each in one
+    of `prefetch + 1` staging sets (`_Staging`) that PNG and packed batches share; files are told apart by their first bytes, read
+    once a path."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str],
                  intrinsics_paths: Sequence[str], use_image_triplet: bool = True, batch_size: int = 8,
@@ -566,29 +650,49 @@ class InferenceFrameLoader:
         # parallelism is batch_size x prefetch), each in its own set of pinned staging tensors
         self.prefetch = max(1, int(prefetch))
         self._driver = ThreadPoolExecutor(max_workers=self.prefetch)
-        self._stage: List[Optional[dict]] = [None] * (self.prefetch + 1)
-        self._stage_packed: List[Optional[dict]] = [None] * (self.prefetch + 1)
-        self._kind: dict = {}                                    # path -> whether it is a packed frame (its first bytes, read once)
+        self._staging = _Staging(self.prefetch + 1, self.batch_size, self.device, self.copy_stream)
+        self._file_header = _FileHeaders().__getitem__
 
     def __len__(self):
         return (self.n_sample + self.batch_size - 1) // self.batch_size
 
-    def _packed(self, path: str) -> bool:
-        if path not in self._kind:
-            with open(path, "rb") as f:
-                self._kind[path] = is_packed_frame(f.read(8))
-        return self._kind[path]
+    # -- one batch: lay out, fill a pinned staging set (decode on the pool, or read packed files), async H2D + unpack on the copy stream --
+    def _submit(self, b: int):
+        lo, hi = b * self.batch_size, min((b + 1) * self.batch_size, self.n_sample)
+        idx = list(range(lo, hi))
+        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
+        heads = [self._file_header(path) for path in paths]
+        if _one_kind(paths, [packed for _, packed in heads], "InferenceFrameLoader"):
+            return self._submit_packed(b, idx, paths, [info for info, _ in heads])
+        files = list(self.pool.map(_read, paths))
+        nb = len(idx)
+        wraw, hraw, c, bits = png_info(files[0])
+        wd, hd, cd, dbits = png_info(files[nb])
+        if bits != 8 or cd != 1:
+            raise KbnError("InferenceFrameLoader: expected 8-bit images and single-channel depth PNGs")
+        width = wraw // 3 if self.use_image_triplet else wraw
+        if (hd, wd) != (hraw, width):
+            raise KbnError(f"depth map is {hd} x {wd}, image is {hraw} x {width}")
+        for j in range(nb):
+            if png_info(files[j]) != (wraw, hraw, c, 8) or png_info(files[nb + j]) != (wd, hd, 1, dbits):
+                raise KbnError("InferenceFrameLoader: all frames of a run must have one size and format")
+        # frames of one size: dense in the flat buffers, which the device then views as nb x hraw x wraw x c and nb x hd x wd
+        sizes = [hraw * wraw * c] * nb + [hd * wd * (dbits // 8)] * nb
+        at = [j * sizes[0] for j in range(nb)] + [j * sizes[nb] for j in range(nb)]
+        st = self._staging.acquire(b % (self.prefetch + 1), nb * sizes[0], nb * sizes[nb], nb)
+        _load_intrinsics(st, [self.intrinsics_paths[i] for i in idx])
+        # one library call decodes the whole batch on its own threads (images first: they are the long poles)
+        decode_png_batch(files, [view[a:a + size] for view, a, size in _places(st, at, sizes)], threads=self.workers)
+        return self._staging.submit(st, nb * sizes[0], nb * sizes[nb], nb, lambda img_d, dep_d, k_d: tuple(ops.unpack_frames(
+            img_d.view(nb, hraw, wraw, c), dep_d.view(torch.int16 if dbits == 16 else torch.uint8).view(nb, hd, wd),
+            width=width, x_offset=width if self.use_image_triplet else 0)) + (k_d,))
 
-    def _submit_packed(self, b: int, idx, paths):
+    def _submit_packed(self, b: int, idx, paths, heads):
         """_submit for a batch of packed frames: the files go as they are into pinned staging, each at a 16-byte-aligned
         offset, pass kbn_frame_check there, cross PCIe packed, and ONE ops.unpack_packed_frames launch decodes the middle thirds."""
         if not self.use_image_triplet:
             raise KbnError("InferenceFrameLoader: packed images are decoded as triplets; use PNG files with use_image_triplet=False")
         nb = len(idx)
-        heads = []
-        for path in paths:
-            with open(path, "rb") as f:
-                heads.append(frame_info(f.read(FRAME_HEADER_BYTES)))
         wraw, hraw, c, bits = heads[0]
         wd, hd, cd, dbits = heads[nb]
         if bits != 8 or cd != 1:
@@ -601,97 +705,22 @@ class InferenceFrameLoader:
         if any(h != heads[0] for h in heads[:nb]) or any(h != heads[nb] for h in heads[nb:]):
             raise KbnError("InferenceFrameLoader: all frames of a run must have one size and format")
         sizes = [os.path.getsize(path) for path in paths]
-        at, total = [], [0, 0]
-        for j, size in enumerate(sizes):
-            which = 0 if j < nb else 1
-            at.append(total[which])
-            total[which] = _align16(total[which] + size)
-        slot = b % (self.prefetch + 1)
-        st = self._stage_packed[slot]
-        if st is None:
-            st = self._stage_packed[slot] = {"image": None, "depth": None, "k": torch.empty((self.batch_size, 3, 3), dtype=torch.float32).pin_memory(),
-                                             "done": None}
-        if st["done"] is not None:
-            st["done"].synchronize()      # the copies that last used this staging set
-        for name, need in (("image", total[0]), ("depth", total[1])):
-            if st[name] is None or st[name].numel() < need:
-                st[name] = torch.empty(need + need // 8, dtype=torch.uint8).pin_memory()
-        k_np = st["k"].numpy()
-        for j in range(nb):
-            k_np[j] = np.load(self.intrinsics_paths[idx[j]]).astype(np.float32)
-        views = (st["image"].numpy(), st["depth"].numpy())
-        _read_packed_into(self.pool, [(paths[j], views[0 if j < nb else 1], at[j], sizes[j], heads[j]) for j in range(2 * nb)])
+        at, total = _layout(sizes)
+        st = self._staging.acquire(b % (self.prefetch + 1), total[0], total[1], nb)
+        _load_intrinsics(st, [self.intrinsics_paths[i] for i in idx])
+        _read_packed_into(self.pool, _packed_jobs(st, paths, at, sizes, heads))
         frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, width, 0, 0) for j in range(nb)]
-        with torch.cuda.stream(self.copy_stream):
-            img_d = st["image"][:total[0]].to(self.device, non_blocking=True)
-            dep_d = st["depth"][:total[1]].to(self.device, non_blocking=True)
-            k_d = st["k"][:nb].to(self.device, non_blocking=True)
-            image, depth = ops.unpack_packed_frames(img_d, dep_d, frames, (hraw, width), channels=c, depth_bits=dbits, middle_only=True)
-            done = torch.cuda.Event()
-            done.record(self.copy_stream)
-        st["done"] = done
-        return image, depth, k_d, done
-
-    # -- one batch: decode on the pool into pinned memory, async H2D + unpack on the copy stream --
-    def _staging(self, slot: int, hraw: int, wraw: int, c: int, hd: int, wd: int, depth_dtype):
-        st = self._stage[slot]
-        key = (hraw, wraw, c, hd, wd, depth_dtype)
-        if st is None or st["key"] != key:
-            st = {"key": key,
-                  "image": torch.empty((self.batch_size, hraw, wraw, c), dtype=torch.uint8).pin_memory(),
-                  "depth": torch.empty((self.batch_size, hd, wd), dtype=depth_dtype).pin_memory(),
-                  "k": torch.empty((self.batch_size, 3, 3), dtype=torch.float32).pin_memory(),
-                  "done": None}
-            self._stage[slot] = st
-        return st
-
-    def _submit(self, b: int):
-        lo, hi = b * self.batch_size, min((b + 1) * self.batch_size, self.n_sample)
-        idx = list(range(lo, hi))
-        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
-        if _one_kind(paths, [self._packed(path) for path in paths], "InferenceFrameLoader"):
-            return self._submit_packed(b, idx, paths)
-        files = list(self.pool.map(_read, paths))
-        img_files, dep_files = files[:len(idx)], files[len(idx):]
-        wraw, hraw, c, bits = png_info(img_files[0])
-        wd, hd, cd, dbits = png_info(dep_files[0])
-        if bits != 8 or cd != 1:
-            raise KbnError("InferenceFrameLoader: expected 8-bit images and single-channel depth PNGs")
-        width = wraw // 3 if self.use_image_triplet else wraw
-        if (hd, wd) != (hraw, width):
-            raise KbnError(f"depth map is {hd} x {wd}, image is {hraw} x {width}")
-        st = self._staging(b % (self.prefetch + 1), hraw, wraw, c, hd, wd, torch.int16 if dbits == 16 else torch.uint8)
-        if st["done"] is not None:
-            st["done"].synchronize()      # the copies that last used this staging set
-        img_np, dep_np, k_np = st["image"].numpy(), st["depth"].numpy(), st["k"].numpy()
-        dep_view = dep_np.view(np.uint16) if dbits == 16 else dep_np
-
-        nb = len(idx)
-        for j in range(nb):
-            if png_info(img_files[j]) != (wraw, hraw, c, 8) or png_info(dep_files[j]) != (wd, hd, 1, dbits):
-                raise KbnError("InferenceFrameLoader: all frames of a run must have one size and format")
-            k_np[j] = np.load(self.intrinsics_paths[idx[j]]).astype(np.float32)
-        # one library call decodes the whole batch on its own threads (images first: they are the long poles)
-        decode_png_batch(img_files + dep_files, [img_np[j] for j in range(nb)] + [dep_view[j] for j in range(nb)],
-                         threads=self.workers)
-        with torch.cuda.stream(self.copy_stream):
-            img_d = st["image"][:nb].to(self.device, non_blocking=True)
-            dep_d = st["depth"][:nb].to(self.device, non_blocking=True)
-            k_d = st["k"][:nb].to(self.device, non_blocking=True)
-            image, depth = ops.unpack_frames(img_d, dep_d, width=width, x_offset=width if self.use_image_triplet else 0)
-            done = torch.cuda.Event()
-            done.record(self.copy_stream)
-        st["done"] = done
-        return image, depth, k_d, done
+        return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_packed_frames(
+            img_d, dep_d, frames, (hraw, width), channels=c, depth_bits=dbits, middle_only=True) + (k_d,))
 
     def __iter__(self):
         nb = len(self)
         pending = [self._driver.submit(self._submit, b) for b in range(min(self.prefetch, nb))]
         for b in range(nb):
-            image, depth, k, done = pending.pop(0).result()
+            batch, done = pending.pop(0).result()
             if b + self.prefetch < nb:
                 pending.append(self._driver.submit(self._submit, b + self.prefetch))
-            yield _hand_over(self.device, done, (image, depth, k))
+            yield _hand_over(self.device, done, batch)
 
 
 def _hand_over(device, done, tensors):
@@ -796,7 +825,8 @@ class TrainingFrameLoader:
     prefix of each buffer crosses PCIe as raw bytes in one asynchronous copy on a side stream, and `ops.unpack_train_frames`
     splits, crops and converts there.  A batch of packed frames (module docstring; all of a batch's files or none) skips the decode: the
     files themselves go to pinned staging, pass `kbn_frame_check` there, and `ops.unpack_packed_frames` decodes them on the device.
-    `prefetch` batches are in flight.  Without a crop (`shape` None or not positive) the frames of
+    `prefetch` batches are in flight, each in one of the `prefetch + 1` staging sets the two kinds share (`_Staging`: a set is grown
+    when a batch needs more, after the copies that last used it).  Without a crop (`shape` None or not positive) the frames of
     a batch must have one size.  An error found while a batch is prepared is raised when that batch is due.  One epoch at a time:
     `iter()` first waits for what an epoch that was left early still has in flight.
 
@@ -851,9 +881,8 @@ class TrainingFrameLoader:
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.prefetch = max(1, int(prefetch))                    # batches decoded concurrently, each in its own staging set
         self._driver = ThreadPoolExecutor(max_workers=min(16, self.prefetch))
-        self._stage: List[Optional[dict]] = [None] * (self.prefetch + 1)
-        self._headers: List[Optional[tuple]] = [None] * self.n_sample
-        self._packed: List[Optional[tuple]] = [None] * self.n_sample   # beside each header: whether the image / the depth file is a packed frame
+        self._staging = _Staging(self.prefetch + 1, self.batch_size, self.device, self.copy_stream)
+        self._file_header = _FileHeaders().__getitem__
         self._pending: list = []
         self._serial = 0                                         # batches submitted so far: picks the staging set
         self._order: Optional[list] = None                       # the running epoch's order, the batch iter() hands out next and the
@@ -876,16 +905,7 @@ class TrainingFrameLoader:
 
     # -- on the iterating thread: the batch's raw sizes, its checks and its crops --
     def _header(self, i: int):
-        if self._headers[i] is None:
-            heads, packed = [], []
-            for path in (self.image_paths[i], self.sparse_depth_paths[i]):
-                with open(path, "rb") as f:
-                    head = f.read(33)                            # a PNG's signature + IHDR; a packed frame's header is its first 32
-                heads.append(_image_info(head))
-                packed.append(is_packed_frame(head))
-            self._packed[i] = tuple(packed)
-            self._headers[i] = tuple(heads)
-        return self._headers[i]
+        return tuple(self._file_header(path)[0] for path in (self.image_paths[i], self.sparse_depth_paths[i]))
 
     def _plan(self, idx: Sequence[int]):
         """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped.
@@ -917,84 +937,42 @@ class TrainingFrameLoader:
         frames = [(i, hh, ww, y, x) for i, (hh, ww), (y, x) in zip(idx, sizes, starts)]
         return frames, shape, c, dbits, self.do_random_crop
 
-    # -- on a driver thread: read, decode into pinned memory, async H2D + unpack on the copy stream --
-    def _staging(self, slot: int, image_bytes: int, depth_bytes: int, frames: int):
-        st = self._stage[slot]
-        if st is None:
-            st = self._stage[slot] = {"image": None, "depth": None, "k": None, "done": None}
-        if st["done"] is not None:
-            st["done"].synchronize()      # the copies that last used this staging set: it is not reused, let alone replaced, before
-        for name, need in (("image", image_bytes), ("depth", depth_bytes)):
-            if st[name] is None or st[name].numel() < need:
-                st[name] = torch.empty(need + need // 8, dtype=torch.uint8).pin_memory()     # some room: the next batch's frames differ a little
-        if st["k"] is None or st["k"].shape[0] < frames:
-            st["k"] = torch.empty((frames, 3, 3), dtype=torch.float32).pin_memory()
-        return st
-
+    # -- on a driver thread: lay out, fill a pinned staging set (decode, or read packed files), async H2D + unpack on the copy stream --
     def _submit(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool):
         nb = len(plan)
         idx = [p[0] for p in plan]
         paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
-        for i in idx:
-            self._header(i)      # read already unless the plan comes from load_state_dict
-        if _one_kind(paths, [self._packed[i][0] for i in idx] + [self._packed[i][1] for i in idx], "TrainingFrameLoader"):
-            return self._submit_packed(slot, plan, shape, c, dbits, cropped, paths)
+        starts = [(y, x) for _, _, _, y, x in plan] if cropped else None
+        if _one_kind(paths, [self._file_header(path)[1] for path in paths], "TrainingFrameLoader"):      # read already unless the plan comes from load_state_dict
+            return self._submit_packed(slot, plan, shape, c, dbits, starts, paths)
         files = list(self.pool.map(_read, paths))
-        img_files, dep_files = files[:nb], files[nb:]
-        frames, img_at, dep_at = [], 0, 0
         for j, (i, hraw, w, y, x) in enumerate(plan):
-            if png_info(img_files[j]) != (3 * w, hraw, c, 8) or png_info(dep_files[j]) != (w, hraw, 1, dbits):
+            if png_info(files[j]) != (3 * w, hraw, c, 8) or png_info(files[nb + j]) != (w, hraw, 1, dbits):
                 raise KbnError(f"TrainingFrameLoader: {self.image_paths[i]} or {self.sparse_depth_paths[i]} changed since its header was read")
-            frames.append((img_at, dep_at, hraw, w, y, x))
-            img_at = _align16(img_at + hraw * 3 * w * c)
-            dep_at = _align16(dep_at + hraw * w * (dbits // 8))
-        st = self._staging(slot, img_at, dep_at, max(nb, self.batch_size))
-        img_np, dep_np, k_np = st["image"].numpy(), st["depth"].numpy(), st["k"].numpy()
-        for j, (i, hraw, w, y, x) in enumerate(plan):
-            k = np.load(self.intrinsics_paths[i]).astype(np.float32)
-            k_np[j] = (_crop_intrinsics(k, y, x) if cropped else k).astype(np.float32)
-        outs = [img_np[f[0]:f[0] + f[2] * 3 * f[3] * c] for f in frames] + [dep_np[f[1]:f[1] + f[2] * f[3] * (dbits // 8)] for f in frames]
+        sizes = [hraw * 3 * w * c for _, hraw, w, _, _ in plan] + [hraw * w * (dbits // 8) for _, hraw, w, _, _ in plan]
+        at, total = _layout(sizes)
+        st = self._staging.acquire(slot, total[0], total[1], nb)
+        _load_intrinsics(st, [self.intrinsics_paths[i] for i in idx], starts)
         # one library call decodes the whole batch on its own threads (images first: they are the long poles)
-        decode_png_batch(img_files + dep_files, outs, threads=self.workers)
-        with torch.cuda.stream(self.copy_stream):
-            img_d = st["image"][:img_at].to(self.device, non_blocking=True)
-            dep_d = st["depth"][:dep_at].to(self.device, non_blocking=True)
-            k_d = st["k"][:nb].to(self.device, non_blocking=True)
-            batch = ops.unpack_train_frames(img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,)
-            done = torch.cuda.Event()
-            done.record(self.copy_stream)
-        st["done"] = done
-        return batch, done
+        decode_png_batch(files, [view[a:a + size] for view, a, size in _places(st, at, sizes)], threads=self.workers)
+        frames = [(at[j], at[nb + j], hraw, w, y, x) for j, (_, hraw, w, y, x) in enumerate(plan)]
+        return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_train_frames(
+            img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,))
 
-    def _submit_packed(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool, paths):
+    def _submit_packed(self, slot: int, plan, shape, c: int, dbits: int, starts, paths):
         """_submit for a batch of packed frames: nothing is decoded on the host.  Every file is read straight into its
         16-byte-aligned place of the pinned staging buffer and passes kbn_frame_check there; the packed bytes cross PCIe in one
         asynchronous copy per buffer, and ONE ops.unpack_packed_frames launch decodes, splits, crops and converts."""
         nb = len(plan)
         sizes = [os.path.getsize(path) for path in paths]
-        at, total = [], [0, 0]
-        for j, size in enumerate(sizes):
-            which = 0 if j < nb else 1
-            at.append(total[which])
-            total[which] = _align16(total[which] + size)
-        st = self._staging(slot, total[0], total[1], max(nb, self.batch_size))
-        k_np = st["k"].numpy()
-        for j, (i, hraw, w, y, x) in enumerate(plan):
-            k = np.load(self.intrinsics_paths[i]).astype(np.float32)
-            k_np[j] = (_crop_intrinsics(k, y, x) if cropped else k).astype(np.float32)
-        views = (st["image"].numpy(), st["depth"].numpy())
+        at, total = _layout(sizes)
+        st = self._staging.acquire(slot, total[0], total[1], nb)
+        _load_intrinsics(st, [self.intrinsics_paths[p[0]] for p in plan], starts)
         want = [(3 * w, hraw, c, 8) for _, hraw, w, _, _ in plan] + [(w, hraw, 1, dbits) for _, hraw, w, _, _ in plan]
-        _read_packed_into(self.pool, [(paths[j], views[0 if j < nb else 1], at[j], sizes[j], want[j]) for j in range(2 * nb)])
+        _read_packed_into(self.pool, _packed_jobs(st, paths, at, sizes, want))
         frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, w, y, x) for j, (_, hraw, w, y, x) in enumerate(plan)]
-        with torch.cuda.stream(self.copy_stream):
-            img_d = st["image"][:total[0]].to(self.device, non_blocking=True)
-            dep_d = st["depth"][:total[1]].to(self.device, non_blocking=True)
-            k_d = st["k"][:nb].to(self.device, non_blocking=True)
-            batch = ops.unpack_packed_frames(img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,)
-            done = torch.cuda.Event()
-            done.record(self.copy_stream)
-        st["done"] = done
-        return batch, done
+        return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_packed_frames(
+            img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,))
 
     def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0, plan=None):
         """The batch's draws, now and here; the rest on a driver thread.  What goes wrong either way is kept for the batch's turn.

@@ -1334,6 +1334,48 @@ def export_pack(image=None, depth_a=None, depth_b=None, scale: float = 255.0, sh
 
 
 _TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
+_PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
+
+
+def _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, record, fields, place, max_raw_width=None, align=1):
+    """What unpack_train_frames and unpack_packed_frames (`fn`) check, in one order: the arguments, then every frame, then where the
+    tensors live -- a wrong frame is named on a machine without a GPU too.  `record`: the struct of one frame, its last four fields
+    H, 3 W, y_start, x_start; `fields`: the entries of a frame tuple, which end with H, W, y_start, x_start; `place(i, frame)` checks
+    where the frame lies in the two buffers and returns the record's leading fields.  Returns h, w, frames, n and the records."""
+    h, w = (int(v) for v in shape)
+    if h < 1 or w < 1:
+        raise KbnError(f"{fn}: the crop shape must be positive, got {h} x {w}")
+    if channels not in (1, 3, 4):
+        raise KbnError(f"{fn}: image channels must be 1, 3 or 4, got {channels}")
+    if depth_bits not in (8, 16):
+        raise KbnError(f"{fn}: depth samples must have 8 or 16 bits, got {depth_bits}")
+    frames = [tuple(int(v) for v in f) for f in frames]
+    n = len(frames)
+    if n < 1:
+        raise KbnError(f"{fn}: no frames")
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise KbnError(f"{fn}: {name}: expected a dense 1-d uint8 tensor")
+    records = bytearray(record.size * n)
+    for i, f in enumerate(frames):
+        if len(f) != fields.count(",") + 1:
+            raise KbnError(f"{fn}: frame {i}: expected ({fields}), got {f}")
+        H, W, y, x = f[-4:]
+        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
+            raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
+        if max_raw_width is not None and 3 * W > max_raw_width:
+            raise KbnError(f"{fn}: frame {i}: a packed triplet of {3 * W} columns is wider than the kernel takes ({max_raw_width})")
+        if y < 0 or y + h > H or x < 0 or x + w > W:
+            raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
+        record.pack_into(records, i * record.size, *place(i, f), H, 3 * W, y, x)
+    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
+        if not t.is_cuda:
+            raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+        if t.data_ptr() % align:
+            raise KbnError(f"{fn}: {name}: the buffer must be {align}-byte aligned")
+    if depths_u8.device != images_u8.device:
+        raise KbnError(f"{fn}: tensors live on different devices ({images_u8.device} and {depths_u8.device})")
+    return h, w, frames, n, records
 
 
 def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16):
@@ -1349,42 +1391,20 @@ def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, 
     (gray is replicated, alpha dropped).  What is wrong with a frame raises KbnError naming it; CPU tensors raise, there is no
     CPU fallback.  The records travel in the kernel arguments: nothing is allocated but the outputs, nothing copied, no wait."""
     fn = "unpack_train_frames"
-    h, w = (int(v) for v in shape)
     channels, depth_bits = int(channels), int(depth_bits)
-    if h < 1 or w < 1:
-        raise KbnError(f"{fn}: the crop shape must be positive, got {h} x {w}")
-    if channels not in (1, 3, 4):
-        raise KbnError(f"{fn}: image channels must be 1, 3 or 4, got {channels}")
-    if depth_bits not in (8, 16):
-        raise KbnError(f"{fn}: depth samples must have 8 or 16 bits, got {depth_bits}")
-    frames = [tuple(int(v) for v in f) for f in frames]
-    n = len(frames)
-    if n < 1:
-        raise KbnError(f"{fn}: no frames")
-    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-            raise KbnError(f"{fn}: {name}: expected a dense 1-d uint8 tensor")
-    records = bytearray(_TRAIN_FRAME_RECORD.size * n)
-    for i, f in enumerate(frames):
-        if len(f) != 6:
-            raise KbnError(f"{fn}: frame {i}: expected (image_offset, depth_offset, H, W, y_start, x_start), got {f}")
-        io, do, H, W, y, x = f
-        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
-            raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
-        if y < 0 or y + h > H or x < 0 or x + w > W:
-            raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
+
+    def place(i, f):
+        io, do, H, W = f[:4]
         if io < 0 or io + H * 3 * W * channels > images_u8.numel():
             raise KbnError(f"{fn}: frame {i}: its {H} x {3 * W} x {channels} triplet at byte {io} leaves the image buffer of {images_u8.numel()} bytes")
         if do < 0 or do % (depth_bits // 8) or do + H * W * (depth_bits // 8) > depths_u8.numel():
             raise KbnError(f"{fn}: frame {i}: its {H} x {W} depth map of {depth_bits}-bit samples at byte {do} is misaligned or leaves "
                            f"the depth buffer of {depths_u8.numel()} bytes")
-        _TRAIN_FRAME_RECORD.pack_into(records, i * _TRAIN_FRAME_RECORD.size, io, do, H, 3 * W, y, x)
-    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
-        if not t.is_cuda:
-            raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+        return io, do
+
+    h, w, frames, n, records = _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, _TRAIN_FRAME_RECORD,
+                                               "image_offset, depth_offset, H, W, y_start, x_start", place)
     device = images_u8.device
-    if depths_u8.device != device:
-        raise KbnError(f"{fn}: tensors live on different devices ({device} and {depths_u8.device})")
     image0, image1, image2 = (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(3))
     depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
     lib = _lib.load()
@@ -1396,9 +1416,6 @@ def unpack_train_frames(images_u8, depths_u8, frames, shape, channels: int = 3, 
                                                                   image2.data_ptr(), depth.data_ptr(), _stream()),
                       nbytes=float(n * h * w) * (3 * channels + depth_bits // 8 + 40)), "kbn_unpack_train_frames_forward")
     return image0, image1, image2, depth
-
-
-_PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
 
 
 def unpack_packed_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16, middle_only: bool = False):
@@ -1413,44 +1430,19 @@ def unpack_packed_frames(images_u8, depths_u8, frames, shape, channels: int = 3,
     kernel inside the files.  middle_only: returns (image0, sparse_depth0) and decodes only the middle third.  A raw width 3 W
     above _lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH raises KbnError (the kernel's LDS budget).  No CPU fallback."""
     fn = "unpack_packed_frames"
-    h, w = (int(v) for v in shape)
     channels, depth_bits = int(channels), int(depth_bits)
-    if h < 1 or w < 1:
-        raise KbnError(f"{fn}: the crop shape must be positive, got {h} x {w}")
-    if channels not in (1, 3, 4):
-        raise KbnError(f"{fn}: image channels must be 1, 3 or 4, got {channels}")
-    if depth_bits not in (8, 16):
-        raise KbnError(f"{fn}: depth samples must have 8 or 16 bits, got {depth_bits}")
-    frames = [tuple(int(v) for v in f) for f in frames]
-    n = len(frames)
-    if n < 1:
-        raise KbnError(f"{fn}: no frames")
-    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
-            raise KbnError(f"{fn}: {name}: expected a dense 1-d uint8 tensor")
-    records = bytearray(_PACKED_FRAME_RECORD.size * n)
-    for i, f in enumerate(frames):
-        if len(f) != 8:
-            raise KbnError(f"{fn}: frame {i}: expected (image_offset, image_bytes, depth_offset, depth_bytes, H, W, y_start, x_start), got {f}")
-        io, ib, do, db, H, W, y, x = f
-        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
-            raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
-        if 3 * W > _lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH:
-            raise KbnError(f"{fn}: frame {i}: a packed triplet of {3 * W} columns is wider than the kernel takes ({_lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH})")
-        if y < 0 or y + h > H or x < 0 or x + w > W:
-            raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
+
+    def place(i, f):
+        io, ib, do, db = f[:4]
         for what, at, size, buf in (("triplet", io, ib, images_u8), ("depth map", do, db, depths_u8)):
             if at < 0 or at % 16 or size < 1 or size > 0xffffffff or at + size > buf.numel():
                 raise KbnError(f"{fn}: frame {i}: its packed {what} of {size} bytes at byte {at} is misaligned or leaves its buffer of {buf.numel()} bytes")
-        _PACKED_FRAME_RECORD.pack_into(records, i * _PACKED_FRAME_RECORD.size, io, do, ib, db, H, 3 * W, y, x)
-    for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
-        if not t.is_cuda:
-            raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
-        if t.data_ptr() % 16:
-            raise KbnError(f"{fn}: {name}: the buffer must be 16-byte aligned")
+        return io, do, ib, db
+
+    h, w, frames, n, records = _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, _PACKED_FRAME_RECORD,
+                                               "image_offset, image_bytes, depth_offset, depth_bytes, H, W, y_start, x_start", place,
+                                               max_raw_width=_lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH, align=16)
     device = images_u8.device
-    if depths_u8.device != device:
-        raise KbnError(f"{fn}: tensors live on different devices ({device} and {depths_u8.device})")
     image0 = torch.empty((n, 3, h, w), device=device, dtype=torch.float32)
     image1, image2 = (None, None) if middle_only else (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(2))
     depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)

@@ -31,6 +31,7 @@ KBN_AUGMENT_STAGE_SELECT, KBN_AUGMENT_STAGE_APPLY = 1, 2
 KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames whose flags one launch carries; workspace bytes a frame and range map
 KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_forward launch carries
 KBN_UNPACK_PACKED_MAX_RAW_WIDTH = 16384   # widest packed triplet kbn_unpack_packed_frames_forward takes (its LDS budget)
+KBN_PACK_FRAMES_MAX_WIDTH = 16384   # widest plane row kbn_pack_frames_forward takes (its LDS budget)
 KBN_SUMMARY_CELL_ZERO, KBN_SUMMARY_CELL_COPY, KBN_SUMMARY_CELL_PHOTO_ERR, KBN_SUMMARY_CELL_DEPTH, KBN_SUMMARY_CELL_REL_ERR = 0, 1, 2, 3, 4
 KBN_SUMMARY_COLORMAP_VIRIDIS, KBN_SUMMARY_COLORMAP_INFERNO = 0, 1
 KBN_SUMMARY_MAX_ROWS = 4   # rows of a kbn_summary_panel_forward panel
@@ -275,6 +276,8 @@ SIGNATURES = {
     "kbn_export_pack_forward": (_I, [_P, _F, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "kbn_png_encode_rgb8_bound": (C.c_size_t, [_I, _I]),
     "kbn_png_encode_rgb8": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
+    "kbn_png_encode_gray8_bound": (C.c_size_t, [_I, _I]),
+    "kbn_png_encode_gray8": (_I, [_P, _I, _I, _P, C.c_size_t, _P, _I]),
     "kbn_unpack_frames_forward":(_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "kbn_unpack_train_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(TrainFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "kbn_frame_info": (_I, [_P, C.c_size_t, _P, _P, _P, _P]),
@@ -283,6 +286,9 @@ SIGNATURES = {
     "kbn_frame_decode": (_I, [_P, C.c_size_t, _P, C.c_size_t]),
     "kbn_frame_check": (_I, [_P, C.c_size_t]),
     "kbn_unpack_packed_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(PackedFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "kbn_pack_frames_stride": (C.c_size_t, [_I, _I, _I, _I]),
+    "kbn_pack_frames_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
+    "kbn_pack_frames_forward": (_I, [_P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "kbn_histogram_forward": (_I, [_P, _L, _P, _P, _P, _P, C.c_size_t, _P]),
     "kbn_crc32c": (C.c_uint, [C.c_char_p, C.c_size_t, C.c_uint]),
 }

@@ -297,10 +297,11 @@ int png_encode_gray16_impl(const unsigned short* pixels, int width, int height, 
 
 // 8-bit RGB (colour type 2): the image run_kbnet.py --save_outputs stores beside its depth maps (reference src/kbnet.py:1014-1016,
 // Image.fromarray of an H x W x 3 uint8 array).  `pixels`: height x width x 3, interleaved.
-int png_encode_rgb8_impl(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
-                         size_t* out_bytes, int level) {
+// With channels 1: 8-bit gray (colour type 0), what tools/unpack_dataset.py writes for a one-plane packed frame of 8 bits.
+int png_encode_u8_impl(const unsigned char* pixels, int width, int height, int channels, unsigned char* out, size_t out_capacity,
+                       size_t* out_bytes, int level) {
     if (!pixels || !out || !out_bytes || width < 1 || height < 1 || level < -1 || level > 9) return KBN_ERR_INVALID_ARGUMENT;
-    const size_t stride = 3 * (size_t)width, row = 1 + stride, raw = row * height;
+    const size_t stride = (size_t)channels * (size_t)width, row = 1 + stride, raw = row * height;
     if (raw > 0xffffffffull) return KBN_ERR_UNSUPPORTED;
     std::vector<unsigned char> lines(raw);
     for (int y = 0; y < height; ++y) {
@@ -308,7 +309,7 @@ int png_encode_rgb8_impl(const unsigned char* pixels, int width, int height, uns
         l[0] = 0;   // filter type None
         memcpy(l + 1, pixels + stride * y, stride);
     }
-    return png_emit(lines, width, height, 8, 2, out, out_capacity, out_bytes, level);
+    return png_emit(lines, width, height, 8, channels == 3 ? 2 : 0, out, out_capacity, out_bytes, level);
 }
 
 }  // namespace
@@ -341,7 +342,23 @@ size_t kbn_png_encode_rgb8_bound(int width, int height) {
 int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                         size_t* out_bytes, int level) {
     try {
-        return png_encode_rgb8_impl(pixels, width, height, out, out_capacity, out_bytes, level);
+        return png_encode_u8_impl(pixels, width, height, 3, out, out_capacity, out_bytes, level);
+    } catch (...) {
+        return KBN_ERR_WORKSPACE;
+    }
+}
+
+size_t kbn_png_encode_gray8_bound(int width, int height) {
+    if (width < 1 || height < 1) return 0;
+    const unsigned long long raw = (1ull + (unsigned long long)width) * (unsigned long long)height;
+    if (raw > 0xffffffffull) return 0;
+    return 8 + 25 + 12 + (size_t)compressBound((uLong)raw) + 12;
+}
+
+int kbn_png_encode_gray8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                         size_t* out_bytes, int level) {
+    try {
+        return png_encode_u8_impl(pixels, width, height, 1, out, out_capacity, out_bytes, level);
     } catch (...) {
         return KBN_ERR_WORKSPACE;
     }

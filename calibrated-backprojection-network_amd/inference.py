@@ -1,5 +1,6 @@
 """The inference entry point: the reference's run() (src/kbnet.py:676-1026, what run_kbnet.py calls) on this package's device path
--- score a checkpoint on a list of frames, write results.txt and, with save_outputs, the four directories of PNG files.
+-- score a checkpoint on a list of frames, write results.txt and, with save_outputs, the four directories of PNG files (or, through
+run_with_format(..., output_format="packed"), of packed frames encoded on the device: DESIGN 8u).
 
     reference, per frame (batch 1)                          here, per batch of any size
     DataLoader(KBNetInferenceDataset), .to(device)          loader.InferenceFrameLoader: decoded on host threads, raw bytes over PCIe
@@ -31,8 +32,8 @@ from .summary import log, log_evaluation_settings, log_input_settings, log_netwo
 
 
 class _GroundTruthReader:
-    """The ground-truth PNG files of batch b + 1 read and decoded (native reader, host threads) into a pinned slot while batch b
-    runs.  get(b) -> (host uint16 view nb x H x W, device int16 nb x H x W): the upload is one asynchronous copy of 2 bytes a pixel
+    """The ground-truth files of batch b + 1 -- PNGs or packed frames (told apart by the magic; a batch is all one or all the other)
+    -- read and decoded (native readers, host threads) into a pinned slot while batch b runs.  get(b) -> (host uint16 view nb x H x W, device int16 nb x H x W): the upload is one asynchronous copy of 2 bytes a pixel
     on the current stream.  A slot is decoded into again only after the copy that last read it has finished."""
 
     SLOTS = 3
@@ -53,17 +54,23 @@ class _GroundTruthReader:
     def _decode(self, b: int):
         paths = self.paths[b * self.batch_size:(b + 1) * self.batch_size]
         files = list(self.pool.map(loader._read, paths))
-        w, h, c, bits = loader.png_info(files[0])
+        packed = loader._one_kind(paths, [loader.is_packed_frame(data) for data in files], "run: ground truth")
+        info = (lambda data: loader.frame_info(data[:loader.FRAME_HEADER_BYTES])) if packed else loader.png_info
+        w, h, c, bits = info(files[0])
         for path, data in zip(paths, files):
-            if loader.png_info(data) != (w, h, 1, 16):
-                raise KbnError(f"run: ground truth {path} is not a 16-bit single-channel PNG of {h} x {w} like the first of its batch")
+            if info(data) != (w, h, 1, 16):
+                raise KbnError(f"run: ground truth {path} is not a 16-bit single-channel {'packed frame' if packed else 'PNG'} of "
+                               f"{h} x {w} like the first of its batch")
         slot = self.slots[b % self.SLOTS]
         if slot["copied"] is not None:
             slot["copied"].synchronize()
         if slot["host"] is None or tuple(slot["host"].shape[1:]) != (h, w):
             slot["host"] = torch.empty((self.batch_size, h, w), dtype=torch.int16).pin_memory()
         view = slot["host"].numpy().view(np.uint16)
-        loader.decode_png_batch(files, [view[j] for j in range(len(files))], threads=self.workers)
+        if packed:      # kbn_frame_decode runs kbn_frame_check first; ctypes drops the interpreter lock around it
+            list(self.pool.map(lambda j: loader.decode_frame(files[j], out=view[j]), range(len(files))))
+        else:
+            loader.decode_png_batch(files, [view[j] for j in range(len(files))], threads=self.workers)
         return slot, len(files)
 
     def get(self, b: int):
@@ -124,9 +131,61 @@ def run(image_path,
         workers=8,
         png_level=6,
         return_results=False):
+    """run_with_format with output_format "png": the reference's run() under its arguments, names and defaults, then keyword-only
+    batch_size, workers, png_level and return_results -- the signature of DESIGN 8n, which stays as it is.  Everything is documented
+    at run_with_format, which holds the code."""
+    return run_with_format(**locals())
+
+
+def run_with_format(image_path,
+                    sparse_depth_path,
+                    intrinsics_path,
+                    ground_truth_path=None,
+                    # Input settings
+                    input_channels_image=3,
+                    input_channels_depth=2,
+                    normalized_image_range=[0, 1],
+                    outlier_removal_kernel_size=7,
+                    outlier_removal_threshold=1.5,
+                    # Sparse to dense pool settings
+                    min_pool_sizes_sparse_to_dense_pool=[5, 7, 9, 11, 13],
+                    max_pool_sizes_sparse_to_dense_pool=[15, 17],
+                    n_convolution_sparse_to_dense_pool=3,
+                    n_filter_sparse_to_dense_pool=8,
+                    # Depth network settings
+                    n_filters_encoder_image=[48, 96, 192, 384, 384],
+                    n_filters_encoder_depth=[16, 32, 64, 128, 128],
+                    resolutions_backprojection=[0, 1, 2, 3],
+                    n_filters_decoder=[256, 128, 128, 64, 12],
+                    deconv_type="up",
+                    min_predict_depth=1.5,
+                    max_predict_depth=100.0,
+                    # Weight settings
+                    weight_initializer="xavier_normal",
+                    activation_func="leaky_relu",
+                    # Evaluation settings
+                    min_evaluate_depth=0.0,
+                    max_evaluate_depth=100.0,
+                    # Checkpoint settings
+                    checkpoint_path="trained_kbnet",
+                    depth_model_restore_path=None,
+                    # Output settings
+                    save_outputs=False,
+                    keep_input_filenames=False,
+                    # Hardware settings
+                    device="cuda",
+                    *,
+                    output_format="png",
+                    batch_size=8,
+                    workers=8,
+                    png_level=6,
+                    return_results=False):
     """The reference's run() (src/kbnet.py:676-1026): its arguments, names and defaults (src/global_constants.py), then keyword-only
     batch_size (frames a forward; the last batch may be short), workers (host threads of the loader, of the ground-truth reader and
-    of the writer), png_level (zlib level of the written files) and return_results.
+    of the writer), png_level (zlib level of the written files), return_results, and output_format: "png" (what run() passes) or
+    "packed" for packed frames (`<name>.kbf` in the same four directories, encoded on the device, readable as sparse
+    depth and ground truth by this package's loaders; png_level is ignored); any other value raises KbnError before anything else
+    happens.  run() is this function without output_format.
 
     image_path, sparse_depth_path, intrinsics_path, ground_truth_path: newline-delimited files of paths (loader.read_paths);
     ground_truth_path '' or None: no ground truth, no metrics.  As the reference's run() builds KBNetInferenceDataset with its default
@@ -143,6 +202,8 @@ def run(image_path,
     Differences from the reference, on purpose: batches instead of batch 1; the time line goes to results.txt too and is device time
     (events around preprocess + forward); device 'cpu' and path lists of different lengths raise KbnError; the image files of the
     [-1, 1] and [0, 255] ranges hold the picture (loader.image_export_affine); files are written while the run proceeds."""
+    if output_format not in loader.OUTPUT_FORMATS:
+        raise KbnError(f"run: output_format {output_format!r}: expected one of {', '.join(repr(f) for f in loader.OUTPUT_FORMATS)}")
     if device == "cuda" or device == "gpu":
         device = torch.device("cuda")
     else:
@@ -210,7 +271,8 @@ def run(image_path,
     truths = _GroundTruthReader(ground_truth_paths, batch_size, device, workers) if ground_truth_available else None
     writer = None
     if save_outputs:
-        writer = loader.OutputWriter(output_path, threads=workers, level=png_level, normalized_image_range=normalized_image_range)
+        writer = loader.OutputWriter(output_path, threads=workers, level=png_level, normalized_image_range=normalized_image_range,
+                                     file_format=output_format)
     rows, timers, kept = [], [], None
     seen = 0
     try:

@@ -304,9 +304,15 @@ class _Staging:
 
 
 # ---------------------------------------------- the reference's loader functions (numpy)
+def _decode_file(path: str) -> np.ndarray:
+    """The pixels of one PNG or packed file, told apart by the magic: the same array from either."""
+    data = _read(path)
+    return decode_frame(data) if is_packed_frame(data) else decode_png(data)
+
+
 def load_image(path: str, normalize: bool = True, data_format: str = "HWC") -> np.ndarray:
-    """reference src/data_utils.py:58-85 (`Image.open(path).convert('RGB')` -> float32)."""
-    px = decode_png(_read(path))
+    """reference src/data_utils.py:58-85 (`Image.open(path).convert('RGB')` -> float32); a packed frame is read like the PNG."""
+    px = _decode_file(path)
     if px.dtype != np.uint8:
         raise KbnError("load_image: 16-bit images are not supported")
     if px.ndim == 2:
@@ -327,10 +333,10 @@ def load_image_triplet(path: str, normalize: bool = True):
 
 
 def load_depth(path: str, data_format: str = "HW") -> np.ndarray:
-    """reference src/data_utils.py:123-152: 16-bit PNG / 256, non-positive values -> 0."""
-    z = np.array(decode_png(_read(path)), dtype=np.float32)
+    """reference src/data_utils.py:123-152: 16-bit PNG (or packed frame) / 256, non-positive values -> 0."""
+    z = np.array(_decode_file(path), dtype=np.float32)
     if z.ndim != 2:
-        raise KbnError("load_depth: expected a single-channel PNG")
+        raise KbnError("load_depth: expected a single-channel PNG or packed frame")
     z = z / 256.0
     z[z <= 0] = 0.0
     if data_format == "HW":
@@ -386,7 +392,7 @@ _scratch = threading.local()    # one encode buffer per host thread, grown as ne
 
 def _encode_png(kind: str, pixels: np.ndarray, width: int, height: int, level: int) -> memoryview:
     """The PNG file image of C-contiguous pixels, as a view of the calling thread's scratch buffer: valid until that thread encodes
-    again.  kind: 'gray16' (H x W uint16) or 'rgb8' (H x W x 3 uint8).  ctypes drops the interpreter lock around the encoder."""
+    again.  kind: 'gray16' (H x W uint16), 'rgb8' (H x W x 3 uint8) or 'gray8' (H x W uint8).  ctypes drops the interpreter lock around the encoder."""
     lib = _lib.load()
     cap = getattr(lib, f"kbn_png_encode_{kind}_bound")(width, height)
     buf = getattr(_scratch, "buf", None)
@@ -413,6 +419,36 @@ def encode_depth_png(samples: np.ndarray, level: int = 6) -> bytes:
     if a.ndim != 2:
         raise KbnError("encode_depth_png: expected an H x W array")
     return bytes(_encode_png("gray16", a, a.shape[1], a.shape[0], level))
+
+
+def unpack_frames(src_packed_paths: Sequence[str], dst_png_paths: Sequence[str], workers: int = 8, level: int = 6) -> Tuple[int, int]:
+    """The inverse of pack_frames: packed frames to PNG files, src_packed_paths[i] -> dst_png_paths[i], on `workers` host threads --
+    decoded on the host (kbn_frame_decode, after kbn_frame_check), encoded with the native PNG encoders, written under a temporary
+    name and moved into place.  8-bit RGB, 8-bit gray and 16-bit gray frames; any other format raises KbnError naming the file.
+    Returns (packed bytes read, PNG bytes written)."""
+    if len(src_packed_paths) != len(dst_png_paths):
+        raise KbnError(f"unpack_frames: {len(src_packed_paths)} sources, {len(dst_png_paths)} destinations")
+    kinds = {(3, 8): "rgb8", (1, 8): "gray8", (1, 16): "gray16"}
+
+    def one(pair):
+        src, dst = pair
+        data = _read(src)
+        if not is_packed_frame(data):
+            raise KbnError(f"unpack_frames: {src} is not a packed frame")
+        w, h, c, bits = frame_info(data[:FRAME_HEADER_BYTES])
+        if (c, bits) not in kinds:
+            raise KbnError(f"unpack_frames: {src} holds {c} channels of {bits} bits; 8-bit RGB, 8-bit gray and 16-bit gray become PNGs")
+        png = bytes(_encode_png(kinds[(c, bits)], decode_frame(data), w, h, level))
+        os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+        tmp = f"{dst}.tmp{os.getpid()}.{threading.get_ident()}"
+        with open(tmp, "wb") as f:
+            f.write(png)
+        os.replace(tmp, dst)
+        return len(data), len(png)
+
+    with ThreadPoolExecutor(max_workers=max(1, int(workers))) as ex:
+        sizes = list(ex.map(one, zip(src_packed_paths, dst_png_paths)))
+    return sum(s[0] for s in sizes), sum(s[1] for s in sizes)
 
 
 def depth_samples(z) -> np.ndarray:
@@ -455,6 +491,13 @@ def save_depth_batch(z: torch.Tensor, paths: Sequence[str], threads: int = 8) ->
 
 
 OUTPUT_DIRECTORIES = ("image", "output_depth", "sparse_depth", "ground_truth")     # reference src/kbnet.py:991-1001
+OUTPUT_FORMATS = ("png", "packed")      # OutputWriter's file_format, inference.run_with_format's output_format
+PACKED_EXTENSION = ".kbf"
+
+
+def packed_filename(filename: str) -> str:
+    """The name OutputWriter(file_format="packed") gives the file that would be the PNG `filename`: its extension replaced."""
+    return os.path.splitext(filename)[0] + PACKED_EXTENSION
 
 
 def image_export_affine(normalized_image_range) -> Tuple[float, float]:
@@ -492,10 +535,22 @@ class OutputWriter:
     it), everything downstream reads the writer's own packed buffer, and `ground_truth_samples` is copied into the slot before
     submit() returns.
 
+    file_format "packed"  writes packed frames (`<name>.kbf` where "png" writes `<name>.png`) that this package's loaders
+    read back, and no host thread encodes an output: after the export_pack launch two ops.pack_frames calls on the caller's stream
+    encode the RGB pixels (3 planes of 8 bits) and the 2 N planes of 16 bits into the slot's device buffer; the side stream copies
+    every file's SLOT (the sizes are known to the device alone, so the bound is copied: 7.6 bytes a pixel at KITTI size, beside
+    the 7 of the PNG path) and the sizes; a host thread reads its file's size, runs kbn_frame_check on the bytes where they lie,
+    writes them under a temporary name and moves the file into place.  Only the ground truth's host samples are encoded on the pool (encode_frame).
+    `level` is ignored.  Slot reuse, back-pressure, error delivery and the guarantee below are the same.
+
     close() waits for everything and raises the first error a thread met; the object is a context manager.  One writer is driven
     by one thread."""
 
-    def __init__(self, output_path: str, threads: int = 8, in_flight: int = 2, level: int = 6, normalized_image_range=(0, 1)):
+    def __init__(self, output_path: str, threads: int = 8, in_flight: int = 2, level: int = 6, normalized_image_range=(0, 1),
+                 file_format: str = "png"):
+        if file_format not in OUTPUT_FORMATS:
+            raise KbnError(f"OutputWriter: file_format {file_format!r}: expected one of {', '.join(repr(f) for f in OUTPUT_FORMATS)}")
+        self.file_format = file_format
         self.scale, self.shift = image_export_affine(normalized_image_range)
         if not -1 <= int(level) <= 9:
             raise KbnError(f"OutputWriter: zlib level {level} (-1 .. 9)")
@@ -560,6 +615,8 @@ class OutputWriter:
             if truth.dtype != np.uint16 or truth.shape != (n, h, w):
                 raise KbnError(f"OutputWriter: ground_truth_samples is {truth.dtype} {truth.shape}, expected uint16 {(n, h, w)}")
         device = image.device
+        if self.file_format == "packed":
+            return self._submit_packed(filenames, image, output_depth, sparse_depth, truth, device, n, h, w)
         with torch.cuda.device(device):
             if self._copy_stream is None or self._copy_stream.device != device:
                 self._copy_stream = torch.cuda.Stream(device=device)
@@ -595,6 +652,85 @@ class OutputWriter:
         data = _encode_png(kind, pixels, w, h, self.level)
         with open(os.path.join(dirpath, filename), "wb") as f:
             f.write(data)
+
+    # -- file_format "packed": a slot holds [rgb | 2 x capacity planes of samples] on the device, and the encoded files' slots +
+    #    their sizes on the device and pinned --
+    def _packed_slot(self, device, n: int, h: int, w: int) -> dict:
+        slot = self._slots[self._serial % len(self._slots)]
+        self._serial += 1
+        self._drain(slot)
+        if slot["key"] is None or slot["key"][0] != device or slot["key"][2:] != (h, w) or slot["key"][1] < n:
+            px = n * h * w
+            at_depth = _align16(3 * px)
+            strides = (ops.pack_frames_stride(h, w, 3, 8), ops.pack_frames_stride(h, w, 1, 16))
+            at_files = n * strides[0]
+            work = max(ops.pack_frames_workspace_bytes(n, h, w, 3, 8), ops.pack_frames_workspace_bytes(2 * n, h, w, 1, 16))
+            slot.update(key=(device, n, h, w), at=at_depth, strides=strides, at_files=at_files,
+                        pixels=torch.empty(at_depth + 4 * px, dtype=torch.uint8, device=device),
+                        device=torch.empty(at_files + 2 * n * strides[1], dtype=torch.uint8, device=device),
+                        sizes=torch.empty(3 * n, dtype=torch.int64, device=device),
+                        workspace=torch.empty(work, dtype=torch.uint8, device=device),
+                        host=torch.empty(at_files + 2 * n * strides[1], dtype=torch.uint8).pin_memory(),
+                        host_sizes=torch.empty(3 * n, dtype=torch.int64).pin_memory(), truth=np.empty((n, h, w), dtype=np.uint16))
+            for name in ("device", "sizes"):
+                slot[name].record_stream(self._copy_stream)      # the allocator learns that the side stream reads them
+        return slot
+
+    def _submit_packed(self, filenames, image, output_depth, sparse_depth, truth, device, n: int, h: int, w: int) -> None:
+        with torch.cuda.device(device):
+            if self._copy_stream is None or self._copy_stream.device != device:
+                self._copy_stream = torch.cuda.Stream(device=device)
+            slot = self._packed_slot(device, n, h, w)
+            capacity, px = slot["key"][1], n * h * w
+            s_rgb, s_depth = slot["strides"]
+            rgb = slot["pixels"][:3 * px].view(n, h, w, 3)
+            planes = slot["pixels"][slot["at"]:slot["at"] + 4 * px].view(torch.int16).view(2 * n, h, w)      # output depth, then sparse depth
+            ops.export_pack(image, output_depth, sparse_depth, scale=self.scale, shift=self.shift, out=(rgb, planes[:n], planes[n:]))
+            files = {which: slot[which][:capacity * s_rgb].view(capacity, s_rgb)[:n] for which in ("device", "host")}
+            depth_files = {which: slot[which][slot["at_files"]:].view(2 * capacity, s_depth)[:2 * n] for which in ("device", "host")}
+            ops.pack_frames(rgb, out=files["device"], out_bytes=slot["sizes"][:n], workspace=slot["workspace"])
+            ops.pack_frames(planes, out=depth_files["device"], out_bytes=slot["sizes"][n:3 * n], workspace=slot["workspace"])
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(device))
+            self._copy_stream.wait_event(ready)
+            with torch.cuda.stream(self._copy_stream):
+                files["host"].copy_(files["device"], non_blocking=True)
+                depth_files["host"].copy_(depth_files["device"], non_blocking=True)
+                slot["host_sizes"][:3 * n].copy_(slot["sizes"][:3 * n], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+        if truth is not None:
+            np.copyto(slot["truth"][:n], truth)
+        sizes = slot["host_sizes"].numpy()
+        rgb_host, depth_host = files["host"].numpy(), depth_files["host"].numpy()
+        jobs = []
+        for i, filename in enumerate(filenames):
+            name = packed_filename(filename)
+            jobs.append((self._write_packed, done, rgb_host[i], sizes, i, os.path.join(self.dirpaths["image"], name)))
+            jobs.append((self._write_packed, done, depth_host[i], sizes, n + i, os.path.join(self.dirpaths["output_depth"], name)))
+            jobs.append((self._write_packed, done, depth_host[n + i], sizes, 2 * n + i, os.path.join(self.dirpaths["sparse_depth"], name)))
+            if truth is not None:
+                jobs.append((self._write_truth_packed, slot["truth"][i], os.path.join(self.dirpaths["ground_truth"], name)))
+        slot["files"] = [self.pool.submit(*job) for job in jobs]
+
+    @staticmethod
+    def _place(data, path: str) -> None:
+        tmp = f"{path}.tmp{os.getpid()}.{threading.get_ident()}"
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)
+
+    def _write_packed(self, done, file_slot: np.ndarray, sizes: np.ndarray, index: int, path: str) -> None:
+        done.synchronize()      # the slot's copies have landed: the file's bytes and its size
+        size = int(sizes[index])
+        if not FRAME_HEADER_BYTES <= size <= file_slot.shape[0]:
+            raise KbnError(f"OutputWriter: the device encoder reports {size} bytes for {path}, its slot holds {file_slot.shape[0]}")
+        data = file_slot[:size]
+        check_frame(data)       # where the bytes lie
+        self._place(data, path)
+
+    def _write_truth_packed(self, samples: np.ndarray, path: str) -> None:
+        self._place(encode_frame(samples), path)
 
     def close(self) -> None:
         """Waits for every file; raises the first error a thread met (once)."""

@@ -1333,6 +1333,84 @@ def export_pack(image=None, depth_a=None, depth_b=None, scale: float = 255.0, sh
     return tuple(outs)
 
 
+def pack_frames_stride(height: int, width: int, channels: int, bits: int) -> int:
+    """Bytes of one frame's slot in pack_frames' `out` (kbn_pack_frames_stride: the encoder's bound rounded up to 16); raises
+    KbnError for sizes the device encoder refuses."""
+    stride = int(_lib.load().kbn_pack_frames_stride(int(width), int(height), int(channels), int(bits)))
+    if stride == 0:
+        raise KbnError(f"pack_frames: {height} x {width} x {channels} samples of {bits} bits cannot be packed on the device (channels 1, 3 "
+                       f"or 4, bits 8 or 16, sizes >= 1, width <= {_lib.KBN_PACK_FRAMES_MAX_WIDTH}, an encoding below 4 GiB)")
+    return stride
+
+
+def pack_frames_workspace_bytes(n: int, height: int, width: int, channels: int, bits: int) -> int:
+    """Device bytes pack_frames needs as `workspace` for n such frames (kbn_pack_frames_workspace_bytes)."""
+    pack_frames_stride(height, width, channels, bits)
+    return int(_lib.load().kbn_pack_frames_workspace_bytes(int(n), int(width), int(height), int(channels), int(bits)))
+
+
+@_on_tensor_device
+def pack_frames(samples, bits=None, out=None, out_bytes=None, workspace=None):
+    """The packed files of a batch of frames, encoded ON THE DEVICE (kbn_pack_frames_forward, csrc/pack_frames.hip) ->
+    (out, out_bytes): out[i, :out_bytes[i]] is byte for byte loader.encode_frame of frame i.
+      samples   N x H x W x C uint8 (C = 1, 3, 4), N x H x W uint8 or int16, or N x H x W x C int16 -- int16 holding the uint16 bit
+                patterns, as export_pack returns them; dense, on the device
+      bits      8 or 16, by default what the dtype says
+      out       N x stride uint8, stride a multiple of 16 and >= pack_frames_stride(H, W, C, bits), 16-byte aligned, rows dense;
+                a view of a larger buffer is welcome.  Bytes past out_bytes[i] keep what they held.
+      out_bytes N int64 on the device: the sizes are known to the device alone, no host synchronisation here
+      workspace a dense uint8 device tensor of at least pack_frames_workspace_bytes(...) bytes; allocated when None
+    Three launches, whatever N is.  CPU tensors raise KbnError (no CPU fallback), so do shapes and dtypes that disagree, naming the
+    offender."""
+    fn = "pack_frames"
+    if not isinstance(samples, torch.Tensor) or not samples.is_cuda:
+        raise KbnError(f"{fn}: samples: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+    t = samples.detach()
+    if t.dtype not in (torch.uint8, torch.int16) or t.dim() not in (3, 4):
+        raise KbnError(f"{fn}: samples is {t.dtype} {tuple(t.shape)}, expected N x H x W (x C) uint8 or int16 (uint16 bit patterns)")
+    want_bits = 8 if t.dtype == torch.uint8 else 16
+    if bits is not None and int(bits) != want_bits:
+        raise KbnError(f"{fn}: bits {bits} with {t.dtype} samples (uint8 holds 8 bits, int16 the uint16 patterns of 16)")
+    n, h, w = (int(v) for v in t.shape[:3])
+    c = int(t.shape[3]) if t.dim() == 4 else 1
+    if n < 1 or h < 1 or w < 1 or c < 1:
+        raise KbnError(f"{fn}: samples is empty: {tuple(t.shape)}")
+    if c not in (1, 3, 4):
+        raise KbnError(f"{fn}: samples has {c} channels, expected 1, 3 or 4")
+    t = t.contiguous()
+    device = t.device
+    stride = pack_frames_stride(h, w, c, want_bits)
+    if out is None:
+        out = torch.empty((n, stride), device=device, dtype=torch.uint8)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+            raise KbnError(f"{fn}: out: expected a tensor on {device} (the HIP path has no CPU fallback)")
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1:
+            raise KbnError(f"{fn}: out is {out.dtype} {tuple(out.shape)}, expected uint8 {n} x stride with dense rows")
+        if out.shape[1] < stride or out.shape[1] % 16 or (n > 1 and (out.stride(0) % 16 or out.stride(0) < out.shape[1])):
+            raise KbnError(f"{fn}: out is {tuple(out.shape)} with rows {out.stride(0)} bytes apart: a slot is a multiple of 16 bytes and at least {stride}")
+        if out.data_ptr() % 16:
+            raise KbnError(f"{fn}: out is not 16-byte aligned")
+    out_stride = int(out.stride(0)) if n > 1 else int(out.shape[1])
+    if out_bytes is None:
+        out_bytes = torch.empty((n,), device=device, dtype=torch.int64)
+    elif (not isinstance(out_bytes, torch.Tensor) or not out_bytes.is_cuda or out_bytes.device != device or out_bytes.dtype != torch.int64
+          or tuple(out_bytes.shape) != (n,) or not out_bytes.is_contiguous()):
+        raise KbnError(f"{fn}: out_bytes: expected a contiguous int64 tensor of {n} on {device}")
+    lib = _lib.load()
+    need = int(lib.kbn_pack_frames_workspace_bytes(n, w, h, c, want_bits))
+    if workspace is None:
+        workspace = torch.empty((need,), device=device, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != device or workspace.dtype != torch.uint8
+          or not workspace.is_contiguous() or workspace.numel() < need):
+        raise KbnError(f"{fn}: workspace: expected a dense uint8 tensor of at least {need} bytes on {device}")
+    check(_launch("pack_frames", 0.0,
+                  lambda: lib.kbn_pack_frames_forward(t.data_ptr(), n, w, h, c, want_bits, out.data_ptr(), out_stride, out_bytes.data_ptr(),
+                                                      workspace.data_ptr(), workspace.numel(), _stream()),
+                  nbytes=float(n * h * w * c) * (want_bits // 8) * 3.0), "kbn_pack_frames_forward")
+    return out, out_bytes
+
+
 _TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
 _PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
 

@@ -1040,6 +1040,11 @@ int kbn_export_pack_forward(const float* image, float scale, float shift, const 
 size_t kbn_png_encode_rgb8_bound(int width, int height);
 int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                         size_t* out_bytes, int level);
+/* HOST: height x width uint8 -> an 8-bit grayscale PNG, under kbn_png_encode_rgb8's contract (tools/unpack_dataset.py writes a
+ * one-plane packed frame of 8 bits with it). */
+size_t kbn_png_encode_gray8_bound(int width, int height);
+int kbn_png_encode_gray8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
+                         size_t* out_bytes, int level);
 
 /* Decoded pixels (device buffers) -> the tensors the reference's dataset returns:
  *   image_u8     N x height x raw_width x image_channels uint8 (1 gray, 3 RGB, 4 RGBA); columns
@@ -1132,6 +1137,34 @@ typedef struct kbn_packed_frame {
 int kbn_unpack_packed_frames_forward(const unsigned char* images, size_t image_bytes, const unsigned char* depths, size_t depth_bytes,
                                      const kbn_packed_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
                                      float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
+
+/* The device ENCODER of the packed frame store (csrc/pack_frames.hip): n frames of one size -> n file images, each byte
+ * for byte what kbn_frame_encode writes for the same samples (header, table, zero padding up to the payload, payload).
+ *   kbn_pack_frames_stride           capacity of one frame's slot: kbn_frame_encode_bound rounded up to 16; 0 for sizes the encoder
+ *                                    refuses
+ *   kbn_pack_frames_workspace_bytes  device bytes a call needs (a payload length per (frame, group, plane), a byte per segment); 0
+ *                                    for sizes the encoder refuses and n < 1
+ *   kbn_pack_frames_forward
+ *     samples    n x height x width x channels interleaved, uint8 or (bits 16) uint16 (2-byte aligned), dense, on the DEVICE -- per
+ *                frame exactly what kbn_frame_encode takes on the host
+ *     out        frame i's file image at out + i * out_stride (out 16-byte aligned, out_stride a multiple of 16 and >=
+ *                kbn_pack_frames_stride); out_bytes[i] (8-byte aligned): its size, written by the device.  Bytes of a slot past
+ *                out_bytes[i], and anything outside the slots, stay as they were.
+ *     workspace  workspace_bytes >= kbn_pack_frames_workspace_bytes device bytes, 4-byte aligned; no allocation in here
+ * Three launches whatever n is (sizes, table, emit), no host synchronisation, integer work: the same bytes on every run.
+ * Before anything is launched -- KBN_ERR_INVALID_ARGUMENT: NULL pointers, sizes < 1, a misaligned pointer, a stride that is short
+ * or not a multiple of 16; KBN_ERR_WORKSPACE: a short workspace; KBN_ERR_UNSUPPORTED: other channel counts or bit widths, an
+ * encoding that could pass 4 GiB, n x ceil(height / 8) > 2^31 - 1 (the grid's first dimension), a width above
+ * KBN_PACK_FRAMES_MAX_WIDTH, the samples of one plane row.  The cap is the emit kernel's LDS budget: it keeps one byte offset of 4
+ * bytes for each of the 8 x ceil(width / 16) segments of a (group, plane) in LDS, 2 x width bytes = 32 KB at the cap, beside the
+ * 8.2 KB image it assembles the payload in -- 40.2 KB of the 64 KB a workgroup gets without opting in to more (the decoder's
+ * KBN_UNPACK_PACKED_MAX_RAW_WIDTH is the same budget). */
+#define KBN_PACK_FRAMES_MAX_WIDTH 16384
+size_t kbn_pack_frames_stride(int width, int height, int channels, int bits);
+size_t kbn_pack_frames_workspace_bytes(int n, int width, int height, int channels, int bits);
+int kbn_pack_frames_forward(const void* samples, int n, int width, int height, int channels, int bits, unsigned char* out,
+                            size_t out_stride, unsigned long long* out_bytes, void* workspace, size_t workspace_bytes,
+                            kbn_stream_t stream);
 
 /* TensorBoard's default histogram of an fp32 device tensor -- what SummaryWriter.add_histogram(bins='tensorflow') computes on the
  * host, np.histogram(values.astype(float), bins=edges) with min, max, sum and values.dot(values) -- in one pass (csrc/histogram.hip).

@@ -5,7 +5,8 @@
                                  --output_root /data/kitti_packed [--list_dir training/kitti_packed] [--workers 8]
 
 --paths: reference-style path lists (one path a line, kb.loader.read_paths) of IMAGE and SPARSE DEPTH files: these are the paths
-the loaders take packed.  Intrinsics stay .npy and ground truth stays PNG: pass their lists on unchanged.
+the loaders take packed; GROUND TRUTH lists may be given too (kb.inference.run and train()'s validation read packed ground truth,
+DESIGN 8u).  Intrinsics stay .npy: pass their lists on unchanged.  tools/unpack_dataset.py is the inverse.
 Every listed file src becomes <output_root>/<src without its root or drive, suffix .kbf>; a file listed twice is converted once.
 For every list a new one of the same name is written into --list_dir (default: <output_root>/lists), line for line.
 Prints the total bytes before and after.  No GPU is needed."""

@@ -32,6 +32,8 @@ KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames 
 KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_forward launch carries
 KBN_UNPACK_PACKED_MAX_RAW_WIDTH = 16384   # widest packed triplet kbn_unpack_packed_frames_forward takes (its LDS budget)
 KBN_PACK_FRAMES_MAX_WIDTH = 16384   # widest plane row kbn_pack_frames_forward takes (its LDS budget)
+KBN_MAX_CHANNELS, KBN_MAX_WEIGHT_ELEMENTS = 1 << 20, 1 << 28   # the conv layers' common range: past it every size function answers 0
+KBN_MAX_MAP_SIDE, KBN_MAX_SIZE_BYTES = 1 << 24, 1 << 62
 KBN_SUMMARY_CELL_ZERO, KBN_SUMMARY_CELL_COPY, KBN_SUMMARY_CELL_PHOTO_ERR, KBN_SUMMARY_CELL_DEPTH, KBN_SUMMARY_CELL_REL_ERR = 0, 1, 2, 3, 4
 KBN_SUMMARY_COLORMAP_VIRIDIS, KBN_SUMMARY_COLORMAP_INFERNO = 0, 1
 KBN_SUMMARY_MAX_ROWS = 4   # rows of a kbn_summary_panel_forward panel

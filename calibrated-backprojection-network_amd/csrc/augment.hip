@@ -290,13 +290,13 @@ extern "C" {
 
 size_t kbn_augment_workspace_bytes(const kbn_augment_tensor* tensors, int count, int n, int height, int width) {
     if (!tensors || count < 1 || n < 1 || height < 1 || width < 1) return 0;
-    size_t bytes = 0;
+    unsigned __int128 bytes = 0;   // three ints and a count multiply past 64 bits
     for (int i = 0; i < count; ++i) {
         const kbn_augment_tensor& t = tensors[i];
         if (t.role != KBN_AUGMENT_ROLE_RANGE || t.channels < 1) continue;
-        bytes += (size_t)n * (KBN_AUGMENT_WORKSPACE_RECORD_BYTES + 8 * (size_t)t.channels * height * width);   // a record and a candidate list a frame
+        bytes += (unsigned __int128)n * (KBN_AUGMENT_WORKSPACE_RECORD_BYTES + (unsigned __int128)8 * t.channels * height * width);   // a record and a candidate list a frame
     }
-    return bytes;
+    return bytes > KBN_MAX_SIZE_BYTES ? 0 : (size_t)bytes;
 }
 
 int kbn_augment_forward_at(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
@@ -328,7 +328,8 @@ int kbn_augment_forward_at(const kbn_augment_tensor* tensors, int count, const u
     }
     const bool select = ranges > 0 && any_remove;
     if (select && (!densities || !workspace)) return KBN_ERR_INVALID_ARGUMENT;
-    if (select && workspace_bytes < kbn_augment_workspace_bytes(tensors, count, n, height, width)) return KBN_ERR_WORKSPACE;
+    const size_t workspace_need = select ? kbn_augment_workspace_bytes(tensors, count, n, height, width) : 0;
+    if (select && (workspace_need == 0 || workspace_bytes < workspace_need)) return KBN_ERR_WORKSPACE;   // 0: no size_t holds the need
     if (select && (reinterpret_cast<uintptr_t>(workspace) & 7)) return KBN_ERR_INVALID_ARGUMENT;
     if (ranges > 0 && any_noise && noise_type == KBN_AUGMENT_NOISE_NONE) return KBN_ERR_INVALID_ARGUMENT;
 

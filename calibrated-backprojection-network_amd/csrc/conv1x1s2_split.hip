@@ -249,6 +249,7 @@ static size_t c1_panel_bytes(int out_channels, int cin) {
 
 size_t kbn_conv1x1s2_split_packed_weight_bytes(int out_channels, int tensor_channels, int has_xyz) {
     if (out_channels < 1 || tensor_channels < 1 || (tensor_channels % kbn::SP_CK) != 0) return 0;
+    if (!kbn::layer_shape_ok(out_channels, tensor_channels, 1)) return 0;
     return c1_panel_bytes(out_channels, tensor_channels) + (has_xyz ? (size_t)out_channels * 3 * 4 : 0);
 }
 
@@ -308,6 +309,7 @@ int kbn_conv1x1s2_split_forward(const kbn_conv_src* srcs, int n_src, const void*
     // the exponent follows the data when EVERY source brings its slots; otherwise the static act_exponent serves
     if (srcs[0].absmax && (n_src == 1 || srcs[1].absmax)) { p.amax[0] = srcs[0].absmax; p.amax[1] = n_src > 1 ? srcs[1].absmax : nullptr; }
     p.out_amax = out_absmax;
+    if (!layer_shape_ok(out_channels, cin, 1)) return KBN_ERR_UNSUPPORTED;   // the shapes the blob's size function answers 0 for
     p.nTilesN = ceil_div(out_channels, 128);
     p.inv_scale = static_cast<const float*>(packed_weight);
     p.wp = reinterpret_cast<const _Float16*>(p.inv_scale + p.nTilesN * 128);

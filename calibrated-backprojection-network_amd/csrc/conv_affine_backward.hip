@@ -166,7 +166,7 @@ extern "C" int kbn_conv2d_backward_weight(const kbn_conv_src* srcs, int n_src, c
 static bool bd_case_ok(int ks, int stride) { return bw_case_ok(ks, stride); }
 
 extern "C" size_t kbn_conv2d_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size, int stride) {
-    if (out_channels <= 0 || in_channels <= 0 || !bd_case_ok(kernel_size, stride)) return 0;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, kernel_size) || !bd_case_ok(kernel_size, stride)) return 0;
     if (stride == 2) return (long long)out_channels * in_channels > 0x7fffffffLL ? 0 : (size_t)out_channels * in_channels * sizeof(float);
     // the forward conv of grad_out: `in_channels` filters over `out_channels` channels, and its scale and shift vectors
     const size_t blob = kbn_conv2d_affine_packed_weight_bytes(in_channels, out_channels, kernel_size);

@@ -57,6 +57,9 @@ struct BwPlan {
 BwPlan bwd_weight_plan(int n, int oc, int cin, int ks, int stride, int h, int w, int splits) {
     BwPlan pl{};
     if (n <= 0 || oc <= 0 || cin <= 0 || h <= 0 || w <= 0 || ks <= 0 || stride <= 0) return pl;
+    // the ranges of include/kbnet_hip.h, asked before any int arithmetic (ceil_div adds before it divides)
+    if (oc > KBN_MAX_CHANNELS || cin > KBN_MAX_CHANNELS || ks > 7 || stride > 2 || h > KBN_MAX_MAP_SIDE || w > KBN_MAX_MAP_SIDE) return pl;
+    if ((long long)h * w > 0x7fffffffLL) return pl;   // before n x OH x OW, which then fits 64 bits
     pl.OH = ceil_div(h, stride);
     pl.OW = ceil_div(w, stride);
     const long long M = (long long)n * pl.OH * pl.OW;

@@ -432,6 +432,7 @@ int conv2d_launch(const kbn_conv_src* srcs, int n_src, const float* packed_weigh
     }
     for (int s = n_src; s < KBN_MAX_SRC; ++s) p.src[s] = p.src[0];
 
+    if (!layer_shape_ok(out_channels, ctot, kernel_size)) return KBN_ERR_UNSUPPORTED;   // no blob exists for it either
     const ConvPlan pl = make_plan(out_channels, ctot, kernel_size, stride, 0);
     p.nsrc = n_src; p.N = n; p.OC = out_channels; p.Ctot = ctot; p.Cpad = pl.Cpad;
     p.wp = packed_weight; p.out = out; p.out_bstride = out_batch_stride;
@@ -508,6 +509,7 @@ extern "C" {
 size_t kbn_conv2d_packed_weight_bytes(int out_channels, int in_channels, int kernel_size, int stride) {
     if (out_channels < 1 || in_channels < 1 || (kernel_size != 1 && kernel_size != 3)) return 0;
     if (stride != 1 && stride != 2) return 0;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, kernel_size)) return 0;
     kbn::ConvPlan pl = kbn::make_plan(out_channels, in_channels, kernel_size, stride, 0);
     return sizeof(float) * ((size_t)pl.nTilesN * pl.Cpad * kernel_size * kernel_size * pl.NT +
                             (size_t)kbn::wino_packed_floats(out_channels, in_channels, kernel_size, stride));
@@ -517,6 +519,7 @@ int kbn_conv2d_pack_weight(const float* weight, float* packed, int out_channels,
                            int kernel_size, int stride, kbn_stream_t stream) {
     if (!weight || !packed || out_channels < 1 || in_channels < 1) return KBN_ERR_INVALID_ARGUMENT;
     if ((kernel_size != 1 && kernel_size != 3) || (stride != 1 && stride != 2)) return KBN_ERR_UNSUPPORTED;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, kernel_size)) return KBN_ERR_UNSUPPORTED;
     kbn::ConvPlan pl = kbn::make_plan(out_channels, in_channels, kernel_size, stride, 0);
     int taps = kernel_size * kernel_size;
     long long total = (long long)pl.nTilesN * pl.Cpad * taps * pl.NT;
@@ -535,6 +538,7 @@ int kbn_conv2d_query(int n, int out_channels, int in_channels, int kernel_size, 
     if (!info || n < 1 || out_channels < 1 || in_channels < 1 || in_height < 1 || in_width < 1)
         return KBN_ERR_INVALID_ARGUMENT;
     if ((kernel_size != 1 && kernel_size != 3) || (stride != 1 && stride != 2)) return KBN_ERR_UNSUPPORTED;
+    if (!layer_shape_ok(out_channels, in_channels, kernel_size)) return KBN_ERR_UNSUPPORTED;
     const ConvPlan pl = make_plan(out_channels, in_channels, kernel_size, stride, 0);
     const int outH = ceil_div(in_height, stride), outW = ceil_div(in_width, stride);
     TileChoice tc = choose_tile(outH, outW, n, pl.nTilesN, kernel_size, stride, pl.MW, pl.CK, pl.NT);

@@ -244,6 +244,7 @@ size_t kbn_conv3x3_split_packed_weight_bytes(int out_channels, int in_channels, 
     using namespace kbn;
     if (mode == 4) mode = 3;   // the transposed conv runs the folded up-conv's kernels on its own folded weights: same blob layout
     if (out_channels < 1 || in_channels < 1 || (in_channels % SP_CK) != 0 || mode < 0 || mode > 3) return 0;
+    if (!layer_shape_ok(out_channels, in_channels, 3)) return 0;
     const int nt = split_nt(mode, out_channels, in_channels), tiles = ceil_div(out_channels, nt);
     return (size_t)tiles * nt * 4 + (size_t)tiles * (in_channels / SP_CK) * ((mode == 3 ? UF_ITEMS : 9) * 2 * 2 * nt * 16)   // per 16 channels: [set][part][2 k-groups][nt][8] fp16
            + (size_t)(in_channels / SP_CK) * 4;                                                                                  // the bound table of the pair format (split_l1_kernel)
@@ -326,6 +327,7 @@ static int conv3x3_split_impl(const kbn_conv_src* srcs, int n_src, const void* p
     if (srcs[0].absmax && (n_src == 1 || srcs[1].absmax)) { p.amax[0] = srcs[0].absmax; p.amax[1] = n_src > 1 ? srcs[1].absmax : nullptr; }
     else if (p.pair_src && n_src > 1 && srcs[1].absmax) p.amax[1] = srcs[1].absmax;   // the fp32 source beside a pair source: its own window
     p.out_amax = out_absmax;
+    if (!layer_shape_ok(out_channels, cin, 3)) return KBN_ERR_UNSUPPORTED;   // the shapes the blob's size function answers 0 for
     const int ntf = split_nt(mode, out_channels, cin);
     p.nTilesN = ceil_div(out_channels, ntf);
     p.inv_scale = static_cast<const float*>(packed_weight);

@@ -841,7 +841,7 @@ static int up2x_dma_pick(Up2xParams& q, int NB, int half, int t, hipStream_t st)
 extern "C" {
 
 size_t kbn_upconv2x_packed_weight_bytes(int out_channels, int in_channels) {
-    if (out_channels < 1 || in_channels < 1) return 0;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, 3)) return 0;
     kbn::Up2xPlan pl = kbn::make_up2x_plan(out_channels, in_channels);
     size_t floats = 2 * (size_t)pl.nTilesN * pl.Cpad * (8 + 6) * pl.NT;   // 4-phase weights + 3-product weights
     if (kbn::up2x9_eligible(out_channels)) {                               // + 9-product weights
@@ -854,6 +854,7 @@ size_t kbn_upconv2x_packed_weight_bytes(int out_channels, int in_channels) {
 int kbn_upconv2x_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                              kbn_stream_t stream) {
     if (!weight || !packed || out_channels < 1 || in_channels < 1) return KBN_ERR_INVALID_ARGUMENT;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, 3)) return KBN_ERR_UNSUPPORTED;
     kbn::Up2xPlan pl = kbn::make_up2x_plan(out_channels, in_channels);
     long long total = 2LL * pl.nTilesN * pl.Cpad * 8 * pl.NT;
     hipLaunchKernelGGL(kbn::pack_up2x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -881,7 +882,7 @@ static int upconv2x_forward_impl(const float* src, long long src_batch_stride, c
     if (!src || !packed_weight || !out || n < 1 || in_channels < 1 || out_channels < 1 || src_height < 1 ||
         src_width < 1)
         return KBN_ERR_INVALID_ARGUMENT;
-    if (src_height > 16383 || src_width > 16383) return KBN_ERR_UNSUPPORTED;
+    if (src_height > 16383 || src_width > 16383 || !layer_shape_ok(out_channels, in_channels, 3)) return KBN_ERR_UNSUPPORTED;
     const Up2xPlan pl = make_up2x_plan(out_channels, in_channels);
     Up2xParams p;
     p.src = src; p.wp = packed_weight; p.out = out;
@@ -1003,6 +1004,7 @@ int kbn_upconv2x_forward(const float* src, long long src_batch_stride, const flo
 
 int kbn_deconv2x_pack_weight(const float* weight, float* packed, int out_channels, int in_channels, kbn_stream_t stream) {
     if (!weight || !packed || out_channels < 1 || in_channels < 1) return KBN_ERR_INVALID_ARGUMENT;
+    if (!kbn::layer_shape_ok(out_channels, in_channels, 3)) return KBN_ERR_UNSUPPORTED;
     kbn::Up2xPlan pl = kbn::make_up2x_plan(out_channels, in_channels);
     const long long total = 2LL * pl.nTilesN * pl.Cpad * 8 * pl.NT;
     hipLaunchKernelGGL(kbn::pack_up2x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -1030,6 +1032,7 @@ int kbn_upconv2x_query(int n, int in_channels, int out_channels, int src_height,
     using namespace kbn;
     if (!info || n < 1 || in_channels < 1 || out_channels < 1 || src_height < 1 || src_width < 1)
         return KBN_ERR_INVALID_ARGUMENT;
+    if (!layer_shape_ok(out_channels, in_channels, 3)) return KBN_ERR_UNSUPPORTED;
     const Up2xPlan pl = make_up2x_plan(out_channels, in_channels);
     const bool chunks_ok = (pl.Cpad / 8) % 2 == 0 && in_channels == pl.Cpad;
     const bool aligned = (src_width & 3) == 0 && chunks_ok;   // plus 16-byte aligned planes, which torch tensors are

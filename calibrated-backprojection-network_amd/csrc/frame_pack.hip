@@ -188,7 +188,8 @@ extern "C" size_t kbn_frame_encode_bound(int width, int height, int channels, in
     fill_layout(L, width, height, channels, bits);
     // a header byte a segment, and no segment takes more than its samples do raw
     const uint64_t row = L.segments + ((uint64_t)width * bits + 7) / 8 + L.segments;
-    return (size_t)(L.start + row * (uint64_t)height * channels);
+    const unsigned __int128 bound = (unsigned __int128)row * (uint64_t)height * channels + L.start;   // past 64 bits for sides near 2^31
+    return bound > KBN_MAX_SIZE_BYTES ? 0 : (size_t)bound;
 }
 
 extern "C" int kbn_frame_encode(const void* samples, int width, int height, int channels, int bits, unsigned char* out,
@@ -198,6 +199,7 @@ extern "C" int kbn_frame_encode(const void* samples, int width, int height, int 
     if (width < 1 || height < 1) return KBN_ERR_INVALID_ARGUMENT;
     if (!geometry_ok(width, height, channels, bits)) return KBN_ERR_UNSUPPORTED;
     const size_t bound = kbn_frame_encode_bound(width, height, channels, bits);
+    if (bound == 0) return KBN_ERR_UNSUPPORTED;              // no size_t holds it: 0 is a refusal, not "any capacity will do"
     if (out_capacity < bound) return KBN_ERR_WORKSPACE;
     if (bound > 0xffffffffull) return KBN_ERR_UNSUPPORTED;   // the table's offsets are 32-bit
     Layout L;

@@ -22,6 +22,14 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+// HOST: the layer shapes the plan makers and size functions take (include/kbnet_hip.h states them).  ceil_div and round_up work in
+// int, a + b - 1 included, and so do the plans built from them: every size function and every entry point that makes a plan asks
+// this first and answers 0 / KBN_ERR_UNSUPPORTED outside it, so that no plan is ever made from a count near INT_MAX.
+inline bool layer_shape_ok(int out_channels, int in_channels, int kernel_size) {
+    return out_channels >= 1 && in_channels >= 1 && kernel_size >= 1 && kernel_size <= 7 && out_channels <= KBN_MAX_CHANNELS &&
+           in_channels <= KBN_MAX_CHANNELS &&
+           (long long)out_channels * in_channels * kernel_size * kernel_size <= (long long)KBN_MAX_WEIGHT_ELEMENTS;
+}
 
 __device__ __forceinline__ float leaky_relu(float v, float slope) { return v > 0.f ? v : v * slope; }
 // |v| for the running maxima behind the fp16 windows (absmax slots, per-tile maxima): 0 for Inf and NaN

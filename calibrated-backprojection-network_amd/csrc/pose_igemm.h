@@ -44,9 +44,10 @@ inline int check_tensor_srcs(const kbn_conv_src* srcs, int n_src, int n, int h, 
     return KBN_OK;
 }
 
-// Bytes of a weight of `cols` GEMM columns and K rows packed as [n-tile][K chunk][kc][16 NB]; 0: K too large
+// Bytes of a weight of `cols` GEMM columns and K rows packed as [n-tile][K chunk][kc][16 NB]; 0: outside the common range of
+// include/kbnet_hip.h (columns, K, or their product, the weight's elements)
 inline size_t pose_igemm_packed_bytes(int cols, long long K, int kc) {
-    if (K > (1 << 24)) return 0;
+    if (cols < 1 || K < 1 || cols > KBN_MAX_CHANNELS || K > (1 << 24) || cols * K > (long long)KBN_MAX_WEIGHT_ELEMENTS) return 0;
     const int nb = pose_igemm_nb(cols);
     return (size_t)((long long)ceil_div(cols, 16 * nb) * round_up((int)K, kc) * (16 * nb)) * sizeof(float);
 }

@@ -273,6 +273,7 @@ extern "C" int kbn_conv2d_s2_affine_forward(const kbn_conv_src* srcs, int n_src,
     p.W = in_width;
     p.M = (int)M;
     p.K = (int)K;
+    if (pose_igemm_packed_bytes(out_channels, K, S2_KC) == 0) return KBN_ERR_UNSUPPORTED;   // no blob exists for this shape
     p.nchunks = ceil_div((int)K, S2_KC);
     p.act = apply_activation ? 1 : 0;
     p.slope = negative_slope;

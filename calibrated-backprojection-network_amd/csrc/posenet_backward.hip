@@ -334,6 +334,7 @@ extern "C" int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad
     p.W = in_width;
     p.M = (int)M;
     p.K = (int)K;
+    if (pose_igemm_packed_bytes(p.Ctot, K, BD_KC) == 0) return KBN_ERR_UNSUPPORTED;   // no blob exists for this shape
     p.nchunks = ceil_div((int)K, BD_KC);
     const int nb = pose_igemm_nb(p.Ctot);
     const unsigned ntn = (unsigned)ceil_div(p.Ctot, 16 * nb);

@@ -558,7 +558,10 @@ def pack_upconv2x_weight(weight: torch.Tensor, out: Optional[torch.Tensor] = Non
     if (kh, kw) != (3, 3):
         raise KbnError("upconv2x needs a 3x3 weight")
     pack = lib.kbn_deconv2x_pack_weight if transposed else lib.kbn_upconv2x_pack_weight
-    return _pack_into(out, lib.kbn_upconv2x_packed_weight_bytes(oc, cin), w, lambda p: pack(w.data_ptr(), p, oc, cin, _stream()),
+    nbytes = lib.kbn_upconv2x_packed_weight_bytes(oc, cin)
+    if nbytes == 0:      # a refusal, not "an empty blob"
+        raise KbnError(f"unsupported up-conv weight shape {tuple(w.shape)}")
+    return _pack_into(out, nbytes, w, lambda p: pack(w.data_ptr(), p, oc, cin, _stream()),
                       "kbn_deconv2x_pack_weight" if transposed else "kbn_upconv2x_pack_weight")
 
 
@@ -1346,7 +1349,10 @@ def pack_frames_stride(height: int, width: int, channels: int, bits: int) -> int
 def pack_frames_workspace_bytes(n: int, height: int, width: int, channels: int, bits: int) -> int:
     """Device bytes pack_frames needs as `workspace` for n such frames (kbn_pack_frames_workspace_bytes)."""
     pack_frames_stride(height, width, channels, bits)
-    return int(_lib.load().kbn_pack_frames_workspace_bytes(int(n), int(width), int(height), int(channels), int(bits)))
+    need = int(_lib.load().kbn_pack_frames_workspace_bytes(int(n), int(width), int(height), int(channels), int(bits)))
+    if need == 0:      # a refusal, not "no workspace"
+        raise KbnError(f"pack_frames: no workspace for {n} frames")
+    return need
 
 
 @_on_tensor_device
@@ -1399,6 +1405,8 @@ def pack_frames(samples, bits=None, out=None, out_bytes=None, workspace=None):
         raise KbnError(f"{fn}: out_bytes: expected a contiguous int64 tensor of {n} on {device}")
     lib = _lib.load()
     need = int(lib.kbn_pack_frames_workspace_bytes(n, w, h, c, want_bits))
+    if need == 0:      # a refusal, not "no workspace"
+        raise KbnError(f"{fn}: no workspace for {n} frames of {h} x {w} x {c} samples")
     if workspace is None:
         workspace = torch.empty((need,), device=device, dtype=torch.uint8)
     elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != device or workspace.dtype != torch.uint8
@@ -3149,7 +3157,10 @@ def augment(images: Sequence[torch.Tensor], range_maps: Sequence[torch.Tensor], 
     table = (_lib.AugmentTensor * used).from_buffer(records)
     workspace = None
     if any_remove:      # a 16-byte record and a list of 8 bytes an element for every frame of every range map
-        workspace = torch.empty(lib.kbn_augment_workspace_bytes(table, used, n, h, w) // 8, device=device, dtype=torch.int64)
+        need = lib.kbn_augment_workspace_bytes(table, used, n, h, w)
+        if need == 0 and lists[_lib.KBN_AUGMENT_ROLE_RANGE]:      # a refusal; without range maps there is nothing to select from
+            raise KbnError(f"{fn}: no workspace for {n} frames of {h} x {w} range maps")
+        workspace = torch.empty(need // 8, device=device, dtype=torch.int64)
     with torch.cuda.device(device):
         stream = _stream()
 

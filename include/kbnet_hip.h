@@ -174,8 +174,24 @@ int kbn_absmax_frames(const float* x, long long batch_stride, int n, long long p
 #define KBN_RESIZE_NONE 0
 #define KBN_RESIZE_NEAREST 1
 
+/* ----------------------------------------------- the size functions and their argument ranges --
+ * Every size_t-returning function of this header is pure host arithmetic (no launch, no device pointer followed), takes any int
+ * and answers 0 for what its kernels do not support: a dimension <= 0, a kernel size, stride, mode, channel count or bit width that
+ * is not one of the legal ones named beside it, or a shape past the common range below.  A caller allocates what a NONZERO answer
+ * says and treats 0 as a refusal, never as "allocate nothing"; the pack and forward entry points refuse the same shapes
+ * (KBN_ERR_UNSUPPORTED or KBN_ERR_INVALID_ARGUMENT).  tests/host_san/size_sweep.cpp sweeps them all over extreme arguments
+ * in a sanitizer build.
+ * The common range of the conv layers: 1 <= out_channels, in_channels <= KBN_MAX_CHANNELS and out_channels x in_channels x k x k
+ * <= KBN_MAX_WEIGHT_ELEMENTS (1 GiB of fp32 OIHW weights); the plans behind the kernels are computed in int. */
+#define KBN_MAX_CHANNELS 1048576
+#define KBN_MAX_WEIGHT_ELEMENTS 268435456
+/* A map side the weight-gradient scratch functions take (its pixels must also fit an int), and the largest answer any size
+ * function gives: a product of the arguments past it is answered with 0, not with its low 64 bits. */
+#define KBN_MAX_MAP_SIDE 16777216
+#define KBN_MAX_SIZE_BYTES ((size_t)1 << 62)
+
 /* Bytes of the packed weight blob for a conv with these dimensions (0 if unsupported).  The
- * blob layout depends on the stride the weight will be used with. */
+ * blob layout depends on the stride the weight will be used with.  kernel_size 1 or 3, stride 1 or 2, channels in the common range. */
 size_t kbn_conv2d_packed_weight_bytes(int out_channels, int in_channels, int kernel_size, int stride);
 
 /* Re-orders an OIHW weight (out_channels x in_channels x k x k) into the MFMA
@@ -227,6 +243,7 @@ int kbn_scale_planes_forward(const float* x, long long x_batch_stride, const flo
  *   packed_weight from kbn_upconv2x_pack_weight (OIHW 3x3 weight in; the blob holds the 4-phase,
  *   the 3-product and, for <= 16 or a multiple of 32 filters, the 9-product weights back to back).
  * Other target sizes go through kbn_conv2d_forward(..., KBN_RESIZE_NEAREST). */
+/* range: channels in the common range (kernel 3 x 3); 0 otherwise */
 size_t kbn_upconv2x_packed_weight_bytes(int out_channels, int in_channels);
 int kbn_upconv2x_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                              kbn_stream_t stream);
@@ -293,6 +310,7 @@ int kbn_deconv2x_forward(const float* src, long long src_batch_stride, const flo
  *   out       N x out_channels x height x width fp32, frames out_batch_stride elements apart
  * Modes 1 and 3 return KBN_ERR_UNSUPPORTED unless width % 4 == 0 and `out` is 16-byte aligned (callers fall back
  * to kbn_upconv2x_forward); modes 0 and 2 store element-wise in that case.  KBN_NO_SPLIT=1: always unsupported. */
+/* range: mode 0 .. 4, in_channels % 16 == 0, channels in the common range; 0 otherwise */
 size_t kbn_conv3x3_split_packed_weight_bytes(int out_channels, int in_channels, int mode);
 int kbn_conv3x3_split_pack_weight(const float* weight, void* packed, int out_channels, int in_channels, int mode,
                                   kbn_stream_t stream);
@@ -325,6 +343,7 @@ int kbn_conv3x3_split_forward_ksplit(const kbn_conv_src* srcs, int n_src, const 
  *   packed    kbn_conv1x1s2_split_packed_weight_bytes(out_channels, tensor_channels, has_xyz) bytes
  *   xyz       N x 3 x height x width fp32 (output size), frames xyz_batch_stride apart; null iff packed without xyz
  *   out       N x out_channels x height x width, height = ceil(H / 2), width = ceil(W / 2) */
+/* range: tensor_channels % 16 == 0, channels in the common range; 0 otherwise */
 size_t kbn_conv1x1s2_split_packed_weight_bytes(int out_channels, int tensor_channels, int has_xyz);
 int kbn_conv1x1s2_split_pack_weight(const float* weight, void* packed, int out_channels, int in_channels, int xyz_offset,
                                     kbn_stream_t stream);
@@ -395,6 +414,7 @@ int kbn_kb_block_forward(const float* image, long long image_batch_stride, const
  *   out_image/fused N x kb_filters x ceil(H/2) x ceil(W/2) each, with their own batch strides and absmax slots
  * KBN_ERR_UNSUPPORTED unless conv0_filters == kb_filters == 48 (KBNet's level 0 in all three presets) -- the caller then
  * runs kbn_conv2d_forward + kbn_kb_block_forward. */
+/* range: image_channels 1 .. 4, both filter counts 48; 0 otherwise */
 size_t kbn_kb1_front_packed_weight_bytes(int image_channels, int conv0_filters, int kb_filters);
 /* KBN_OK when kbn_kb1_front_forward would take this problem, KBN_ERR_UNSUPPORTED otherwise (widths, map size, slope outside
  * [0, 1], KBN_NO_SPLIT): lets a caller decide BEFORE it launches the depth branch whose xyz output the kernel consumes. */
@@ -422,6 +442,7 @@ int kbn_kb1_front_forward(const float* image, long long image_batch_stride, cons
  *   out_next_fused  N x next_filters x h2 x w2, frames out_next_fused_batch_stride apart; out_next_fused_absmax its slot (or NULL)
  * KBN_ERR_UNSUPPORTED (kbn_kb1_front_next_query tells beforehand) unless kb_filters == 48 and next_filters == 96 -- KBNet's levels 0 / 1
  * in all presets -- or with KBN_NO_FRONT_NEXT=1: the caller then runs kbn_kb1_front_forward and the next block's conv_fused on its own. */
+/* range: (48, 48, 96) only; 0 otherwise */
 size_t kbn_kb1_front_next_packed_weight_bytes(int image_channels, int fused_channels, int filters);
 int kbn_kb1_front_next_pack_weight(const float* w_conv_fused, void* packed, int image_channels, int fused_channels, int filters,
                                    kbn_stream_t stream);
@@ -447,6 +468,7 @@ int kbn_kb1_front_next_forward(const float* image, long long image_batch_stride,
  *   out_depth       N x 16 x ceil(H/2) x ceil(W/2) (frames out_depth_batch_stride apart), out_depth_absmax its slot (or NULL)
  *   xyz             N x 3 x ceil(H/2) x ceil(W/2): what kbn_kb1_front_forward / kbn_conv1x1s2_split_forward take
  * KBN_ERR_UNSUPPORTED unless conv0_filters == kb_filters == 16. */
+/* range: depth_channels 1 .. 8, both filter counts 16; 0 otherwise */
 size_t kbn_kb1_depth_front_packed_weight_bytes(int depth_channels, int conv0_filters, int kb_filters);
 int kbn_kb1_depth_front_query(int depth_channels, int conv0_filters, int kb_filters, int height, int width, float conv0_negative_slope);
 int kbn_kb1_depth_front_pack_weight(const float* w_conv0, const float* w_conv_depth, const float* w_proj, void* packed,
@@ -471,6 +493,7 @@ int kbn_kb1_depth_front_forward(const float* depth, long long depth_batch_stride
  * KBN_ERR_UNSUPPORTED (kbn_s2d_depth_front_query says so beforehand) for any other pool list, input_channels != 2, n_convolution != 3,
  * n_filter != 8, slopes outside [0, 1], under KBN_NO_DEPTH_FRONT_FUSION=1 or KBN_NO_SPLIT=1, and wherever kbn_kb1_depth_front_forward
  * declines: the caller runs kbn_s2d_forward + kbn_kb1_depth_front_forward. */
+/* range: n_pools 1 .. 8; 0 otherwise */
 size_t kbn_s2d_depth_front_packed_weight_bytes(int n_pools);
 int kbn_s2d_depth_front_pack_weight(const float* w_pool_conv0, const float* w_pool_conv1, const float* w_pool_conv2, const float* w_conv,
                                     void* packed, int n_pools, kbn_stream_t stream);
@@ -510,6 +533,7 @@ int kbn_conv_head_forward(const float* x, long long x_batch_stride, const float*
  * accuracy class, same parity gate): on the fp32 MFMAs that conv was what bound kbn_conv_head_forward.  packed_w_conv from
  * kbn_conv_tail_pack_weight (raw channels x channels x 3 x 3 weight in); w_out raw.  No alignment requirements.
  * KBN_ERR_UNSUPPORTED for channels > 12 (the caller runs kbn_conv_head_forward or the two-launch path). */
+/* range: channels 1 .. 16; 0 otherwise */
 size_t kbn_conv_tail_packed_weight_bytes(int channels);
 int kbn_conv_tail_pack_weight(const float* w_conv, void* packed, int channels, kbn_stream_t stream);
 int kbn_conv_tail_forward(const float* x, long long x_batch_stride, const void* packed_w_conv, const float* w_out, float* depth,
@@ -616,6 +640,7 @@ int kbn_photometric_loss_backward(const float* image0, const float* image1, cons
  * eval mode is scale = g / sqrt(var + eps), shift = b - mean * scale; the scale is applied to the finished sum, not folded
  * into the weights.  out: out_channels x ceil(in_h / 2) x ceil(in_w / 2) per frame, frames out_batch_stride elements apart.
  * Every output pixel is a function of its frame and the weights alone. */
+/* range: kernel_size 3, 5 or 7, channels in the common range, in_channels x k x k <= 2^24; 0 otherwise */
 size_t kbn_conv2d_s2_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
 int kbn_conv2d_s2_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                                      int kernel_size, kbn_stream_t stream);
@@ -650,6 +675,7 @@ int kbn_pose_head_forward(const float* latent, long long latent_batch_stride, co
  *   output pixels is split over `splits` workgroups per tile (<= 0: chosen from the shape alone, not from the device), whose
  *   partial sums go to `scratch` (kbn_conv2d_s2_backward_weight_scratch_bytes(..., splits) bytes; 0 bytes, and scratch may be
  *   NULL, when one split remains) and are added in split order by a second launch.  grad_weight is plain OIHW. */
+/* range: kernel_size 3, 5 or 7, channels in the common range, out_channels x k x k <= 2^24; 0 otherwise */
 size_t kbn_conv2d_s2_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
 int kbn_conv2d_s2_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                                             int kernel_size, kbn_stream_t stream);
@@ -657,6 +683,7 @@ int kbn_conv2d_s2_backward_data(const float* grad_out, long long grad_out_batch_
                                 float* grad_in0, long long grad_in0_batch_stride, int channels0, float* grad_in1,
                                 long long grad_in1_batch_stride, int channels1, int n, int out_channels, int kernel_size,
                                 int in_height, int in_width, kbn_stream_t stream);
+/* range: kernel_size 3, 5 or 7; n, sides >= 1, sides <= KBN_MAX_MAP_SIDE, height x width and n x output pixels below 2^31, channels in the common range, in_channels x k x k <= 2^24, the weight below 2^31 elements; splits <= 0 lets the library choose.  0 otherwise, and 0 when the gradient is not split (no scratch needed): kbn_conv2d_s2_backward_weight tells the two apart */
 size_t kbn_conv2d_s2_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size, int in_height,
                                                    int in_width, int splits);
 int kbn_conv2d_s2_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out, long long grad_out_batch_stride,
@@ -725,6 +752,7 @@ int kbn_bn_act_backward_sync_apply(const float* u, long long u_batch_stride, con
  * kbn_conv2d_s2_affine_forward: one or two KBN_SRC_TENSOR sources, any channel counts, taps outside the image zero, scale
  * applied to the finished sum (the projection passes scale 1, shift 0), every output pixel a function of its frame and the
  * weights alone.  The packed weight is this entry's own (another K chunk than kbn_conv2d_s2_affine_pack_weight's). */
+/* range: kernel_size 1, 3 or 7, channels in the common range, in_channels x k x k <= 2^24; 0 otherwise */
 size_t kbn_conv2d_affine_packed_weight_bytes(int out_channels, int in_channels, int kernel_size);
 int kbn_conv2d_affine_pack_weight(const float* weight, float* packed, int out_channels, int in_channels,
                                   int kernel_size, kbn_stream_t stream);
@@ -752,11 +780,13 @@ int kbn_maxpool3x3s2_forward(const float* in, long long in_batch_stride, float* 
  *   At stride 1 this is kbn_conv2d_affine_forward over grad_out with the weight transposed and its taps flipped -- what
  *   kbn_conv2d_backward_data_pack_weight writes, with the unit scale and zero shift behind it; at (1, 2) one launch of its own
  *   writes W^T grad_out to the even-even pixels and zeros to the rest (the blob is the weight itself). */
+/* range: as kbn_conv2d_s2_backward_weight_scratch_bytes, with (kernel_size, stride) (3, 1), (1, 1) or (1, 2) */
 size_t kbn_conv2d_backward_weight_scratch_bytes(int n, int out_channels, int in_channels, int kernel_size, int stride, int in_height,
                                                 int in_width, int splits);
 int kbn_conv2d_backward_weight(const kbn_conv_src* srcs, int n_src, const float* grad_out, long long grad_out_batch_stride,
                                float* grad_weight, int n, int out_channels, int kernel_size, int stride, int in_height,
                                int in_width, int splits, float* scratch, size_t scratch_bytes, kbn_stream_t stream);
+/* range: (kernel_size, stride) (3, 1), (1, 1) or (1, 2), channels in the common range; 0 otherwise */
 size_t kbn_conv2d_backward_data_packed_weight_bytes(int out_channels, int in_channels, int kernel_size, int stride);
 int kbn_conv2d_backward_data_pack_weight(const float* weight, float* packed, int out_channels, int in_channels, int kernel_size,
                                          int stride, kbn_stream_t stream);
@@ -922,6 +952,8 @@ typedef struct kbn_augment_tensor {
     int map_index; /* range maps: the map's index among the call's range maps (a word of the random counter) */
     int reserved;
 } kbn_augment_tensor;
+/* range: tensors non-NULL, count, n, height, width >= 1, a need of at most KBN_MAX_SIZE_BYTES; 0 otherwise, and 0 when no record is a
+ * range map (nothing to select from).  kbn_augment_forward refuses a selection whose need is 0. */
 size_t kbn_augment_workspace_bytes(const kbn_augment_tensor* tensors, int count, int n, int height, int width); /* 0 for bad arguments */
 int kbn_augment_forward(const kbn_augment_tensor* tensors, int count, const unsigned char* flags, int n, int height, int width,
                         const float* densities, void* workspace, size_t workspace_bytes, int normalization, int noise_type,
@@ -1014,6 +1046,7 @@ int kbn_png_decode_batch(const unsigned char* const* files, const size_t* file_b
  *                              height), else KBN_ERR_WORKSPACE.  Thread-safe, no GPU work: a pool of host threads writes a batch.
  * Readers (kbn_png_decode, PIL) recover the samples bit for bit; the file's bytes are not PIL's (other filters). */
 int kbn_depth_to_u16_forward(const float* depth, unsigned short* samples, long long count, kbn_stream_t stream);
+/* range: sides >= 1 and (1 + 2 width) x height < 2^32 (zlib counts in 32 bits); 0 otherwise */
 size_t kbn_png_encode_gray16_bound(int width, int height);
 int kbn_png_encode_gray16(const unsigned short* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                           size_t* out_bytes, int level);
@@ -1037,11 +1070,13 @@ int kbn_png_encode_gray16(const unsigned short* pixels, int width, int height, u
 int kbn_export_pack_forward(const float* image, float scale, float shift, const float* depth_a, const float* depth_b,
                             unsigned char* rgb, unsigned short* samples_a, unsigned short* samples_b, int n, int height, int width,
                             kbn_stream_t stream);
+/* range: sides >= 1 and (1 + 3 width) x height < 2^32; 0 otherwise */
 size_t kbn_png_encode_rgb8_bound(int width, int height);
 int kbn_png_encode_rgb8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                         size_t* out_bytes, int level);
 /* HOST: height x width uint8 -> an 8-bit grayscale PNG, under kbn_png_encode_rgb8's contract (tools/unpack_dataset.py writes a
  * one-plane packed frame of 8 bits with it). */
+/* range: sides >= 1 and (1 + width) x height < 2^32; 0 otherwise */
 size_t kbn_png_encode_gray8_bound(int width, int height);
 int kbn_png_encode_gray8(const unsigned char* pixels, int width, int height, unsigned char* out, size_t out_capacity,
                          size_t* out_bytes, int level);
@@ -1106,6 +1141,7 @@ int kbn_unpack_train_frames_forward(const unsigned char* images, size_t image_by
  * KBN_ERR_INVALID_ARGUMENT: NULL pointers, sizes < 1, a damaged or truncated file, a short output; KBN_ERR_UNSUPPORTED: other
  * channels / bits / version constants, an image whose encoding could pass 4 GiB (the table's offsets are 32-bit). */
 int kbn_frame_info(const unsigned char* file, size_t file_bytes, int* width, int* height, int* channels, int* bits);
+/* range: sides >= 1, channels 1, 3 or 4, bits 8 or 16, a bound of at most KBN_MAX_SIZE_BYTES; 0 otherwise.  kbn_frame_encode itself takes frames whose bound is below 4 GiB */
 size_t kbn_frame_encode_bound(int width, int height, int channels, int bits);
 int kbn_frame_encode(const void* samples, int width, int height, int channels, int bits, unsigned char* out, size_t out_capacity,
                      size_t* out_bytes);
@@ -1160,7 +1196,9 @@ int kbn_unpack_packed_frames_forward(const unsigned char* images, size_t image_b
  * 8.2 KB image it assembles the payload in -- 40.2 KB of the 64 KB a workgroup gets without opting in to more (the decoder's
  * KBN_UNPACK_PACKED_MAX_RAW_WIDTH is the same budget). */
 #define KBN_PACK_FRAMES_MAX_WIDTH 16384
+/* range: kbn_frame_encode_bound's range, width <= KBN_PACK_FRAMES_MAX_WIDTH, a bound below 4 GiB; 0 otherwise */
 size_t kbn_pack_frames_stride(int width, int height, int channels, int bits);
+/* range: n >= 1 and kbn_pack_frames_stride's range; 0 otherwise */
 size_t kbn_pack_frames_workspace_bytes(int n, int width, int height, int channels, int bits);
 int kbn_pack_frames_forward(const void* samples, int n, int width, int height, int channels, int bits, unsigned char* out,
                             size_t out_stride, unsigned long long* out_bytes, void* workspace, size_t workspace_bytes,

@@ -72,6 +72,139 @@ def encode(samples):
     return head + b"\0" * (start - len(head)) + payload
 
 
+def _segment_bytes(n, b, bits, left):
+    """Bytes of a segment's fields (frame_pack.h): a left row stores its first sample raw and n - 1 fields, an up row n fields."""
+    return ((bits + (n - 1) * b if left else n * b) + 7) // 8
+
+
+def _assemble(w, h, c, bits, parts):
+    """The file around the (group, plane) payloads `parts` [(header bytes, field bytes)] in table order."""
+    groups, _, start = _layout(w, h, c)
+    assert len(parts) == groups * c
+    table, payload = [], b""
+    for heads, data in parts:
+        table.append(len(payload))
+        payload += heads + data
+    table.append(len(payload))
+    header = MAGIC + struct.pack("<IIHHHHQ", w, h, c, bits, ROWS, SEG, len(payload))
+    head = header + struct.pack(f"<{len(table)}I", *table)
+    return head + b"\0" * (start - len(head)) + payload
+
+
+def build(samples, widths=None, pad=None):
+    """A file of `samples` that need not be the canonical one: the header byte of segment (group, plane, row in group, k) is
+    widths(group, plane, row, k, needed, bits) clipped to [needed, bits] (`needed`: what encode() writes), and the bits between the
+    last field and the segment's end are the low bits of pad(group, plane, row, k, count).  With both None: encode(samples)."""
+    a = np.asarray(samples)
+    bits = 8 * a.dtype.itemsize
+    assert a.dtype in (np.uint8, np.uint16)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    h, w, c = a.shape
+    groups, segments, _ = _layout(w, h, c)
+    a = a.astype(np.int64)
+    parts = []
+    for g in range(groups):
+        for plane in range(c):
+            heads, data = b"", b""
+            for y in range(g * ROWS, min(h, (g + 1) * ROWS)):
+                r = y - g * ROWS
+                for k in range(segments):
+                    xs = range(k * SEG, min(w, (k + 1) * SEG))
+                    if r == 0:
+                        z = [_zigzag(_signed(int(a[y, x, plane] - a[y, x - 1, plane]), bits)) for x in xs[1:]]
+                        raw = [(int(a[y, xs[0], plane]), bits)]
+                    else:
+                        z = [_zigzag(_signed(int(a[y, x, plane] - a[y - 1, x, plane]), bits)) for x in xs]
+                        raw = []
+                    needed = max(z).bit_length() if z else 0
+                    b = needed if widths is None else min(bits, max(needed, int(widths(g, plane, r, k, needed, bits))))
+                    fields = raw + [(v, b) for v in z]
+                    used = sum(width for _, width in fields)
+                    spare = -used % 8
+                    if pad is not None and spare:
+                        fields.append((int(pad(g, plane, r, k, spare)) & ((1 << spare) - 1), spare))
+                    heads += bytes([b])
+                    data += _pack_fields(fields)
+                    assert len(_pack_fields(fields)) == _segment_bytes(len(xs), b, bits, r == 0)
+            parts.append((heads, data))
+    out = _assemble(w, h, c, bits, parts)
+    if widths is None and pad is None:
+        assert out == encode(samples)
+    return out
+
+
+def build_random(w, h, c, bits, rng):
+    """A file nobody encoded: every header byte uniform in [0, bits], every field and pad bit random, the table from the segments'
+    sizes.  Returns (file, samples): the samples are what decode() makes of it."""
+    groups, segments, _ = _layout(w, h, c)
+    parts = []
+    for g in range(groups):
+        rows = min(ROWS, h - g * ROWS)
+        for _ in range(c):
+            heads = bytes(int(v) for v in rng.integers(0, bits + 1, size=rows * segments))
+            size = sum(_segment_bytes(min(SEG, w - k * SEG), heads[r * segments + k], bits, r == 0)
+                       for r in range(rows) for k in range(segments))
+            parts.append((heads, bytes(int(v) for v in rng.integers(0, 256, size=size))))
+    data = _assemble(w, h, c, bits, parts)
+    return data, decode(data)
+
+
+WIDTH_CHOICES = ("all_bits", "needed_plus_1", "random", "build_random")
+
+
+def hand_made(choice, w, h, c, bits, seed=0):
+    """(file, samples) of a hand-made file that is not the canonical encoding of its samples, by one of WIDTH_CHOICES: every b = bits;
+    b = needed + 1 with every pad bit set; the first b = needed + 1, the others random in [needed, bits], random pad bits;
+    build_random.  The samples of the first three are noise / 16: at most bits - 3 bits a field, so there is room above."""
+    assert choice in WIDTH_CHOICES
+    for attempt in range(10):
+        g = np.random.Generator(np.random.Philox(977 * seed + 31 * w + h + 7 * c + bits + 1000 * attempt))
+        if choice == "build_random":
+            data, a = build_random(w, h, c, bits, g)
+        else:
+            a = (g.integers(0, 1 << bits, size=(h, w, c)) // 16).astype(np.uint16 if bits == 16 else np.uint8)
+            a = a[:, :, 0] if c == 1 else a
+            first = []
+
+            def widths(group, plane, row, k, needed, top):
+                if choice == "all_bits":
+                    return top
+                if choice == "needed_plus_1" or not first:
+                    first.append(1)
+                    return needed + 1
+                return int(g.integers(needed, top + 1))
+
+            pad = {"all_bits": None, "needed_plus_1": lambda *_: 0xff, "random": lambda *_: int(g.integers(0, 256))}[choice]
+            data = build(a, widths, pad)
+        if data != encode(a):
+            return data, a
+    raise AssertionError("no non-canonical file in ten draws")
+
+
+def segments_of(data):
+    """[(b, needed, pad bits as an int)] of every segment of a file, read back from its bytes: `needed` is the width of the largest
+    field the segment holds."""
+    w, h, c, bits, _ = info(data)
+    groups, segments, start = _layout(w, h, c)
+    table = struct.unpack(f"<{groups * c + 1}I", data[32:32 + 4 * (groups * c + 1)])
+    out = []
+    for e in range(groups * c):
+        part = data[start + table[e]:start + table[e + 1]]
+        rows = min(ROWS, h - e // c * ROWS)
+        at = rows * segments
+        for r in range(rows):
+            for k in range(segments):
+                n, b = min(SEG, w - k * SEG), part[r * segments + k]
+                size = _segment_bytes(n, b, bits, r == 0)
+                value = int.from_bytes(part[at:at + size], "little")
+                used = (bits + (n - 1) * b) if r == 0 else n * b
+                fields = [(value >> ((bits if r == 0 else 0) + i * b)) & ((1 << b) - 1) for i in range(n - 1 if r == 0 else n)]
+                out.append((b, max(fields).bit_length() if fields else 0, value >> used))
+                at += size
+    return out
+
+
 def info(data):
     assert data[:8] == MAGIC
     w, h, c, bits, rows, seg, payload_bytes = struct.unpack("<IIHHHHQ", data[8:32])

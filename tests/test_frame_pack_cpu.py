@@ -108,6 +108,58 @@ def test_committed_version_1_files_decode():
         assert kb.loader.encode_frame(want) == data
 
 
+# ----------------------------------------------------------------------------- files no encoder of ours writes
+# Version 1 allows a header byte wider than its segment needs (up to `bits`), nonzero pad bits, and any b on a one-sample left-row
+# segment.  The format, not the encoder, is the contract: whatever kbn_frame_check accepts decodes alike everywhere.
+WIDTH_CHOICES = orc.WIDTH_CHOICES
+noncanonical = orc.hand_made
+
+
+@pytest.mark.parametrize("bits", [8, 16])
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_hand_made_files_decode_like_the_oracle(size, c, bits):
+    w, h = size
+    for choice in WIDTH_CHOICES:
+        data, a = noncanonical(choice, w, h, c, bits)
+        kb.loader.check_frame(data)                                        # the library accepts it
+        assert kb.loader.frame_info(data) == (w, h, c, bits)
+        got = kb.loader.decode_frame(data)
+        assert got.dtype == a.dtype and got.shape == a.shape
+        assert np.array_equal(got, orc.decode(data)), choice               # library == NumPy
+        assert np.array_equal(got, a), choice                              # == the samples it was built from (build_random: the oracle's)
+        assert data != kb.loader.encode_frame(a), choice                   # and it is not what the encoder writes
+        segments = orc.segments_of(data)                                   # read back from the bytes
+        assert all(b >= needed for b, needed, _ in segments)
+        wide, padded = sum(b > needed for b, needed, _ in segments), sum(pad != 0 for _, _, pad in segments)
+        # every file of the first three choices has a header byte above its need (their samples leave room: noise / 16); a file of
+        # build_random is non-canonical by a wide byte or by a pad bit (its random fields may happen to need every b)
+        assert wide > 0 if choice != "build_random" else wide + padded > 0, choice
+        # ... and a nonzero pad bit where the choice sets them and the file has any: every b = bits makes whole bytes, and so does
+        # a file whose segments are all one-sample left-row segments (`bits` bits each)
+        has_pad_bits = any((b * (n if up else n - 1)) % 8 for b, n, up in _segment_shapes(data))
+        if choice in ("needed_plus_1", "random") and has_pad_bits:
+            assert padded > 0, choice
+
+
+def _segment_shapes(data):
+    """(b, samples, is an up row) of every segment of a file, in file order."""
+    w, h, c, _ = kb.loader.frame_info(data)
+    heads = iter(b for b, _, _ in orc.segments_of(data))
+    for group in range(-(-h // 8)):
+        for _ in range(c):
+            for row in range(min(8, h - 8 * group)):
+                for k in range(-(-w // 16)):
+                    yield next(heads), min(16, w - 16 * k), row != 0
+
+
+def test_build_without_choices_is_the_encoder():
+    for w, h in SIZES:
+        a = make("every_b", w, h, 3, 8)
+        assert orc.build(a) == orc.encode(a) == kb.loader.encode_frame(a)
+        assert all(b == needed and pad == 0 for b, needed, pad in orc.segments_of(orc.encode(a)))
+
+
 # ----------------------------------------------------------------------------- kbn_frame_check
 def _valid():
     """A 3-plane 8-bit 37 x 19 file (three groups, a short last one; three segments a row, a short last one) and where its parts are."""
@@ -166,6 +218,9 @@ def _damaged():
     d = bytearray(data)
     d[start - 1] = 1
     cases["padding not zero"] = d
+    # the payload cut to 10 bytes, payload_bytes and every entry saying so, but entry 1 left far above: plane 0 claims room for its
+    # header bytes that the file does not have (check_file reads them before it sees entry 2 fall back)
+    cases["a short payload under an inner entry above payload_bytes"] = _with_table(data[:start + 10], [0, 1000] + [10] * (len(table) - 2), 10)
     return cases
 
 
@@ -292,6 +347,12 @@ def test_the_comparisons_catch_planted_mistakes():
             continue
         caught = [not np.array_equal(orc.decode(f, mistake), a) for f, a in zip(files, cases)]
         assert any(caught), mistake
+    # ... and each is caught on a hand-made file too: the comparisons of test_hand_made_files_decode_like_the_oracle have the same power
+    made = [noncanonical(choice, w, h, c, bits) for w, h in SIZES[2:] for c, bits in ((1, 8), (3, 8), (1, 16)) for choice in WIDTH_CHOICES]
+    assert all(np.array_equal(orc.decode(f), a) for f, a in made)
+    for mistake in orc.MISTAKES:
+        if mistake != "third_rounded":
+            assert any(not np.array_equal(orc.decode(f, mistake), a) for f, a in made), mistake
     g = np.random.Generator(np.random.Philox(3))
     triplet = g.integers(0, 256, size=(25, 3 * 43, 3), dtype=np.uint8)
     depth = g.integers(0, 65536, size=(25, 43), dtype=np.uint16)
@@ -300,6 +361,10 @@ def test_the_comparisons_catch_planted_mistakes():
     got = orc.unpack(tf, df, 2, 7, 16, 24)
     assert all(np.array_equal(a, b) for a, b in zip(got[:3], want))
     assert np.array_equal(got[3][0], depth[2:18, 7:31].astype(np.float32) / 256)
+    planted = orc.unpack(tf, df, 2, 7, 16, 24, mistake="third_rounded")
+    assert not np.array_equal(planted[0], want[0]) and not np.array_equal(planted[2], want[2])
+    tf, df = orc.build(triplet, lambda *a: a[5]), orc.build(depth // 16, lambda *a: a[4] + 1, lambda *a: 0xff)      # hand-made files of the same frame
+    assert tf != orc.encode(triplet) and all(np.array_equal(a, b) for a, b in zip(orc.unpack(tf, df, 2, 7, 16, 24)[:3], want))
     planted = orc.unpack(tf, df, 2, 7, 16, 24, mistake="third_rounded")
     assert not np.array_equal(planted[0], want[0]) and not np.array_equal(planted[2], want[2])
 

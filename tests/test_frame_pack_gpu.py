@@ -1,8 +1,10 @@
 """GPU: the device decoder of the packed frame store.  ops.unpack_packed_frames against ops.unpack_train_frames /
 ops.unpack_frames on the same frames' raw bytes and against NumPy slices; both loaders over packed files against themselves over
-the PNG files the packed ones were made from.  Every packed file here is made by kbn_frame_encode (compared byte for byte with
-the NumPy encoder in tests/test_frame_pack_cpu.py) and passes kbn_frame_check before its bytes go to the device."""
+the PNG files the packed ones were made from.  The packed files are made by kbn_frame_encode (compared byte for byte with
+the NumPy encoder in tests/test_frame_pack_cpu.py) or, for the format's sake, by hand (tests/frame_pack_oracle.py: header bytes wider
+than needed, nonzero pad bits, random field bits); every one passes kbn_frame_check before its bytes go to the device."""
 import filecmp
+import functools
 import os
 import struct
 
@@ -10,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import frame_pack_oracle as orc
 import kbnet_amd as kb
 import run_cases as rc
 from conftest import GOLDEN_DIR
@@ -40,16 +43,21 @@ RAW = [kb.loader.decode_png(read(p)) for p in T_IMAGES]      # H x 3W x 3 uint8:
 DEP = [kb.loader.decode_png(read(p)) for p in T_DEPTHS]      # H x W uint16
 
 
-def stage(arrays, lead=0):
-    """The packed files of `arrays` in one buffer, each at a 16-byte-aligned offset (the first at `lead`): (bytes, [(offset, size)])."""
+def stage_files(files, lead=0):
+    """Ready-made packed files in one buffer, each at a 16-byte-aligned offset (the first at `lead`): (bytes, [(offset, size)]).
+    Every file passes kbn_frame_check first: nothing the host refuses goes to the device."""
     flat, places = bytearray(lead), []
-    for a in arrays:
-        data = kb.loader.encode_frame(a)
-        kb.loader.check_frame(data)
+    for data in files:
+        kb.loader.check_frame(bytes(data))
         flat += b"\xee" * (-len(flat) % 16)
         places.append((len(flat), len(data)))
         flat += data
     return np.frombuffer(bytes(flat), dtype=np.uint8), places
+
+
+def stage(arrays, lead=0):
+    """stage_files of the encoder's files of `arrays`."""
+    return stage_files([kb.loader.encode_frame(a) for a in arrays], lead)
 
 
 def stage_raw(arrays):
@@ -75,6 +83,24 @@ def both(dev, raws, deps, starts, shape, channels=3, depth_bits=16, lead=0):
                                        [(a, b, h, w, y, x) for a, b, (h, w), (y, x) in zip(rip, rdp, sizes, starts)], shape,
                                        channels=channels, depth_bits=depth_bits)
     return packed, plain
+
+
+def both_files(dev, image_files, depth_files, starts, shape, channels=3, depth_bits=16):
+    """both() for ready-made files: (packed decoder's tensors from the files, raw-byte kernel's tensors from the samples the HOST
+    decoder gives for the same files, those samples)."""
+    raws, deps = [kb.loader.decode_frame(f) for f in image_files], [kb.loader.decode_frame(f) for f in depth_files]
+    pi, pip = stage_files(image_files)
+    pd, pdp = stage_files(depth_files)
+    ri, rip = stage_raw(raws)
+    rd, rdp = stage_raw(deps)
+    sizes = [(d.shape[0], d.shape[1]) for d in deps]
+    packed = kb.ops.unpack_packed_frames(torch.from_numpy(pi.copy()).to(dev), torch.from_numpy(pd.copy()).to(dev),
+                                         [(a, n, b, m, h, w, y, x) for (a, n), (b, m), (h, w), (y, x) in zip(pip, pdp, sizes, starts)], shape,
+                                         channels=channels, depth_bits=depth_bits)
+    plain = kb.ops.unpack_train_frames(torch.from_numpy(ri.copy()).to(dev), torch.from_numpy(rd.copy()).to(dev),
+                                       [(a, b, h, w, y, x) for a, b, (h, w), (y, x) in zip(rip, rdp, sizes, starts)], shape,
+                                       channels=channels, depth_bits=depth_bits)
+    return packed, plain, raws, deps
 
 
 def slices(raw, dep, y, x, h, w):
@@ -133,6 +159,55 @@ def test_channels_and_depth_widths(dev, channels, depth_bits):
     for shape, starts in (((13, 17), [(5, 3), (6, 4)]), ((19, 21), [(0, 0), (0, 0)]), ((8, 16), [(8, 5), (11, 0)])):
         packed, plain = both(dev, raws, deps, starts, shape, channels=channels, depth_bits=depth_bits)
         assert_same(packed, plain, raws, deps, starts, shape, shape)
+
+
+# ------------------------------------------------------------------------------------- files no encoder of ours writes
+# The format is the contract: any file kbn_frame_check accepts, canonical or not, decodes on the device to what the host decoder and
+# the NumPy oracle make of it.  Thirds of 25 x 43 (raw width 129: thirds begin inside segments, a short last group of one row, a short
+# last segment of one sample) and of 19 x 21 (raw width 63).
+@functools.lru_cache(maxsize=None)
+def hand_made(choice, w, h, c, bits):
+    data, samples = orc.hand_made(choice, w, h, c, bits, seed=3)
+    assert np.array_equal(orc.decode(data), samples) and data != kb.loader.encode_frame(samples)
+    return data, samples
+
+
+@pytest.mark.parametrize("depth_bits", [8, 16])
+@pytest.mark.parametrize("channels", [1, 3, 4])
+@pytest.mark.parametrize("choice", orc.WIDTH_CHOICES)
+def test_hand_made_files_decode_on_the_device_as_on_the_host(dev, choice, channels, depth_bits):
+    """Image and depth file both hand-made, by each of the four width choices: crops (13, 21) from (6, 4) and (9, 17), clamped to the
+    smaller frame; (16, 24) from (8, 16), the 16-byte store path; the full frames.  Every launch twice: the same bits."""
+    image = {hw: hand_made(choice, 3 * hw[1], hw[0], channels, 8) for hw in ((25, 43), (19, 21))}
+    depth = {hw: hand_made(choice, hw[1], hw[0], 1, depth_bits) for hw in ((25, 43), (19, 21))}
+    big, small = (25, 43), (19, 21)
+    launches = [((13, 21), [big, small, big, small], [(6, 4), (6, 0), (9, 17), (0, 0)]),
+                ((16, 24), [big], [(8, 16)]),
+                ((25, 43), [big, big], [(0, 0), (0, 0)]),
+                ((19, 21), [small], [(0, 0)])]
+    for shape, frames, starts in launches:
+        ifiles, dfiles = [image[hw][0] for hw in frames], [depth[hw][0] for hw in frames]
+        packed, plain, raws, deps = both_files(dev, ifiles, dfiles, starts, shape, channels=channels, depth_bits=depth_bits)
+        for hw, raw, dep in zip(frames, raws, deps):      # the host decoder gave the oracle's samples
+            assert np.array_equal(raw, image[hw][1]) and np.array_equal(dep, depth[hw][1])
+        assert_same(packed, plain, raws, deps, starts, shape, (choice, shape))
+        again = both_files(dev, ifiles, dfiles, starts, shape, channels=channels, depth_bits=depth_bits)[0]
+        for a, b in zip(packed, again):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (choice, shape)
+
+
+@pytest.mark.parametrize("choice", orc.WIDTH_CHOICES[:3])
+def test_a_canonical_and_a_hand_made_file_of_one_frame_in_one_launch(dev, choice):
+    """Frame 0 the encoder's files, frame 1 hand-made files of the same samples: identical outputs."""
+    ifile, raw = hand_made(choice, 129, 25, 3, 8)
+    dfile, dep = hand_made(choice, 43, 25, 1, 16)
+    canonical = kb.loader.encode_frame(raw), kb.loader.encode_frame(dep)
+    assert canonical[0] != ifile and canonical[1] != dfile
+    for shape, start in (((13, 21), (9, 17)), ((16, 24), (8, 16)), ((25, 43), (0, 0))):
+        packed, plain, raws, deps = both_files(dev, [canonical[0], ifile], [canonical[1], dfile], [start, start], shape)
+        assert_same(packed, plain, raws, deps, [start, start], shape, (choice, shape))
+        for t in packed:
+            assert torch.equal(t[0].view(torch.int32), t[1].view(torch.int32)), (choice, shape)
 
 
 def test_a_third_narrower_than_a_segment(dev):

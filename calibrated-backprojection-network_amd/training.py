@@ -23,10 +23,11 @@ train_resumable() is train() in sessions: the same call, made in one job slot af
 last one left in checkpoint_path, bit for bit as the uninterrupted run.  train_ranks_resumable() is the same for
 train_ranks() -- the ranks agree on the step a session stops after, rank 0 writes the one state every rank continues from -- and
 launch_resumable() starts its processes and passes the scheduler's signal on to them.  All entry points run one
-loop, _train_loop."""
+loop: _train_loop names the phases of a run, top to bottom, and a _Run holds what the phases and the steps share."""
 
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import inspect
 import os
@@ -38,6 +39,7 @@ import subprocess
 import sys
 import threading
 import time
+import types
 
 import numpy as np
 import torch
@@ -281,13 +283,12 @@ class _Session:
         self.n_train_step = self.n_checkpoint = None
         self.vote = dist.StopVote(0, 1)      # of one process; the loop of several ranks puts theirs here
 
-    def start(self, checkpoint_path, record, n_train_step, n_checkpoint, rank=0, world=1):
-        """-> the state to continue from, or None for a fresh start.  Reads only; KbnError when `record` is not the run's.  With
-        several ranks rank 0 looks (find_state) and its answer -- a step or none, and the messages -- is everybody's: a file system
-        may show one rank a newest state cut short and another the whole of it.  Every rank then loads that one file, and every
-        rank raises for a record that is not the run's."""
-        self.checkpoint_path, self.record = checkpoint_path, record
-        self.n_train_step, self.n_checkpoint = int(n_train_step), int(n_checkpoint)
+    def start(self, checkpoint_path, n_checkpoint, rank=0, world=1):
+        """-> the newest complete state of `checkpoint_path`, or None for a fresh start.  Reads only.  With several ranks rank 0
+        looks (find_state) and its answer -- a step or none, and the messages -- is everybody's: a file system may show one rank a
+        newest state cut short and another the whole of it.  Every rank then loads that one file.  The loop checks the state's
+        record against the call's (_resume_point), on every rank, and leaves the record and the run's steps here."""
+        self.checkpoint_path, self.n_checkpoint = checkpoint_path, int(n_checkpoint)
         if world == 1:
             state, self.skipped = find_state(checkpoint_path)
         else:
@@ -298,8 +299,6 @@ class _Session:
             step, self.skipped = dist.broadcast_object(found, src=0)
             if step is not None and rank != 0:
                 state = torch.load(os.path.join(checkpoint_path, STATE_FILE.format(step)), map_location="cpu")
-        if state is not None:
-            check_argument_record(state["arguments"], record)
         return state
 
     def step_done(self) -> bool:
@@ -317,6 +316,11 @@ class _Session:
         snapshot["arguments"] = self.record
         self.write(os.path.join(self.checkpoint_path, STATE_FILE.format(snapshot["step"])), lambda part: torch.save(snapshot, part))
         prune_states(self.checkpoint_path, self.keep_states, self.n_checkpoint, self.n_train_step, current=snapshot["step"])
+
+
+def _new_session(max_steps, max_seconds, stop_signals, keep_states) -> _Session:
+    """A session and its Budget (session.budget, the context the loop runs in), with the refusals of both."""
+    return _Session(Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals), keep_states)
 
 
 def _train_loop(train_image_path,
@@ -393,343 +397,401 @@ def _train_loop(train_image_path,
           sync_batch_norm=True,
           session=None):
     """The loop of train_ranks() and train_resumable(): train_ranks()'s arguments and `session`, the hooks of a resumable run
-    (_Session; None for train_ranks: nothing of a session is read, written or checked)."""
+    (_Session; None for train_ranks: nothing of a session is read, written or checked).  The phases of a run, top to bottom; what
+    they share is the _Run's."""
     arguments = dict(locals())      # before anything else is bound: what the call was given
-    if device == "cuda" or device == "gpu":
-        device = torch.device("cuda")
-    else:
-        raise KbnError(f"train: device {device!r}: the HIP path has no CPU fallback (the reference trains on the CPU for anything but 'cuda' / 'gpu')")
-    rank, world = int(rank), int(world)
-    if world < 1 or not 0 <= rank < world:
-        raise KbnError(f"train_ranks: rank {rank} of world {world}")
-    if world > 1 and not (torch.distributed.is_available() and torch.distributed.is_initialized()
-                          and torch.distributed.get_world_size() == world and torch.distributed.get_rank() == rank):
-        raise KbnError(f"train_ranks: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init, or "
-                       "kb.training.launch, which starts the ranks)")
-    main = rank == 0      # the rank that writes
-    transforms_seed = None
-    if world > 1:      # before anything is drawn: the weights' initialisation, the epoch's order, the crops, the augmentation
-        dist.broadcast_rng_state(src=0)
-        transforms_seed = dist.broadcast_object(torch.initial_seed(), src=0)
-    workers = int(n_thread if workers is None else workers)
-    if int(val_batch_size) < 1:
-        raise KbnError(f"train: val_batch_size {val_batch_size}")
-
-    depth_model_checkpoint_path = os.path.join(checkpoint_path, "depth_model-{}.pth")
-    pose_model_checkpoint_path = os.path.join(checkpoint_path, "pose_model-{}.pth")
-    log_path = os.path.join(checkpoint_path, "results.txt")
-    event_path = os.path.join(checkpoint_path, "events")
-
-    best_results = {"step": -1, "mae": np.inf, "rmse": np.inf, "imae": np.inf, "irmse": np.inf}
-
-    # ---- input paths ----
-    train_image_paths = loader.read_paths(train_image_path)
-    train_sparse_depth_paths = loader.read_paths(train_sparse_depth_path)
-    train_intrinsics_paths = loader.read_paths(train_intrinsics_path)
-    n_train_sample = len(train_image_paths)
-    for name, paths in (("sparse depth", train_sparse_depth_paths), ("intrinsics", train_intrinsics_paths)):
-        if len(paths) != n_train_sample:
-            raise KbnError(f"train: {n_train_sample} training image paths, {len(paths)} {name} paths")
-    if n_train_sample < 1:
-        raise KbnError(f"train: {train_image_path} lists no frame")
-    n_train_step = n_train_steps(n_train_sample, n_batch, learning_schedule, world=world)
-
-    validation_available = val_image_path is not None and val_sparse_depth_path is not None and \
-        val_intrinsics_path is not None and val_ground_truth_path is not None
-    if validation_available:
-        val_image_paths = loader.read_paths(val_image_path)
-        val_sparse_depth_paths = loader.read_paths(val_sparse_depth_path)
-        val_intrinsics_paths = loader.read_paths(val_intrinsics_path)
-        val_ground_truth_paths = loader.read_paths(val_ground_truth_path)
-        n_val_sample = len(val_image_paths)
-        for name, paths in (("sparse depth", val_sparse_depth_paths), ("intrinsics", val_intrinsics_paths),
-                            ("ground truth", val_ground_truth_paths)):
-            if len(paths) != n_val_sample:
-                raise KbnError(f"train: {n_val_sample} validation image paths, {len(paths)} {name} paths")
-
-    # ---- a resumable run: the newest complete state of checkpoint_path, refused or returned before anything is built or written ----
-    state = None
-    if session is not None:
-        contents = dict(zip(PATH_ARGUMENTS, (train_image_paths, train_sparse_depth_paths, train_intrinsics_paths)))
-        if validation_available:
-            contents.update(zip(PATH_ARGUMENTS[3:], (val_image_paths, val_sparse_depth_paths, val_intrinsics_paths, val_ground_truth_paths)))
-        state = session.start(checkpoint_path, argument_record(arguments, contents), n_train_step, n_checkpoint, rank, world)
-        if state is not None and state["step"] >= n_train_step:      # finished in an earlier session
-            return _stored_results(state) if return_results else None
-        if state is not None:
-            best_results = state["best_results"]
-
-    # ---- the models: what KBNetModel(trainable=True) refuses is refused before anything is written ----
-    depth_model = KBNetModel(
-        input_channels_image=input_channels_image, input_channels_depth=input_channels_depth,
-        min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
-        max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
-        n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
-        n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
-        resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
-        weight_initializer=weight_initializer, activation_func=activation_func, min_predict_depth=min_predict_depth,
-        max_predict_depth=max_predict_depth, device=device, trainable=True)
-    depth_model.requires_grad_(True)
-    parameters_depth_model = depth_model.parameters()
-
-    pose_model = ResNetPoseNetModel(18, rotation_parameterization="axis", weight_initializer=weight_initializer, activation_func="relu",
-                                    device=device, trainable=True)
-    pose_model.requires_grad_(True).set_batch_norm("batch")      # the reference's pose_model.train()
-    parameters_pose_model = pose_model.parameters()
-
-    if state is None:      # a continuation restores its own checkpoints, with the optimizer, once that exists
-        if depth_model_restore_path is not None and depth_model_restore_path != "":
-            depth_model.restore_model(depth_model_restore_path)
-        if pose_model_restore_path is not None and pose_model_restore_path != "":
-            pose_model.restore_model(pose_model_restore_path)
-
-    averager = None
-    if world > 1:
-        averager = dist.GradientAverager(parameters_depth_model + parameters_pose_model, rank, world)      # the list the optimizer steps
-        averager.broadcast_parameters()
-        if sync_batch_norm:
-            pose_model.sync_batch_norm(dist.BatchNormGroup(rank, world))
-
-    if main and not os.path.exists(checkpoint_path):
-        os.makedirs(checkpoint_path)
-
-    # ---- the loaders ----
-    sharding = {} if world == 1 else {"rank": rank, "world": world, "crops": "global"}
-    train_loader = loader.TrainingFrameLoader(train_image_paths, train_sparse_depth_paths, train_intrinsics_paths,
-                                              shape=(n_height, n_width), random_crop_type=augmentation_random_crop_type,
-                                              batch_size=n_batch, shuffle=True, device=device, workers=workers, **sharding)
-    train_transforms = transforms.Transforms(normalized_image_range=normalized_image_range, random_flip_type=augmentation_random_flip_type,
-                                             random_remove_points=augmentation_random_remove_points,
-                                             random_noise_type=augmentation_random_noise_type,
-                                             random_noise_spread=augmentation_random_noise_spread, seed=transforms_seed)
-    if validation_available:
-        ground_truths = []
-        for path in val_ground_truth_paths:
-            ground_truth, validity_map = loader.load_depth_with_validity_map(path)
-            ground_truths.append(np.stack([ground_truth, validity_map], axis=-1))
-        val_dataloader = loader.InferenceFrameLoader(val_image_paths, val_sparse_depth_paths, val_intrinsics_paths, use_image_triplet=True,
-                                                     batch_size=int(val_batch_size), device=device, workers=workers)
-
-    train_summary_writer = val_summary_writer = None
-    logged, checkpoints = [], []
-    if not main:      # rank 0 alone writes: the other ranks open no writer and keep no log
-        log_path = None
-    try:
-        if main:
-            train_summary_writer = summary_writer_factory(event_path + "-train")
-            val_summary_writer = summary_writer_factory(event_path + "-val")
-
-        # ---- the head of results.txt ----
-        log = summary.log if main else (lambda s, filepath=None, to_console=True: None)
-        if state is None:      # the path and settings blocks: once, on the fresh start
-            log("Training input paths:", log_path)
-            for path in (train_image_path, train_sparse_depth_path, train_intrinsics_path):
-                log(path, log_path)
-            log("", log_path)
-            log("Validation input paths:", log_path)
-            for path in (val_image_path, val_sparse_depth_path, val_intrinsics_path, val_ground_truth_path):
-                log(path, log_path)
-            log("", log_path)
-            if main:
-                summary.log_input_settings(
-                    log_path, n_batch=n_batch, n_height=n_height, n_width=n_width, input_channels_image=input_channels_image,
-                    input_channels_depth=input_channels_depth, normalized_image_range=normalized_image_range,
-                    outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold)
-                summary.log_network_settings(
-                    log_path, min_pool_sizes_sparse_to_dense_pool=min_pool_sizes_sparse_to_dense_pool,
-                    max_pool_sizes_sparse_to_dense_pool=max_pool_sizes_sparse_to_dense_pool,
-                    n_convolution_sparse_to_dense_pool=n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool=n_filter_sparse_to_dense_pool,
-                    n_filters_encoder_image=n_filters_encoder_image, n_filters_encoder_depth=n_filters_encoder_depth,
-                    resolutions_backprojection=resolutions_backprojection, n_filters_decoder=n_filters_decoder, deconv_type=deconv_type,
-                    min_predict_depth=min_predict_depth, max_predict_depth=max_predict_depth, weight_initializer=weight_initializer,
-                    activation_func=activation_func, parameters_depth_model=parameters_depth_model, parameters_pose_model=parameters_pose_model)
-                summary.log_training_settings(
-                    log_path, n_batch=n_batch, n_train_sample=n_train_sample, n_train_step=n_train_step, learning_rates=learning_rates,
-                    learning_schedule=learning_schedule, augmentation_probabilities=augmentation_probabilities,
-                    augmentation_schedule=augmentation_schedule, augmentation_random_crop_type=augmentation_random_crop_type,
-                    augmentation_random_flip_type=augmentation_random_flip_type, augmentation_random_remove_points=augmentation_random_remove_points,
-                    augmentation_random_noise_type=augmentation_random_noise_type, augmentation_random_noise_spread=augmentation_random_noise_spread)
-                summary.log_loss_func_settings(
-                    log_path, w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness,
-                    w_weight_decay_depth=w_weight_decay_depth, w_weight_decay_pose=w_weight_decay_pose)
-                summary.log_evaluation_settings(log_path, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth)
-                summary.log_system_settings(
-                    log_path, checkpoint_path=checkpoint_path, n_checkpoint=n_checkpoint, summary_event_path=event_path, n_summary=n_summary,
-                    n_summary_display=n_summary_display, validation_start_step=validation_start_step,
-                    depth_model_restore_path=depth_model_restore_path, pose_model_restore_path=pose_model_restore_path, device=device,
-                    n_thread=n_thread)
-
-        # ---- the optimizer and the schedules ----
-        learning_schedule_pos, learning_rate = 0, learning_rates[0]
-        augmentation_schedule_pos, augmentation_probability = 0, augmentation_probabilities[0]
-        optimizer = optim.Adam([{"params": parameters_depth_model, "weight_decay": w_weight_decay_depth},
-                                {"params": parameters_pose_model, "weight_decay": w_weight_decay_pose}], lr=learning_rate)
-
-        def save(model, path):      # a session's files appear whole or not at all
-            if session is None:
-                model.save_model(path, train_step, optimizer)
-            else:
-                session.write(path, lambda part: model.save_model(part, train_step, optimizer))
-
-        def snapshot(digest=None):      # what a continuation needs beyond the two checkpoints; no wait for the device
-            return {"step": train_step, "epoch": epoch, "batch": batch + 1, "loader": train_loader.state_dict(),
-                    "transforms": train_transforms.state_dict(), "random": random_state(device),
-                    "best_results": {k: _plain(v) for k, v in best_results.items()}, "logged": list(logged),
-                    "seconds": seconds_before + time.time() - time_start, "digest": digest}
-
-        train_step, first_epoch, first_batch, seconds_before, stopped = 0, 1, 0, 0.0, False
+    s = types.SimpleNamespace(**arguments)
+    run = _Run(s)                                                    # the process checks; rank 0's random state on every rank
+    contents = _path_lists(arguments)
+    state, finished = run.resume_point(arguments, contents)          # refused or returned before anything is built or written
+    if finished:
+        return _stored_results(state) if s.return_results else None
+    run.build_models(state)                                          # what they refuse is refused before anything is written
+    run.join_ranks()
+    run.build_loaders(contents)
+    with _summary_writers(s.summary_writer_factory, run.event_path, run.main) as (run.train_summary_writer, run.val_summary_writer):
         if state is None:
-            log("Begin training...", log_path)
+            run.log_head(contents)
+        run.begin(state)
+        run.train_epochs()
+        run.finish()
+    return run.results()
+
+
+def _path_lists(arguments: dict) -> dict:
+    """PATH_ARGUMENTS name -> the paths its file lists: the three training lists, then the four validation lists where all four are
+    given (validation is off otherwise, and none of them is read).  KbnError for lists of different lengths and for no frame."""
+    def read(names, what, kinds):
+        lists = {name: loader.read_paths(arguments[name]) for name in names}
+        n_sample = len(lists[names[0]])
+        for name, kind in zip(names[1:], kinds):
+            if len(lists[name]) != n_sample:
+                raise KbnError(f"train: {n_sample} {what} image paths, {len(lists[name])} {kind} paths")
+        return lists
+
+    contents = read(PATH_ARGUMENTS[:3], "training", ("sparse depth", "intrinsics"))
+    if not contents[PATH_ARGUMENTS[0]]:
+        raise KbnError(f"train: {arguments[PATH_ARGUMENTS[0]]} lists no frame")
+    if all(arguments[name] is not None for name in PATH_ARGUMENTS[3:]):
+        contents.update(read(PATH_ARGUMENTS[3:], "validation", ("sparse depth", "intrinsics", "ground truth")))
+    return contents
+
+
+def _resume_point(arguments: dict, world: int, state, contents=None):
+    """Where a call stands in its run -> (the argument record, the run's steps, finished?).  arguments: the call's, bound with their
+    defaults; state: the newest complete state of its checkpoint_path, or None; contents: the path lists, where the caller has read
+    them already (the loop has: it refuses them before it looks for a state).  KbnError when the state's record is not this one;
+    finished: the state is one of the run's last step."""
+    if contents is None:
+        contents = _path_lists(arguments)
+    record = argument_record(arguments, contents)
+    n_train_step = n_train_steps(len(contents[PATH_ARGUMENTS[0]]), arguments["n_batch"], arguments["learning_schedule"], world=world)
+    if state is not None:
+        check_argument_record(state["arguments"], record)
+    return record, n_train_step, state is not None and state["step"] >= n_train_step
+
+
+@contextlib.contextmanager
+def _summary_writers(summary_writer_factory, event_path, main):
+    """-> (the train writer, the val writer), on rank 0; (None, None) elsewhere, where the factory is not called.  An exception in
+    the body closes what was opened and is the one raised: the writers' own close errors are swallowed.  On the normal path the train
+    writer is closed, then the val writer whatever the first close did, and their errors propagate."""
+    writers = []
+    try:
+        for which in ("-train", "-val") if main else ():
+            writers.append(summary_writer_factory(event_path + which))
+        yield writers if main else (None, None)
+    except BaseException:
+        for writer in writers:
+            with contextlib.suppress(Exception):      # the run's own exception is the one to see
+                writer.close()
+        raise
+    with contextlib.ExitStack() as closing:      # callbacks run last in, first out, each whatever the one before it raised
+        for writer in reversed(writers):
+            closing.callback(writer.close)
+
+
+def _named(function, values: dict) -> dict:
+    """The items of `values` that `function`'s parameter list names: its keyword arguments from the settings, listed nowhere twice."""
+    return {name: values[name] for name in inspect.signature(function).parameters if name in values}
+
+
+class _Schedules:
+    """The run's place in its two schedules, the reference's src/kbnet.py:378-390: learning_rate and augmentation_probability are
+    those of the last epoch advance() was called for.  A continuation replays advance() for every epoch up to its state's."""
+
+    def __init__(self, learning_schedule, learning_rates, augmentation_schedule, augmentation_probabilities):
+        self.learning_schedule, self.learning_rates = learning_schedule, learning_rates
+        self.augmentation_schedule, self.augmentation_probabilities = augmentation_schedule, augmentation_probabilities
+        self.learning_position, self.learning_rate = 0, learning_rates[0]
+        self.augmentation_position, self.augmentation_probability = 0, augmentation_probabilities[0]
+
+    def advance(self, epoch: int) -> bool:
+        """The two moves at the start of `epoch` (1-based) -> did the learning rate move?"""
+        self.learning_position, self.learning_rate, moved = scheduled(epoch, self.learning_position, self.learning_schedule, self.learning_rates)
+        self.augmentation_position, self.augmentation_probability, _ = scheduled(
+            epoch, self.augmentation_position, self.augmentation_schedule, self.augmentation_probabilities, frozen=-1 in self.augmentation_schedule)
+        return moved
+
+
+class _Run:
+    """What a run of _train_loop holds between its phases and its steps: the settings `s` as the call gave them, the process's place
+    among the ranks, the models, the optimizer, the loaders, the counters and the lists.  Its methods are the loop's phases, in the
+    order _train_loop calls them, and the parts of a step; they read their arguments and these attributes, nothing else."""
+
+    def __init__(self, s):
+        """The process checks, and rank 0's random state on every rank."""
+        if s.device != "cuda" and s.device != "gpu":
+            raise KbnError(f"train: device {s.device!r}: the HIP path has no CPU fallback (the reference trains on the CPU for anything but 'cuda' / 'gpu')")
+        self.device, rank, world = torch.device("cuda"), int(s.rank), int(s.world)
+        if world < 1 or not 0 <= rank < world:
+            raise KbnError(f"train_ranks: rank {rank} of world {world}")
+        if world > 1 and not (torch.distributed.is_available() and torch.distributed.is_initialized()
+                              and torch.distributed.get_world_size() == world and torch.distributed.get_rank() == rank):
+            raise KbnError(f"train_ranks: rank {rank} of world {world} needs an initialised process group of that size (kb.dist.init, or "
+                           "kb.training.launch, which starts the ranks)")
+        self.s, self.session, self.rank, self.world = s, s.session, rank, world
+        self.main, self.transforms_seed = rank == 0, None      # main: the rank that writes
+        if world > 1:      # before anything is drawn: the weights' initialisation, the epoch's order, the crops, the augmentation
+            dist.broadcast_rng_state(src=0)
+            self.transforms_seed = dist.broadcast_object(torch.initial_seed(), src=0)
+        self.workers = int(s.n_thread if s.workers is None else s.workers)
+        if int(s.val_batch_size) < 1:
+            raise KbnError(f"train: val_batch_size {s.val_batch_size}")
+
+        self.depth_model_checkpoint_path = os.path.join(s.checkpoint_path, "depth_model-{}.pth")
+        self.pose_model_checkpoint_path = os.path.join(s.checkpoint_path, "pose_model-{}.pth")
+        self.log_path = os.path.join(s.checkpoint_path, "results.txt") if self.main else None      # rank 0 alone keeps a log
+        self.event_path = os.path.join(s.checkpoint_path, "events")
+        self.write = (lambda path, writer: writer(path)) if s.session is None else s.session.write      # a session's files appear whole
+
+        self.best_results = {"step": -1, "mae": np.inf, "rmse": np.inf, "imae": np.inf, "irmse": np.inf}
+        self.logged, self.checkpoints = [], []
+        self.train_step, self.epoch, self.batch = 0, 0, -1      # the last step taken, and the epoch and the batch it was
+        self.first_epoch, self.first_batch, self.resumed_from = 1, 0, None
+        self.seconds_before, self.time_start = 0.0, None      # trained in earlier sessions; when this one began
+        self.stopped, self.digest = False, None
+
+    def log(self, text):
+        if self.main:
+            summary.log(text, self.log_path)
+
+    # ---- the phases before the first step ----
+    def resume_point(self, arguments, contents):
+        """-> (the state a session continues from or None, is the run finished?): the newest complete state of checkpoint_path,
+        which a changed argument refuses."""
+        s, session = self.s, self.session
+        state = None if session is None else session.start(s.checkpoint_path, s.n_checkpoint, self.rank, self.world)
+        record, self.n_train_step, finished = _resume_point(arguments, self.world, state, contents)
+        if session is not None:
+            session.record, session.n_train_step = record, self.n_train_step
+        return state, finished
+
+    def build_models(self, state):
+        """The depth model, then the pose model, then -- on a fresh start -- what the restore paths name."""
+        s = self.s
+        self.depth_model = KBNetModel(**_named(KBNetModel, dict(vars(s), device=self.device, trainable=True)))      # its fifteen settings
+        self.depth_model.requires_grad_(True)
+        self.parameters_depth_model = self.depth_model.parameters()
+
+        self.pose_model = ResNetPoseNetModel(18, rotation_parameterization="axis", weight_initializer=s.weight_initializer, activation_func="relu",
+                                             device=self.device, trainable=True)
+        self.pose_model.requires_grad_(True).set_batch_norm("batch")      # the reference's pose_model.train()
+        self.parameters_pose_model = self.pose_model.parameters()
+
+        if state is None:      # a continuation restores its own checkpoints, with the optimizer, once that exists
+            for model, path in ((self.depth_model, s.depth_model_restore_path), (self.pose_model, s.pose_model_restore_path)):
+                if path is not None and path != "":
+                    model.restore_model(path)
+
+    def join_ranks(self):
+        """Rank 0's parameters on every rank; the averager of the gradients; the pose model's BatchNorm over the frames of all."""
+        self.averager = None
+        if self.world > 1:
+            self.averager = dist.GradientAverager(self.parameters_depth_model + self.parameters_pose_model, self.rank, self.world)      # the list the optimizer steps
+            self.averager.broadcast_parameters()
+            if self.s.sync_batch_norm:
+                self.pose_model.sync_batch_norm(dist.BatchNormGroup(self.rank, self.world))
+
+    def build_loaders(self, contents):
+        """checkpoint_path, the first thing a run writes; the training loader and Transforms; the validation set."""
+        s = self.s
+        if self.main and not os.path.exists(s.checkpoint_path):
+            os.makedirs(s.checkpoint_path)
+        sharding = {} if self.world == 1 else {"rank": self.rank, "world": self.world, "crops": "global"}
+        self.train_loader = loader.TrainingFrameLoader(*(contents[name] for name in PATH_ARGUMENTS[:3]), shape=(s.n_height, s.n_width),
+                                                       random_crop_type=s.augmentation_random_crop_type, batch_size=s.n_batch, shuffle=True,
+                                                       device=self.device, workers=self.workers, **sharding)
+        self.train_transforms = transforms.Transforms(
+            normalized_image_range=s.normalized_image_range, random_flip_type=s.augmentation_random_flip_type,
+            random_remove_points=s.augmentation_random_remove_points, random_noise_type=s.augmentation_random_noise_type,
+            random_noise_spread=s.augmentation_random_noise_spread, seed=self.transforms_seed)
+        self.validation_available = PATH_ARGUMENTS[3] in contents
+        if self.validation_available:      # every ground truth with its validity map, on the host
+            self.ground_truths = [np.stack(loader.load_depth_with_validity_map(path), axis=-1) for path in contents[PATH_ARGUMENTS[6]]]
+            self.val_dataloader = loader.InferenceFrameLoader(*(contents[name] for name in PATH_ARGUMENTS[3:6]), use_image_triplet=True,
+                                                              batch_size=int(s.val_batch_size), device=self.device, workers=self.workers)
+
+    def log_head(self, contents):
+        """The head of results.txt, once, on the fresh start: the two path blocks and the six settings blocks."""
+        s = self.s
+        for title, names in (("Training input paths:", PATH_ARGUMENTS[:3]), ("Validation input paths:", PATH_ARGUMENTS[3:])):
+            self.log(title)
+            for name in names:
+                self.log(getattr(s, name))
+            self.log("")
+        if self.main:      # every summary.log_*_settings function is given what its own parameter list names
+            values = dict(vars(s), log_path=self.log_path, n_train_sample=len(contents[PATH_ARGUMENTS[0]]), n_train_step=self.n_train_step,
+                          parameters_depth_model=self.parameters_depth_model, parameters_pose_model=self.parameters_pose_model,
+                          summary_event_path=self.event_path, device=self.device)
+            for name in ("input", "network", "training", "loss_func", "evaluation", "system"):
+                function = getattr(summary, f"log_{name}_settings")
+                function(**_named(function, values))
+
+    def begin(self, state):
+        """The schedules and the optimizer; the fresh start or the continuation from `state`; the ranks' vote; the clock."""
+        s = self.s
+        self.schedules = _Schedules(s.learning_schedule, s.learning_rates, s.augmentation_schedule, s.augmentation_probabilities)
+        self.optimizer = optim.Adam([{"params": self.parameters_depth_model, "weight_decay": s.w_weight_decay_depth},
+                                     {"params": self.parameters_pose_model, "weight_decay": s.w_weight_decay_pose}], lr=self.schedules.learning_rate)
+        if state is None:
+            self.log("Begin training...")
         else:
-            # the checkpoints of the state's step, the optimizer with them; every schedule position up to the state's epoch,
-            # replayed; the rest of that epoch, or -- after its last batch -- the next one with its own schedule moves
-            for message in session.skipped:
-                log(message, log_path)
-            train_step = state["step"]
-            depth_model.restore_model(depth_model_checkpoint_path.format(train_step), optimizer)
-            pose_model.restore_model(pose_model_checkpoint_path.format(train_step))
-            for epoch in range(1, state["epoch"] + 1):
-                learning_schedule_pos, learning_rate, _ = scheduled(epoch, learning_schedule_pos, learning_schedule, learning_rates)
-                augmentation_schedule_pos, augmentation_probability, _ = scheduled(
-                    epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
-            for g in optimizer.param_groups:
-                g["lr"] = learning_rate
-            first_epoch = state["epoch"] + (0 if state["loader"] else 1)
-            first_batch = state["batch"] if state["loader"] else 0
-            train_loader.load_state_dict(state["loader"])
-            train_transforms.load_state_dict(state["transforms"])
-            logged, seconds_before = list(state["logged"]), float(state["seconds"])
-            set_random_state(state["random"], device)      # last: building the models drew from the generators
-            log("Resuming training from step {}...".format(train_step), log_path)
-        if session is not None and world > 1:      # on every rank, here: making the vote's group is a collective
-            session.vote = dist.StopVote(rank, world)
-        time_start = time.time()
-        for epoch in range(first_epoch, learning_schedule[-1] + 1):
-            if first_batch == 0:      # not in the middle of the epoch a continuation starts in: its moves were replayed above
-                learning_schedule_pos, learning_rate, moved = scheduled(epoch, learning_schedule_pos, learning_schedule, learning_rates)
-                if moved:
-                    for g in optimizer.param_groups:
-                        g["lr"] = learning_rate
-                augmentation_schedule_pos, augmentation_probability, _ = scheduled(
-                    epoch, augmentation_schedule_pos, augmentation_schedule, augmentation_probabilities, frozen=-1 in augmentation_schedule)
+            self.resume(state)
+        if self.session is not None and self.world > 1:      # on every rank, here: making the vote's group is a collective
+            self.session.vote = dist.StopVote(self.rank, self.world)
+        self.time_start = time.time()
 
-            batches, first_batch = enumerate(train_loader, first_batch), 0
-            for batch, (image0, image1, image2, sparse_depth0, intrinsics) in batches:
-                shard = None
-                if world > 1:
-                    n_global = train_loader.global_batch_size(batch)
-                    if not dist.every_rank_has_frames(n_global, world):      # the same answer on every rank: no step
-                        continue
-                    shard = (dist.shard_bounds(n_global, rank, world)[0], n_global)
-                train_step = train_step + 1
-                image0, image1, image2, sparse_depth0, filtered_sparse_depth0, filtered_validity_map_depth0 = transforms.train_inputs(
-                    train_transforms, image0, image1, image2, sparse_depth0, augmentation_probability,
-                    kernel_size=outlier_removal_kernel_size, threshold=outlier_removal_threshold, shard=shard)
-                output_depth0 = depth_model.forward(image=image0, sparse_depth=sparse_depth0,
-                                                    validity_map_depth=filtered_validity_map_depth0, intrinsics=intrinsics)
-                pose01 = pose_model.forward(image0, image1)
-                pose02 = pose_model.forward(image0, image2)
-                loss, loss_info = depth_model.compute_loss(
-                    image0=image0, image1=image1, image2=image2, output_depth0=output_depth0, sparse_depth0=filtered_sparse_depth0,
-                    validity_map_depth0=filtered_validity_map_depth0, intrinsics=intrinsics, pose01=pose01, pose02=pose02,
-                    w_color=w_color, w_structure=w_structure, w_sparse_depth=w_sparse_depth, w_smoothness=w_smoothness)
-                optimizer.zero_grad()
-                loss.backward()
-                if averager is not None:
-                    averager.average(image0.shape[0], n_global)
-                optimizer.step()
+    def resume(self, state):
+        """The checkpoints of the state's step, the optimizer with them; every schedule position up to the state's epoch, replayed;
+        the rest of that epoch, or -- after its last batch -- the next one with its own schedule moves."""
+        for message in self.session.skipped:
+            self.log(message)
+        self.train_step = self.resumed_from = state["step"]
+        self.depth_model.restore_model(self.depth_model_checkpoint_path.format(self.train_step), self.optimizer)
+        self.pose_model.restore_model(self.pose_model_checkpoint_path.format(self.train_step))
+        for epoch in range(1, state["epoch"] + 1):
+            self.schedules.advance(epoch)
+        self.set_learning_rate()
+        self.first_epoch, self.first_batch = (state["epoch"], state["batch"]) if state["loader"] else (state["epoch"] + 1, 0)
+        self.train_loader.load_state_dict(state["loader"])
+        self.train_transforms.load_state_dict(state["transforms"])
+        self.best_results, self.logged, self.seconds_before = state["best_results"], list(state["logged"]), float(state["seconds"])
+        set_random_state(state["random"], self.device)      # last: building the models drew from the generators
+        self.log("Resuming training from step {}...".format(self.train_step))
 
-                if world > 1 and ((train_step % n_summary) == 0 or (train_step % n_checkpoint) == 0):
-                    # the global batch's loss, only where the loop waits anyway: the frames' four terms summed over the ranks
-                    # in fp64, then compute_loss's own expressions
-                    terms = dist.sum_over_ranks(loss_info["per_frame"].sum(dim=0)) / n_global
-                    color, structure, sparse, smooth = terms.float().unbind(0)
-                    loss = w_color * color + w_structure * structure + w_sparse_depth * sparse + w_smoothness * smooth
-                    loss_info.update(loss_color=color, loss_structure=structure, loss_sparse_depth=sparse, loss_smoothness=smooth, loss=loss)
+    def set_learning_rate(self):
+        for g in self.optimizer.param_groups:
+            g["lr"] = self.schedules.learning_rate
 
-                if (train_step % n_summary) == 0:
-                    image01, image02 = loss_info.pop("image01"), loss_info.pop("image02")
-                    loss_info.pop("per_frame")      # N x 4, this package's addition: a writer's add_scalar wants one number
-                    shown = dict(image0=image0, image01=image01, image02=image02, output_depth0=output_depth0.detach(),
-                                 sparse_depth0=filtered_sparse_depth0, validity_map0=filtered_validity_map_depth0, pose01=pose01, pose02=pose02)
-                    if world > 1:      # rank order is batch order; every n_summary steps, so its cost is not a concern
-                        shown = {name: dist.gather_frames(t, n_global, rank, world) for name, t in shown.items()}
-                    if main:
-                        depth_model.log_summary(summary_writer=train_summary_writer, tag="train", step=train_step, scalars=loss_info,
-                                                n_display=min(n_batch, n_summary_display), **shown)
-
-                if (train_step % n_checkpoint) == 0:
-                    value = loss.item()      # the loop's wait for the device, where the reference logs the loss
-                    time_elapse = (seconds_before + time.time() - time_start) / 3600
-                    time_remain = (n_train_step - train_step) * time_elapse / train_step
-                    log("Step={:6}/{}  Loss={:.5f}  Time Elapsed={:.2f}h  Time Remaining={:.2f}h".format(
-                        train_step, n_train_step, value, time_elapse, time_remain), log_path)
-                    logged.append((train_step, value))
-                    if train_step >= validation_start_step and validation_available:
-                        best_results = validation.validate(
-                            depth_model=depth_model, dataloader=val_dataloader, ground_truths=ground_truths, step=train_step,
-                            best_results=best_results, min_evaluate_depth=min_evaluate_depth, max_evaluate_depth=max_evaluate_depth,
-                            device=device, summary_writer=val_summary_writer, n_summary_display=n_summary_display, log_path=log_path,
-                            outlier_removal_kernel_size=outlier_removal_kernel_size, outlier_removal_threshold=outlier_removal_threshold,
-                            normalized_image_range=normalized_image_range)
-                    for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-                        if main:
-                            save(model, pattern.format(train_step))
-                        checkpoints.append(pattern.format(train_step))
-                    if session is not None and main and train_step < n_train_step:      # the last step's state follows the loop
-                        session.save_state(snapshot())
-
+    # ---- the epochs ----
+    def train_epochs(self):
+        """Every step that is left, or every step until the session's end: self.stopped says which."""
+        s, session = self.s, self.session
+        for epoch in range(self.first_epoch, s.learning_schedule[-1] + 1):
+            # not in the middle of the epoch a continuation starts in: its moves were replayed by resume()
+            if self.first_batch == 0 and self.schedules.advance(epoch):
+                self.set_learning_rate()
+            batches, self.first_batch = enumerate(self.train_loader, self.first_batch), 0
+            for batch, frames in batches:
+                self.epoch, self.batch = epoch, batch
+                taken = self.step(batch, frames)
+                if taken is None:
+                    continue
+                loss, loss_info, shown, n_global = taken
+                summary_step, checkpoint_step = (self.train_step % s.n_summary) == 0, (self.train_step % s.n_checkpoint) == 0
+                if self.world > 1 and (summary_step or checkpoint_step):
+                    loss = self.global_loss(loss_info, n_global)
+                if summary_step:
+                    self.summarise(loss_info, shown, n_global)
+                if checkpoint_step:
+                    self.checkpoint(loss)
                 # every step of a session, on every rank, whatever the step: the ranks' vote is a collective (host-side; no
                 # wait for the device), and the wish of any rank during step s stops them all after step s
-                if session is not None and session.step_done() and train_step < n_train_step:
+                if session is not None and session.step_done() and self.train_step < self.n_train_step:
                     # the session ends here, the step complete: off the checkpoint grid its two checkpoints and its state are
                     # written now (on the grid they just were), and neither a Step= line nor a validation is
-                    if (train_step % n_checkpoint) != 0:
-                        for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-                            if main:
-                                save(model, pattern.format(train_step))
-                            checkpoints.append(pattern.format(train_step))
-                        if main:
-                            session.save_state(snapshot())
-                    stopped = True
-                    break
-            if stopped:
-                break
+                    if not checkpoint_step:
+                        self.write_checkpoints()
+                        self.save_state()
+                    self.stopped = True
+                    return
 
-        digest = None
-        if not stopped:
-            for model, pattern in ((depth_model, depth_model_checkpoint_path), (pose_model, pose_model_checkpoint_path)):
-                if main:
-                    save(model, pattern.format(train_step))
-                if pattern.format(train_step) not in checkpoints:
-                    checkpoints.append(pattern.format(train_step))
-        if world > 1 or (session is not None and (return_results or not stopped)):
-            digest = replica_digest((depth_model, pose_model), optimizer)
-        if session is not None and main and not stopped:
-            session.save_state(snapshot(digest))
-        if world > 1:
+    def step(self, batch, frames):
+        """One training step on this rank's frames of global batch `batch` -> (the loss, loss_info, the tensors a summary shows, the
+        global batch's frame count), or None for a global batch of fewer frames than ranks: the same answer on every rank, no step."""
+        s = self.s
+        image0, image1, image2, sparse_depth0, intrinsics = frames
+        shard = n_global = None
+        if self.world > 1:
+            n_global = self.train_loader.global_batch_size(batch)
+            if not dist.every_rank_has_frames(n_global, self.world):
+                return None
+            shard = (dist.shard_bounds(n_global, self.rank, self.world)[0], n_global)
+        self.train_step = self.train_step + 1
+        image0, image1, image2, sparse_depth0, filtered_sparse_depth0, filtered_validity_map_depth0 = transforms.train_inputs(
+            self.train_transforms, image0, image1, image2, sparse_depth0, self.schedules.augmentation_probability,
+            kernel_size=s.outlier_removal_kernel_size, threshold=s.outlier_removal_threshold, shard=shard)
+        output_depth0 = self.depth_model.forward(image=image0, sparse_depth=sparse_depth0,
+                                                 validity_map_depth=filtered_validity_map_depth0, intrinsics=intrinsics)
+        pose01 = self.pose_model.forward(image0, image1)
+        pose02 = self.pose_model.forward(image0, image2)
+        loss, loss_info = self.depth_model.compute_loss(
+            image0=image0, image1=image1, image2=image2, output_depth0=output_depth0, sparse_depth0=filtered_sparse_depth0,
+            validity_map_depth0=filtered_validity_map_depth0, intrinsics=intrinsics, pose01=pose01, pose02=pose02,
+            w_color=s.w_color, w_structure=s.w_structure, w_sparse_depth=s.w_sparse_depth, w_smoothness=s.w_smoothness)
+        self.optimizer.zero_grad()
+        loss.backward()
+        if self.averager is not None:
+            self.averager.average(image0.shape[0], n_global)
+        self.optimizer.step()
+        shown = dict(image0=image0, output_depth0=output_depth0, sparse_depth0=filtered_sparse_depth0,
+                     validity_map0=filtered_validity_map_depth0, pose01=pose01, pose02=pose02)
+        return loss, loss_info, shown, n_global
+
+    def global_loss(self, loss_info, n_global):
+        """The global batch's loss, only where the loop waits anyway: the frames' four terms summed over the ranks in fp64, then
+        compute_loss's own expressions -> the loss; loss_info holds it and its terms."""
+        s = self.s
+        terms = dist.sum_over_ranks(loss_info["per_frame"].sum(dim=0)) / n_global
+        color, structure, sparse, smooth = terms.float().unbind(0)
+        loss = s.w_color * color + s.w_structure * structure + s.w_sparse_depth * sparse + s.w_smoothness * smooth
+        loss_info.update(loss_color=color, loss_structure=structure, loss_sparse_depth=sparse, loss_smoothness=smooth, loss=loss)
+        return loss
+
+    def summarise(self, loss_info, shown, n_global):
+        """log_summary of the step: the whole global batch's, by rank 0."""
+        shown = dict(shown, image01=loss_info.pop("image01"), image02=loss_info.pop("image02"), output_depth0=shown["output_depth0"].detach())
+        loss_info.pop("per_frame")      # N x 4, this package's addition: a writer's add_scalar wants one number
+        if self.world > 1:      # rank order is batch order; every n_summary steps, so its cost is not a concern
+            shown = {name: dist.gather_frames(t, n_global, self.rank, self.world) for name, t in shown.items()}
+        if self.main:
+            self.depth_model.log_summary(summary_writer=self.train_summary_writer, tag="train", step=self.train_step, scalars=loss_info,
+                                         n_display=min(self.s.n_batch, self.s.n_summary_display), **shown)
+
+    def checkpoint(self, loss):
+        """The Step= line, the validation, the two checkpoints and a session's state."""
+        s = self.s
+        value = loss.item()      # the loop's wait for the device, where the reference logs the loss
+        time_elapse = (self.seconds_before + time.time() - self.time_start) / 3600
+        time_remain = (self.n_train_step - self.train_step) * time_elapse / self.train_step
+        self.log("Step={:6}/{}  Loss={:.5f}  Time Elapsed={:.2f}h  Time Remaining={:.2f}h".format(
+            self.train_step, self.n_train_step, value, time_elapse, time_remain))
+        self.logged.append((self.train_step, value))
+        if self.train_step >= s.validation_start_step and self.validation_available:
+            self.best_results = validation.validate(
+                depth_model=self.depth_model, dataloader=self.val_dataloader, ground_truths=self.ground_truths, step=self.train_step,
+                best_results=self.best_results, min_evaluate_depth=s.min_evaluate_depth, max_evaluate_depth=s.max_evaluate_depth,
+                device=self.device, summary_writer=self.val_summary_writer, n_summary_display=s.n_summary_display, log_path=self.log_path,
+                outlier_removal_kernel_size=s.outlier_removal_kernel_size, outlier_removal_threshold=s.outlier_removal_threshold,
+                normalized_image_range=s.normalized_image_range)
+        self.write_checkpoints()
+        if self.train_step < self.n_train_step:      # the last step's state follows the loop
+            self.save_state()
+
+    # ---- what a step leaves on the disk ----
+    def write_checkpoints(self):
+        """The two checkpoints of the last step taken: written by rank 0, and their paths noted on every rank, once."""
+        for model, pattern in ((self.depth_model, self.depth_model_checkpoint_path), (self.pose_model, self.pose_model_checkpoint_path)):
+            path = pattern.format(self.train_step)
+            if self.main:
+                self.write(path, lambda part: model.save_model(part, self.train_step, self.optimizer))
+            if path not in self.checkpoints:
+                self.checkpoints.append(path)
+
+    def snapshot(self, digest=None):
+        """What a continuation needs beyond the two checkpoints; no wait for the device."""
+        return {"step": self.train_step, "epoch": self.epoch, "batch": self.batch + 1, "loader": self.train_loader.state_dict(),
+                "transforms": self.train_transforms.state_dict(), "random": random_state(self.device),
+                "best_results": {k: _plain(v) for k, v in self.best_results.items()}, "logged": list(self.logged),
+                "seconds": self.seconds_before + time.time() - self.time_start, "digest": digest}
+
+    def save_state(self, digest=None):
+        """A session's state of the last step taken, by rank 0."""
+        if self.session is not None and self.main:
+            self.session.save_state(self.snapshot(digest))
+
+    # ---- the end ----
+    def finish(self):
+        """After the last step: the final checkpoints, the digest, the last state, and no rank leaves before rank 0 has written."""
+        if not self.stopped:
+            self.write_checkpoints()
+        if self.world > 1 or (self.session is not None and (self.s.return_results or not self.stopped)):
+            self.digest = replica_digest((self.depth_model, self.pose_model), self.optimizer)
+        if not self.stopped:
+            self.save_state(self.digest)
+        if self.world > 1:
             dist.barrier()      # no rank leaves, and nobody reads the checkpoints or the state, before rank 0 has written them
-    except BaseException:
-        for writer in (train_summary_writer, val_summary_writer):
-            if writer is not None:
-                try:
-                    writer.close()
-                except Exception:      # noqa: BLE001  (the run's own exception is the one to see)
-                    pass
-        raise
-    if main:
-        try:
-            train_summary_writer.close()
-        finally:
-            val_summary_writer.close()
-    if not return_results:
-        return None
-    results = {"train_step": train_step, "best_results": best_results}
-    if world > 1:
-        results["digest"] = digest      # of this rank's replica: the one value that may differ between ranks, and must not
-    if session is not None:
-        results.update(finished=not stopped, resumed_from=None if state is None else state["step"], digest=digest)
-    return results, logged, checkpoints
+
+    def results(self):
+        if not self.s.return_results:
+            return None
+        results = {"train_step": self.train_step, "best_results": self.best_results}
+        if self.world > 1:
+            results["digest"] = self.digest      # of this rank's replica: the one value that may differ between ranks, and must not
+        if self.session is not None:
+            results.update(finished=not self.stopped, resumed_from=self.resumed_from, digest=self.digest)
+        return results, self.logged, self.checkpoints
 
 
 def train_ranks(*arguments, **keywords):
@@ -823,9 +885,8 @@ def train_resumable(*arguments, max_steps=None, max_seconds=None, stop_signals=(
     One process, one GPU.  A data-parallel run (train_ranks, launch) is continued by train_ranks_resumable() and
     launch_resumable() below."""
     bound = _TRAIN_SIGNATURE.bind(*arguments, **keywords)
-    budget = Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals)
-    session = _Session(budget, keep_states)
-    with budget:
+    session = _new_session(max_steps, max_seconds, stop_signals, keep_states)
+    with session.budget:
         return _train_loop(*bound.args, **bound.kwargs, session=session)
 
 
@@ -855,9 +916,8 @@ def train_ranks_resumable(*arguments, max_steps=None, max_seconds=None, stop_sig
         other bits from there on.
     With return_results every rank returns the same values."""
     bound = _RANKS_SIGNATURE.bind(*arguments, **keywords)
-    budget = Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals)
-    session = _Session(budget, keep_states)
-    with budget:
+    session = _new_session(max_steps, max_seconds, stop_signals, keep_states)
+    with session.budget:
         return _train_loop(*bound.args, **bound.kwargs, session=session)
 
 
@@ -915,15 +975,21 @@ def launch(n_gpus, *, backend="nccl", devices=None, timeout=None, **train_argume
     with a non-zero status, or `timeout` seconds for the whole run (None: no limit), ends the others; launch then raises KbnError
     with that rank's last lines of stderr."""
     world, devices, checkpoint_path, threads = _launch_checks("launch", n_gpus, backend, devices, timeout, train_arguments)
+    arguments_path, results_path = _write_launch_arguments(checkpoint_path, backend=backend, devices=devices, train=train_arguments, threads=threads)
+    _run_children("launch", _child_command(arguments_path), devices, checkpoint_path, threads, timeout)
+    return _launch_results("launch", results_path)
+
+
+def _write_launch_arguments(checkpoint_path, **travelling):
+    """What the ranks of a launch read, into checkpoint_path/launch-arguments.pkl: `travelling`, the caller's random state and where
+    rank 0 leaves its results; an older results file goes -> (the arguments file, the results file)."""
     os.makedirs(checkpoint_path, exist_ok=True)
     arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
     if os.path.exists(results_path):
         os.remove(results_path)
     with open(arguments_path, "wb") as f:
-        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
-                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed())}, f)
-    _run_children("launch", _child_command(arguments_path), devices, checkpoint_path, threads, timeout)
-    return _launch_results("launch", results_path)
+        pickle.dump(dict(travelling, results=results_path, random=(np.random.get_state(), torch.get_rng_state(), torch.initial_seed())), f)
+    return arguments_path, results_path
 
 
 def _launch_checks(what, n_gpus, backend, devices, timeout, train_arguments):
@@ -1065,29 +1131,19 @@ def launch_resumable(n_gpus, *, backend="nccl", devices=None, timeout=None, max_
     bits differ from there on."""
     what = "launch_resumable"
     world, devices, checkpoint_path, threads = _launch_checks(what, n_gpus, backend, devices, timeout, train_arguments)
-    _Session(Budget(max_steps=max_steps, max_seconds=max_seconds, stop_signals=stop_signals), keep_states)      # their refusals
+    _new_session(max_steps, max_seconds, stop_signals, keep_states)      # their refusals
     stop_signals = [int(number) for number in (stop_signals or ())]
     state, _ = find_state(checkpoint_path)
     if state is not None:
         bound = _RANKS_SIGNATURE.bind(**train_arguments, rank=0, world=world)
         bound.apply_defaults()
-        given = dict(bound.arguments)
-        contents = {name: loader.read_paths(given[name]) for name in PATH_ARGUMENTS[:3]}
-        if all(given[name] is not None for name in PATH_ARGUMENTS[3:]):
-            contents.update((name, loader.read_paths(given[name])) for name in PATH_ARGUMENTS[3:])
-        check_argument_record(state["arguments"], argument_record(given, contents))
-        if state["step"] >= n_train_steps(len(contents[PATH_ARGUMENTS[0]]), given["n_batch"], given["learning_schedule"], world=world):
+        _, _, finished = _resume_point(dict(bound.arguments), world, state)      # the loop's own check and answer
+        if finished:
             return _stored_results(state)
 
-    os.makedirs(checkpoint_path, exist_ok=True)
-    arguments_path, results_path = os.path.join(checkpoint_path, ARGUMENTS_FILE), os.path.join(checkpoint_path, RESULTS_FILE)
-    if os.path.exists(results_path):
-        os.remove(results_path)
-    with open(arguments_path, "wb") as f:
-        pickle.dump({"backend": backend, "devices": devices, "train": train_arguments, "results": results_path, "threads": threads,
-                     "random": (np.random.get_state(), torch.get_rng_state(), torch.initial_seed()),
-                     "session": {"max_steps": max_steps, "max_seconds": max_seconds, "stop_signals": stop_signals,
-                                 "keep_states": keep_states}}, f)
+    arguments_path, results_path = _write_launch_arguments(
+        checkpoint_path, backend=backend, devices=devices, train=train_arguments, threads=threads,
+        session={"max_steps": max_steps, "max_seconds": max_seconds, "stop_signals": stop_signals, "keep_states": keep_states})
     mark = "==== {}: a session {} ====".format(what, "from the start" if state is None else "after step {}".format(state["step"]))
     with _Arrivals(stop_signals) as arrivals:
         _run_children(what, _child_command(arguments_path, stop_signals), devices, checkpoint_path, threads, timeout,
@@ -1105,11 +1161,10 @@ def _rank_main(arguments_path: str, early=None) -> None:
     limits = arguments.get("session")
     if limits is None:
         return _rank_run(arguments, None)
-    budget = Budget(max_steps=limits["max_steps"], max_seconds=limits["max_seconds"], stop_signals=limits["stop_signals"])
-    session = _Session(budget, limits["keep_states"])
-    with budget:
+    session = _new_session(**limits)
+    with session.budget:
         if early:
-            budget.signalled = early[0]
+            session.budget.signalled = early[0]
         return _rank_run(arguments, session)
 
 

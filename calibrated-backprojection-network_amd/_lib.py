@@ -191,6 +191,7 @@ SIGNATURES = {
     "kbn_deconv2x_forward": (_I, [_P, _L, _P, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
     "kbn_upconv2x_query": (_I, [_I, _I, _I, _I, _I, C.POINTER(_I)]),
     "kbn_conv2d_query": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "kbn_conv_last_route": (_I, [C.POINTER(_I)]),
     "kbn_kb_block_forward": (_I, [_P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _L, _P,
                                   _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "kbn_kb1_front_packed_weight_bytes": (C.c_size_t, [_I, _I, _I]),

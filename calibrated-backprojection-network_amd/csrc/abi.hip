@@ -39,6 +39,11 @@ struct KnobInit {
 } g_knob_init;   // runs when the shared library is loaded
 }  // namespace
 
+ConvRoute& conv_route() {
+    static thread_local ConvRoute route{};
+    return route;
+}
+
 int device_cu_count() {
     static std::atomic<int> cache[256];
     int dev = 0;
@@ -73,6 +78,12 @@ int kbn_knob(const char* name) {
     for (int k = 0; k < kbn::KNOB_COUNT; ++k)
         if (!strcmp(name, kbn::kKnobNames[k])) return kbn::g_knobs[k].value;
     return 0;
+}
+
+int kbn_conv_last_route(int* info) {
+    if (!info) return KBN_ERR_INVALID_ARGUMENT;
+    memcpy(info, &kbn::conv_route(), sizeof(kbn::ConvRoute));
+    return KBN_OK;
 }
 
 void kbn_reload_env(void) {

@@ -303,6 +303,7 @@ static int dma_variant(ConvParams& p, hipStream_t stream) {
         p.nblocks = (int)nb64;
         hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds, stream, p);
         KBN_CHECK_LAUNCH();
+        route_conv(SYN ? ROUTE_DMA_SYN : ROUTE_DMA, KS, STRIDE, CK, NB, MW, TWB, p.epi_lds);
         return KBN_OK;
     }
 }

@@ -312,6 +312,7 @@ static int launch_variant(const ConvParams& p, size_t stage_bytes, hipStream_t s
     if (lds_bytes > 160 * 1024) return KBN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds_bytes, stream, p);
     KBN_CHECK_LAUNCH();
+    route_conv(PIPE ? ROUTE_IGEMM_PIPE : ROUTE_IGEMM, KS, STRIDE, CK, NB, MW, p.TWB, 0);
     return KBN_OK;
 }
 
@@ -387,10 +388,10 @@ static int cand_of_tile(TileChoice t) {
     return a * 3 + b2;
 }
 
-int conv2d_launch(const kbn_conv_src* srcs, int n_src, const float* packed_weight, float* out,
-                  long long out_batch_stride, int n, int out_channels, int kernel_size, int stride,
-                  int in_height, int in_width, int resize, int apply_activation, float negative_slope,
-                  unsigned* out_absmax, hipStream_t stream) {
+static int conv2d_dispatch(const kbn_conv_src* srcs, int n_src, const float* packed_weight, float* out,
+                           long long out_batch_stride, int n, int out_channels, int kernel_size, int stride,
+                           int in_height, int in_width, int resize, int apply_activation, float negative_slope,
+                           unsigned* out_absmax, hipStream_t stream) {
     if (!srcs || !packed_weight || !out) return KBN_ERR_INVALID_ARGUMENT;
     if (n_src < 1 || n_src > KBN_MAX_SRC || n < 1 || out_channels < 1 || in_height < 1 || in_width < 1)
         return KBN_ERR_INVALID_ARGUMENT;
@@ -500,6 +501,18 @@ int conv2d_launch(const kbn_conv_src* srcs, int n_src, const float* packed_weigh
                           : launch_nb<3, 2, 8>(p, pl.NB, tc.MW, lds, stream);
     if (stride == 2) return launch_nb<1, 2, 16>(p, pl.NB, tc.MW, lds, stream);
     return launch_nb<1, 1, 16>(p, pl.NB, tc.MW, lds, stream);
+}
+
+// The route record (kbn_common.h) is the launchers' own: cleared here, written where a kernel was launched, cleared again on failure.
+int conv2d_launch(const kbn_conv_src* srcs, int n_src, const float* packed_weight, float* out,
+                  long long out_batch_stride, int n, int out_channels, int kernel_size, int stride,
+                  int in_height, int in_width, int resize, int apply_activation, float negative_slope,
+                  unsigned* out_absmax, hipStream_t stream) {
+    route_clear();
+    const int rc = conv2d_dispatch(srcs, n_src, packed_weight, out, out_batch_stride, n, out_channels, kernel_size, stride,
+                                   in_height, in_width, resize, apply_activation, negative_slope, out_absmax, stream);
+    if (rc != KBN_OK) route_clear();
+    return rc;
 }
 
 }  // namespace kbn

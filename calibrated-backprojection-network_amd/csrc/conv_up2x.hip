@@ -554,6 +554,7 @@ static int up2x_dma_variant(Up2xParams& p, hipStream_t stream) {
     p.nblocks = (int)nb64;
     hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), 2 * sizeof(float) * G::BUF, stream, p);
     KBN_CHECK_LAUNCH();
+    route_up2x(ROUTE_UP2X_DMA, NB, MW, TWB, T3 ? 3 : 4, GR == 4 ? 16 : 4, NB >= 3 && MW == 1);
     return KBN_OK;
 }
 
@@ -565,6 +566,7 @@ static int up2x_variant(const Up2xParams& p, size_t lds, hipStream_t stream) {
     if (p.rowsS * p.colsS > MAXPOS * 256) return KBN_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), lds, stream, p);
     KBN_CHECK_LAUNCH();
+    route_up2x(ROUTE_UP2X, NB, MW, p.TWB, 4, 0, NB >= 3 && MW == 1);
     return KBN_OK;
 }
 
@@ -808,6 +810,7 @@ static int up2x9_variant(Up2xParams& p, hipStream_t stream) {
     p.nblocks = (int)nb64;
     hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(256), 2 * sizeof(float) * G::BUF, stream, p);
     KBN_CHECK_LAUNCH();
+    route_up2x(ROUTE_UP2X9, NB, MW, TWB, 9, 16, 0);
     return KBN_OK;
 }
 
@@ -874,9 +877,9 @@ int kbn_upconv2x_pack_weight(const float* weight, float* packed, int out_channel
     return KBN_OK;
 }
 
-static int upconv2x_forward_impl(const float* src, long long src_batch_stride, const float* packed_weight, float* out,
-                                 long long out_batch_stride, int n, int in_channels, int out_channels, int src_height,
-                                 int src_width, int apply_activation, float negative_slope, kbn_stream_t stream, bool plain = false) {
+static int upconv2x_dispatch(const float* src, long long src_batch_stride, const float* packed_weight, float* out,
+                             long long out_batch_stride, int n, int in_channels, int out_channels, int src_height,
+                             int src_width, int apply_activation, float negative_slope, kbn_stream_t stream, bool plain) {
     // `plain`: the blob holds four-phase weights only (kbn_deconv2x_pack_weight) -- the 3- and 9-product forms rest on the nearest-2x fold
     using namespace kbn;
     if (!src || !packed_weight || !out || n < 1 || in_channels < 1 || out_channels < 1 || src_height < 1 ||
@@ -988,6 +991,17 @@ static int upconv2x_forward_impl(const float* src, long long src_batch_stride, c
         case 3: return mw == 1 ? up2x_variant<3, 1, 1>(p, lds, st) : up2x_variant<3, 2, 1>(p, lds, st);
         default: return mw == 1 ? up2x_variant<4, 1, 1>(p, lds, st) : up2x_variant<4, 2, 1>(p, lds, st);
     }
+}
+
+// The route record (kbn_common.h): cleared on entry, written where a kernel was launched, cleared again on failure.
+static int upconv2x_forward_impl(const float* src, long long src_batch_stride, const float* packed_weight, float* out,
+                                 long long out_batch_stride, int n, int in_channels, int out_channels, int src_height,
+                                 int src_width, int apply_activation, float negative_slope, kbn_stream_t stream, bool plain = false) {
+    kbn::route_clear();
+    const int rc = upconv2x_dispatch(src, src_batch_stride, packed_weight, out, out_batch_stride, n, in_channels, out_channels,
+                                     src_height, src_width, apply_activation, negative_slope, stream, plain);
+    if (rc != KBN_OK) kbn::route_clear();
+    return rc;
 }
 
 int kbn_upconv2x_forward(const float* src, long long src_batch_stride, const float* packed_weight, float* out,

@@ -489,6 +489,8 @@ static int wino_variant(const WinoParams& p, size_t lds, hipStream_t stream) {
     const int grid = p.nblocks < n_cu ? p.nblocks : n_cu;
     hipLaunchKernelGGL(conv_wino_kernel<DBG>, dim3(grid), dim3(512), lds, stream, p);
     KBN_CHECK_LAUNCH();
+    route_conv(ROUTE_WINO, 3, 1, WCK, WNT / 16, 0, 0, 0);
+    conv_route().wino_rt = p.RT; conv_route().wino_ct = p.CT;
     return KBN_OK;
 }
 

@@ -162,6 +162,32 @@ __device__ __forceinline__ int nearest_src_index(int dst, int in_size, int out_s
     return s < in_size - 1 ? s : in_size - 1;
 }
 
+// ---- route record of the fp32 conv family (kbn_conv_last_route) ------------------------------------------
+// HOST bookkeeping only: which kernel instantiation conv2d_launch / the 2x up-conv launcher last launched on the calling
+// thread, written by the launcher of that instantiation right after its launch succeeded.  The entry points clear it when
+// they are entered and again when they fail, so a declined or failed call reads as family 0.  Field order = kbn_conv_last_route's.
+enum RouteFamily {
+    ROUTE_NONE = 0, ROUTE_WINO = 1, ROUTE_DMA = 2, ROUTE_DMA_SYN = 3, ROUTE_IGEMM_PIPE = 4, ROUTE_IGEMM = 5,
+    ROUTE_UP2X9 = 6, ROUTE_UP2X_DMA = 7, ROUTE_UP2X = 8
+};
+struct ConvRoute {
+    int family, ks, stride, ck, nb, mw, twb, wino_rt, wino_ct, epi_lds, up_form, up_granule, up_half, reserved[3];
+};
+static_assert(sizeof(ConvRoute) == KBN_CONV_ROUTE_FIELDS * sizeof(int), "kbn_conv_last_route copies the struct as ints");
+ConvRoute& conv_route();   // abi.hip: the calling thread's record
+inline void route_clear() { conv_route() = ConvRoute{}; }
+inline void route_conv(int family, int ks, int stride, int ck, int nb, int mw, int twb, int epi_lds) {
+    ConvRoute r{};
+    r.family = family; r.ks = ks; r.stride = stride; r.ck = ck; r.nb = nb; r.mw = mw; r.twb = twb; r.epi_lds = epi_lds;
+    conv_route() = r;
+}
+inline void route_up2x(int family, int nb, int mw, int twb, int form, int granule, int half) {
+    ConvRoute r{};
+    r.family = family; r.ks = 3; r.stride = 1; r.ck = 8; r.nb = nb; r.mw = mw; r.twb = twb;
+    r.up_form = form; r.up_granule = granule; r.up_half = half;
+    conv_route() = r;
+}
+
 // conv_igemm.hip
 int conv2d_launch(const kbn_conv_src* srcs, int n_src, const float* packed_weight, float* out,
                   long long out_batch_stride, int n, int out_channels, int kernel_size, int stride,

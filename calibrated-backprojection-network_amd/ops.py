@@ -166,6 +166,23 @@ def conv_plan(n: int, out_channels: int, in_channels: int, kernel_size: int, str
     return _PLAN_CACHE[key]
 
 
+ROUTE_FAMILIES = ("none", "wino", "dma", "dma_syn", "igemm_pipe", "igemm", "up2x9", "up2x_dma", "up2x")
+_ROUTE_FIELDS = ("family", "KS", "STRIDE", "CK", "NB", "MW", "TWB", "RT", "CT", "epi_lds", "form", "granule", "half")
+
+
+def last_conv_route() -> dict:
+    """What the calling thread's LAST conv2d / conv2d_kbnet / upconv2x / deconv2x call really launched (kbn_conv_last_route;
+    conv_plan and PROFILE's names are predictions from the shape).  `family` is one of ROUTE_FAMILIES ("none": the call
+    failed or found no kernel); KS, STRIDE, CK, NB, MW, TWB are the template arguments of the kernel that ran, RT x CT the
+    Winograd region, `epi_lds` the LDS epilogue in effect, `form` / `granule` / `half` the up-conv's algebraic form
+    (9 / 3 / 4), DMA granule in bytes (16 / 4 / 0) and half-size tile."""
+    info = (C.c_int * 16)()
+    check(_lib.load().kbn_conv_last_route(info), "kbn_conv_last_route")
+    d = dict(zip(_ROUTE_FIELDS, info))
+    d["family"] = ROUTE_FAMILIES[d["family"]]
+    return d
+
+
 def _require(t: torch.Tensor, name: str, ndim: Optional[int] = None):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise KbnError(f"{name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
@@ -436,8 +453,17 @@ def pair_src(t: PairTensor, name="src") -> ConvSrc:
     return s
 
 
-def coords_src(kinv: torch.Tensor) -> ConvSrc:
+def _kinv(kinv: torch.Tensor) -> torch.Tensor:
+    """The N x 3 x 3 inverse intrinsics as the dense row-major block the kernels read through a raw pointer (torch.linalg.inv
+    hands back column-major matrices: read in place they would be their transposes)."""
     _require(kinv, "kinv", 3)
+    if tuple(kinv.shape[1:]) != (3, 3):
+        raise KbnError(f"kinv must be N x 3 x 3, got {tuple(kinv.shape)}")
+    return kinv.contiguous()
+
+
+def coords_src(kinv: torch.Tensor) -> ConvSrc:
+    kinv = _kinv(kinv)
     s = ConvSrc()
     s.kind = _lib.KBN_SRC_COORDS
     s.channels = 3
@@ -464,7 +490,7 @@ def xyz_src(depth: torch.Tensor, proj_weight: torch.Tensor, kinv: Optional[torch
         s.coordinates = coordinates.data_ptr()
         s.coordinates_batch_stride = coordinates.stride(0)
     else:
-        _require(kinv, "kinv", 3)
+        kinv = _kinv(kinv)
         s.kinv = kinv.data_ptr()
     s._keep = (depth, proj_weight, kinv, coordinates)
     return s

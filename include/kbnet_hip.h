@@ -366,6 +366,17 @@ int kbn_kb_xyz_s2_forward(const float* depth, long long depth_batch_stride, int 
 int kbn_conv2d_query(int n, int out_channels, int in_channels, int kernel_size, int stride,
                      int in_height, int in_width, int resize, int* info);
 
+/* What the LAST kbn_conv2d_forward / kbn_upconv2x_forward / kbn_deconv2x_forward of the calling thread actually launched (the two
+ * queries above predict from the shape alone and assume aligned, dense tensor sources).  Written on the host at the point of
+ * the successful launch; a call that failed or found no kernel leaves family 0; with first-use tuning on it is the final launch's.
+ * info[KBN_CONV_ROUTE_FIELDS] = {family, kernel_size, stride, CK, NB, MW, TWB, Winograd RT, Winograd CT, LDS epilogue in effect,
+ * up-conv form (9 / 3 / 4 products or phases), up-conv DMA granule in bytes (16 / 4 / 0), up-conv half-size tile, 0, 0, 0}.
+ * family: 0 none, 1 conv_wino_kernel, 2 conv_dma_kernel, 3 conv_dma_kernel with generic (SYN) staging, 4 conv_igemm_kernel
+ * pipelined, 5 conv_igemm_kernel not pipelined, 6 conv_up2x9_kernel, 7 conv_up2x_dma_kernel, 8 conv_up2x_kernel.  The numbers
+ * are the template arguments of the kernel that ran (the up-convs report kernel 3 stride 1, the conv behind the 2x fold). */
+#define KBN_CONV_ROUTE_FIELDS 16
+int kbn_conv_last_route(int* info);
+
 /* ----------------------------------------------------------- KB block ----------
  * net_utils.CalibratedBackprojectionBlock.forward(image, depth, coordinates, fused)
  *                                                  reference src/net_utils.py:1343-1371

@@ -8,27 +8,10 @@ import torch
 import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import kbnet_amd as kb
 from oracle import kbnet_oracle as orc
-
-BT_ = torch.tensor([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=torch.float32)
-G_ = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float32)
-AT_ = torch.tensor([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=torch.float32)
-
-
-def winograd_conv3x3(x, w):
-    n, c, h, wd = x.shape
-    BT, G, AT = BT_.to(x.dtype), G_.to(x.dtype), AT_.to(x.dtype)
-    he, we = h + (h & 1), wd + (wd & 1)
-    xp = F.pad(x, (1, 1 + we - wd, 1, 1 + he - h))
-    d = xp.unfold(2, 4, 2).unfold(3, 4, 2)                       # n c th tw 4 4
-    v = torch.einsum("ij,nctujk,lk->nctuil", BT, d, BT)          # B^T d B
-    u = torch.einsum("ij,ocjk,lk->ocil", G, w, G)                # G g G^T
-    m = torch.einsum("ocil,nctuil->notuil", u, v)
-    y = torch.einsum("ij,notujk,lk->notuil", AT, m, AT)          # n o th tw 2 2
-    th, tw = y.shape[2], y.shape[3]
-    y = y.permute(0, 1, 2, 4, 3, 5).reshape(n, w.shape[0], 2 * th, 2 * tw)
-    return y[:, :, :h, :wd]
+from conv_route_cases import winograd_conv3x3   # the fp32 F(2x2,3x3) evaluation the Winograd gate is measured with
 
 
 def run(frames, sds, cfg, dtype, wino_min_cin=None):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import kbnet_amd as kb
+import conv_route_cases as rc
 from conftest import load_golden, rel_err
 from oracle import kbnet_oracle as orc
 
@@ -30,6 +31,26 @@ def dev():
 
 def to(dev, *ts):
     return [t.to(dev) if torch.is_tensor(t) else t for t in ts]
+
+
+def profiled(fn):
+    """fn()'s result and the conv_* launches ops.PROFILE recorded for it: the names of what RAN (a kernel that declined is dropped
+    from the profile), so a module that took a split-operand kernel shows conv_split*."""
+    kb.ops.PROFILE = []
+    try:
+        out = fn()
+        return out, [r[0] for r in kb.ops.PROFILE if r[0].startswith("conv_")]
+    finally:
+        kb.ops.PROFILE = None
+
+
+def takes_split(cin, cout, k):
+    """Conv2d.run_split's conditions for one dense source: the layers the fp32 kernels no longer see by default."""
+    return k == 3 and cin % 16 == 0 and cout >= 48
+
+
+def route():
+    return kb.ops.last_conv_route()
 
 
 # ------------------------------------------------------------------------------ S2D
@@ -136,9 +157,19 @@ def test_conv2d_vs_oracle(dev, cin, cout, k, stride, n, h, w, slope):
     conv = kb.modules.Conv2d(cin, cout, k, stride, "xavier_normal",
                              torch.nn.LeakyReLU(slope) if slope is not None else None).to(dev)
     conv.conv.weight.data.copy_(wt)
-    out = conv(x.to(dev))
+    out, names = profiled(lambda: conv(x.to(dev)))
     assert out.shape == ref.shape
     assert rel_err(out, ref) < TIGHT
+    # which kernel that was: a split-operand one for the wide 3x3 layers, else the fp32 family's -- and then the same layer on the
+    # fp32 kernel its comment in CONV_CASES names
+    split = takes_split(cin, cout, k)
+    assert len(names) == 1 and names[0].startswith("conv_split") == split, names
+    if split:
+        conv.split = False
+        out = conv(x.to(dev))
+        assert out.shape == ref.shape
+        assert rel_err(out, ref) < TIGHT
+    assert route()["family"] == rc.conv_family(cin, cout, k, stride, w), route()
 
 
 def test_conv2d_repacks_after_weight_update(dev):
@@ -175,9 +206,19 @@ def test_upconv2x_wide_outputs_any_alignment(dev, cin, cout, hw):
     ref = orc.conv2d(torch.nn.functional.interpolate(x, size=(2 * h, 2 * w), mode="nearest"), wt, 1, 0.2)
     up = kb.modules.UpConv2d(cin, cout, 3, "xavier_normal", torch.nn.LeakyReLU(0.2)).to(dev)
     up.conv.conv.weight.data.copy_(wt)
-    first = up(x.to(dev), (2 * h, 2 * w)).clone()
+    first, names = profiled(lambda: up(x.to(dev), (2 * h, 2 * w)).clone())
     assert rel_err(first, ref) < TIGHT
     assert torch.equal(up(x.to(dev), (2 * h, 2 * w)), first)   # tuned geometry, same bits
+    # the folded split-operand kernel takes the aligned 64 -> 64 cases first: the kernels the docstring names run with split_up off
+    split = cin % 16 == 0 and w % 2 == 0 and cout >= 48
+    assert names == (["conv_split_upfold"] if split else ["conv_up2x"]), names
+    if split:
+        up.split_up = False
+        first, names = profiled(lambda: up(x.to(dev), (2 * h, 2 * w)).clone())
+        assert names == ["conv_up2x"] and rel_err(first, ref) < TIGHT
+        assert torch.equal(up(x.to(dev), (2 * h, 2 * w)), first)
+    family, granule = rc.up_route(cin, cout, w)
+    assert (route()["family"], route()["granule"]) == (family, granule) and family != "up2x", route()
 
 
 # cin, cout, source (h, w): fp32 four-phase kernels (narrow / unaligned layers: DMA tiles, dword granules, the general kernel) and the
@@ -215,6 +256,9 @@ def test_transpose_conv2d_vs_torch(dev, cin, cout, hw):
         kb.ops.PROFILE = None
     split = cin % 16 == 0 and (2 * w) % 4 == 0 and (cout >= 48 or (cout <= 16 and cin % 32 == 0))
     assert names == (["conv_split_upfold"] if split else ["conv_up2x"]), names
+    if not split:     # which fp32 kernel: always the four-phase form, by DMA where the channels and the rows allow
+        family, granule = rc.up_route(cin, cout, w, plain=True)
+        assert (route()["family"], route()["granule"], route()["form"]) == (family, granule, 4), route()
     assert torch.equal(kb.ops.slot_values(slot), out.abs().amax(dim=(1, 2, 3)))
     assert rel_err(out, ref32) < TIGHT
     rms = ref64.pow(2).mean(dim=(2, 3), keepdim=True).sqrt()
@@ -284,8 +328,10 @@ def test_winograd_matches_direct_kernel(dev, kenv):
     conv = kb.modules.Conv2d(96, 64, 3, 1, "xavier_normal", torch.nn.LeakyReLU(0.2)).to(dev)
     conv.split = False               # the fp32-MFMA kernels (the split-operand kernel would take this shape first)
     a = conv(x).clone()
+    assert route()["family"] == "wino", route()
     kenv.setenv("KBN_NO_WINO", "1")
     b = conv(x).clone()
+    assert route()["family"] == "dma" and (route()["KS"], route()["STRIDE"], route()["CK"], route()["NB"]) == (3, 1, 8, 4), route()
     assert rel_err(a, b) < TIGHT
     assert not torch.equal(a, b)  # two different kernels did run
 
@@ -313,20 +359,46 @@ def test_first_use_tuning_keeps_results_bitwise(dev):
     for cin, cout, k, stride, h, w in ((48, 96, 3, 2, 46, 88), (64, 64, 3, 1, 26, 52), (51, 48, 1, 2, 30, 52)):
         x = torch.randn(2, cin, h, w, generator=g).to(dev)
         conv = kb.modules.Conv2d(cin, cout, k, stride, "xavier_normal", torch.nn.LeakyReLU(0.2)).to(dev)
-        first = conv(x).clone()          # the cost model's choice, nothing timed
+        first, names = profiled(lambda: conv(x).clone())          # the cost model's choice, nothing timed
         with kb.ops.autotune():
             assert lib.kbn_get_autotune() == 1
             assert torch.equal(conv(x), first)     # candidates are timed here
         assert lib.kbn_get_autotune() == 0
         for _ in range(3):
             assert torch.equal(conv(x), first)     # the cached winner
+        # the two 3x3 shapes run a split-operand kernel by default and never reach the fp32 family's tune_pick: once more with
+        # split off, where the route record is the final launch's whatever the tuner timed in between
+        split = takes_split(cin, cout, k)
+        assert names[0].startswith("conv_split") == split, names
+        if split:
+            conv.split = False
+            first = conv(x).clone()
+            family = route()["family"]
+            assert family == rc.conv_family(cin, cout, k, stride, w), route()
+            with kb.ops.autotune():
+                assert torch.equal(conv(x), first)
+                assert route()["family"] == family
+            for _ in range(3):
+                assert torch.equal(conv(x), first)
+                assert route()["family"] == family
+        else:
+            assert route()["family"] == rc.conv_family(cin, cout, k, stride, w), route()
     up = kb.modules.UpConv2d(32, 48, 3, "xavier_normal", torch.nn.LeakyReLU(0.2)).to(dev)
     x = torch.randn(2, 32, 12, 20, generator=g).to(dev)
-    first = up(x, (24, 40)).clone()
+    first, names = profiled(lambda: up(x, (24, 40)).clone())
+    assert names == ["conv_split_upfold"], names
     with kb.ops.autotune():
         assert torch.equal(up(x, (24, 40)), first)
     for _ in range(3):
         assert torch.equal(up(x, (24, 40)), first)
+    up.split_up = False                  # the fp32 up-conv's own tuner (tile width and half-size tiles)
+    first = up(x, (24, 40)).clone()
+    assert (route()["family"], route()["granule"], route()["form"]) == ("up2x_dma", 16, 3), route()
+    with kb.ops.autotune():
+        assert torch.equal(up(x, (24, 40)), first)
+    for _ in range(3):
+        assert torch.equal(up(x, (24, 40)), first)
+        assert (route()["family"], route()["granule"], route()["form"]) == ("up2x_dma", 16, 3), route()
 
 
 def test_every_tile_and_region_shape_keeps_results_bitwise(dev, kenv):
@@ -340,34 +412,65 @@ def test_every_tile_and_region_shape_keeps_results_bitwise(dev, kenv):
         x = torch.randn(2, cin, h, w, generator=g).to(dev)
         conv = kb.modules.Conv2d(cin, cout, k, stride, "xavier_normal", act).to(dev)
         kenv.setenv("KBN_NO_WINO", "1")            # the direct kernels, also for the wide 3x3 case
-        ref = conv(x).clone()
-        for epi in ("0", "2"):                            # plain epilogue / stores through LDS (store-bound layers)
-            kenv.setenv("KBN_EPI_LDS", epi)
-            for mw in (1, 2, 4, 8):
-                for twb in (1, 2, 4):
-                    kenv.setenv("KBN_FORCE_MW", str(mw))
-                    kenv.setenv("KBN_FORCE_TWB", str(twb))
-                    assert torch.equal(conv(x), ref), f"conv {cin}->{cout} k{k} s{stride}: MW={mw} TWB={twb} epi={epi}"
-        kenv.delenv("KBN_EPI_LDS")
-        kenv.delenv("KBN_FORCE_MW")
-        kenv.delenv("KBN_FORCE_TWB")
+        ref, names = profiled(lambda: conv(x).clone())
+        # (48 -> 96, k3 s2) and (64 -> 48, k3 s1) take a split-operand kernel, which no knob below touches: those two run
+        # the whole loop a second time with split off, on the LDS-DMA kernel, where the route must report every forced tile
+        split = takes_split(cin, cout, k)
+        assert names[0].startswith("conv_split") == split, names
+        for fp32 in ((False, True) if split else (True,)):
+            if fp32 and split:
+                conv.split = False
+                ref = conv(x).clone()
+            for epi in ("0", "2"):                            # plain epilogue / stores through LDS (store-bound layers)
+                kenv.setenv("KBN_EPI_LDS", epi)
+                for mw in (1, 2, 4, 8):
+                    for twb in (1, 2, 4):
+                        kenv.setenv("KBN_FORCE_MW", str(mw))
+                        kenv.setenv("KBN_FORCE_TWB", str(twb))
+                        assert torch.equal(conv(x), ref), f"conv {cin}->{cout} k{k} s{stride}: MW={mw} TWB={twb} epi={epi}"
+                        if fp32:
+                            nb = rc.plan_nb(cout)
+                            assert (route()["family"], route()["NB"], route()["MW"], route()["TWB"]) == \
+                                ("dma", nb, min(mw, rc.plan_mw(nb)), twb), (route(), mw, twb)
+            kenv.delenv("KBN_EPI_LDS")
+            kenv.delenv("KBN_FORCE_MW")
+            kenv.delenv("KBN_FORCE_TWB")
         kenv.delenv("KBN_NO_WINO")
     x = torch.randn(2, 64, 44, 72, generator=g).to(dev)
     conv = kb.modules.Conv2d(64, 128, 3, 1, "xavier_normal", act).to(dev)
     assert kb.ops.conv_plan(2, 128, 64, 3, 1, 44, 72)["kernel"] == "wino"
-    ref = conv(x).clone()
+    ref, names = profiled(lambda: conv(x).clone())
+    assert names == ["conv_split"], names             # the split-operand kernel takes 64 -> 128: KBN_WINO_RT is a no-op on it
     for rt in (4, 8, 2, 6, 5, 3, 7, 10):              # every entry of conv_wino.hip's kRegions
         kenv.setenv("KBN_WINO_RT", str(rt))
         assert torch.equal(conv(x), ref), f"Winograd region with {rt} tile rows"
+    kenv.delenv("KBN_WINO_RT")
+    conv.split = False                                # the Winograd kernel itself
+    ref = conv(x).clone()
+    assert route()["family"] == "wino", route()
+    for rt, ct in rc.WINO_REGIONS:
+        kenv.setenv("KBN_WINO_RT", str(rt))
+        assert torch.equal(conv(x), ref), f"Winograd region with {rt} tile rows"
+        assert (route()["family"], route()["RT"], route()["CT"]) == ("wino", rt, ct), route()
     kenv.delenv("KBN_WINO_RT")
     for cin, cout, hw in ((32, 48, (12, 20)), (64, 12, (20, 36)), (64, 64, (11, 38))):
         up = kb.modules.UpConv2d(cin, cout, 3, "xavier_normal", act).to(dev)
         x = torch.randn(2, cin, *hw, generator=g).to(dev)
         shape = (2 * hw[0], 2 * hw[1])
-        ref = up(x, shape).clone()
+        ref, names = profiled(lambda: up(x, shape).clone())
+        assert names == ["conv_split_upfold"], names  # all three: the folded split kernel (the narrow one for 64 -> 12)
         for twb in (1, 2):
             kenv.setenv("KBN_FORCE_TWB", str(twb))
             assert torch.equal(up(x, shape), ref), f"up-conv {cin}->{cout}: TWB={twb}"
+        kenv.delenv("KBN_FORCE_TWB")
+        up.split_up = False                           # conv_up2x.hip's kernels, which do read KBN_FORCE_TWB
+        ref = up(x, shape).clone()
+        family, granule = rc.up_route(cin, cout, hw[1])
+        for twb in (1, 2):
+            kenv.setenv("KBN_FORCE_TWB", str(twb))
+            assert torch.equal(up(x, shape), ref), f"fp32 up-conv {cin}->{cout}: TWB={twb}"
+            # (the dword-granule launch has one tile width: its candidates differ in the tile's height)
+            assert (route()["family"], route()["granule"], route()["TWB"]) == (family, granule, twb if granule == 16 else 1), route()
         kenv.delenv("KBN_FORCE_TWB")
 
 

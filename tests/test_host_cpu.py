@@ -144,7 +144,7 @@ def test_library_exports_every_declared_symbol():
     header = open(os.path.join(ROOT, "include", "kbnet_hip.h")).read()
     header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     declared = set(re.findall(r"\b(kbn_[a-z0-9_]+)\s*\(", header))
-    assert {"kbn_s2d_forward", "kbn_conv2d_forward", "kbn_kb_block_forward", "kbn_depth_head_forward"} <= declared
+    assert {"kbn_s2d_forward", "kbn_conv2d_forward", "kbn_kb_block_forward", "kbn_depth_head_forward", "kbn_conv_last_route"} <= declared
     lib_path = kb._lib.LIB_PATH
     if not os.path.exists(lib_path):
         kb._build.build(verbose=False)
@@ -155,6 +155,11 @@ def test_library_exports_every_declared_symbol():
     loaded = kb._lib.load()
     assert loaded.kbn_version() == kb._lib.ABI_VERSION
     assert loaded.kbn_status_string(-2) == b"configuration outside the kernel limits"
+    # the route record: nothing launched on this thread -> family "none"; a refused call (no sources) leaves it there
+    assert loaded.kbn_conv_last_route(None) == kb._lib.KBN_ERR_INVALID_ARGUMENT
+    assert loaded.kbn_conv2d_forward(None, 0, None, None, 0, 1, 1, 3, 1, 4, 4, 0, 0, 0.0, None, None) == kb._lib.KBN_ERR_INVALID_ARGUMENT
+    route = kb.ops.last_conv_route()
+    assert route["family"] == "none" and set(route) == set(kb.ops._ROUTE_FIELDS) and not any(v for k, v in route.items() if k != "family")
     # pure host arithmetic, no GPU needed
     assert loaded.kbn_conv2d_packed_weight_bytes(48, 3, 3, 1) == 4 * 1 * 4 * 9 * 48
     assert loaded.kbn_conv2d_packed_weight_bytes(12, 64, 3, 1) == 4 * 1 * 64 * 9 * 16

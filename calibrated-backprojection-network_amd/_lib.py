@@ -31,6 +31,7 @@ KBN_AUGMENT_STAGE_SELECT, KBN_AUGMENT_STAGE_APPLY = 1, 2
 KBN_AUGMENT_MAX_FRAMES, KBN_AUGMENT_WORKSPACE_RECORD_BYTES = 512, 16   # frames whose flags one launch carries; workspace bytes a frame and range map
 KBN_UNPACK_TRAIN_MAX_FRAMES = 64   # frame records a kbn_unpack_train_frames_forward launch carries
 KBN_UNPACK_PACKED_MAX_RAW_WIDTH = 16384   # widest packed triplet kbn_unpack_packed_frames_forward takes (its LDS budget)
+KBN_UNPACK_SEQUENCE_MAX_FRAMES = 48   # sample records a launch of the two sequence entry points carries
 KBN_PACK_FRAMES_MAX_WIDTH = 16384   # widest plane row kbn_pack_frames_forward takes (its LDS budget)
 KBN_MAX_CHANNELS, KBN_MAX_WEIGHT_ELEMENTS = 1 << 20, 1 << 28   # the conv layers' common range: past it every size function answers 0
 KBN_MAX_MAP_SIDE, KBN_MAX_SIZE_BYTES = 1 << 24, 1 << 62
@@ -128,6 +129,32 @@ class PackedFrame(C.Structure):
         ("depth_bytes", C.c_uint),
         ("height", C.c_int),
         ("raw_width", C.c_int),
+        ("y_start", C.c_int),
+        ("x_start", C.c_int),
+    ]
+
+
+class SequenceFrame(C.Structure):
+    """Mirror of `kbn_sequence_frame` (include/kbnet_hip.h): one sample of a kbn_unpack_sequence_frames_forward call."""
+    _fields_ = [
+        ("image_offset", C.c_longlong * 3),
+        ("depth_offset", C.c_longlong),
+        ("height", C.c_int),
+        ("width", C.c_int),
+        ("y_start", C.c_int),
+        ("x_start", C.c_int),
+    ]
+
+
+class PackedSequenceFrame(C.Structure):
+    """Mirror of `kbn_packed_sequence_frame` (include/kbnet_hip.h): one sample of a kbn_unpack_packed_sequence_frames_forward call."""
+    _fields_ = [
+        ("image_offset", C.c_longlong * 3),
+        ("depth_offset", C.c_longlong),
+        ("image_bytes", C.c_uint * 3),
+        ("depth_bytes", C.c_uint),
+        ("height", C.c_int),
+        ("width", C.c_int),
         ("y_start", C.c_int),
         ("x_start", C.c_int),
     ]
@@ -289,6 +316,8 @@ SIGNATURES = {
     "kbn_frame_decode": (_I, [_P, C.c_size_t, _P, C.c_size_t]),
     "kbn_frame_check": (_I, [_P, C.c_size_t]),
     "kbn_unpack_packed_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(PackedFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "kbn_unpack_sequence_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(SequenceFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "kbn_unpack_packed_sequence_frames_forward": (_I, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(PackedSequenceFrame), _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "kbn_pack_frames_stride": (C.c_size_t, [_I, _I, _I, _I]),
     "kbn_pack_frames_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "kbn_pack_frames_forward": (_I, [_P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),

@@ -50,26 +50,8 @@ __global__ __launch_bounds__(UT_THREADS) void unpack_train_kernel(const UnpackTr
     const int live = VEC ? 4 : min(4, p.width - x0);
     float* const out[3] = {p.image1, p.image0, p.image2};   // by third: t-1, t, t+1
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const unsigned char* s = src + (long long)t * W * C;
-        float* o = out[t] + b * 3 * HW + at;
-        f32x4 v[3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool in = VEC || i < live;
-            const float c0 = in ? (float)s[i * C] : 0.f;
-            v[0][i] = c0;
-            v[1][i] = C >= 3 ? (in ? (float)s[i * C + 1] : 0.f) : c0;
-            v[2][i] = C >= 3 ? (in ? (float)s[i * C + 2] : 0.f) : c0;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) store_quad<VEC>(o + c * HW, v[c], live);
-    }
-    float* od = p.depth + b * HW + at;
-    f32x4 z;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) z[i] = (VEC || i < live) ? (float)sd[i] / 256.0f : 0.f;
-    store_quad<VEC>(od, z, live);
+    for (int t = 0; t < 3; ++t) convert_store_pixels<C, VEC>(src + (long long)t * W * C, out[t] + b * 3 * HW + at, HW, live);
+    convert_store_depth<DepthT, VEC>(sd, p.depth + b * HW + at, live);
 }
 
 template <int C, typename DepthT>

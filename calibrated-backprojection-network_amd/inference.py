@@ -189,11 +189,12 @@ def run_with_format(image_path,
 
     image_path, sparse_depth_path, intrinsics_path, ground_truth_path: newline-delimited files of paths (loader.read_paths);
     ground_truth_path '' or None: no ground truth, no metrics.  As the reference's run() builds KBNetInferenceDataset with its default
-    use_image_triplet=True, every image file is a TRIPLET whose middle third is the frame.  Writes checkpoint_path/results.txt --
+    use_image_triplet=True, every image file is a TRIPLET whose middle third is the frame; an image entry may also be a sequence
+    entry previous<TAB>current<TAB>next, of which `current` is the frame and the only file read.  Writes checkpoint_path/results.txt --
     the input paths, the four settings blocks, the mean and the standard deviation over the frames of each frame's MAE, RMSE [mm],
     iMAE, iRMSE [1/km], the time -- and with save_outputs checkpoint_path/outputs/{image, output_depth, sparse_depth, ground_truth}/
     <name>.png per frame: the normalised image, the output depth, the FILTERED sparse depth, the ground truth's own samples; <name>
-    is '{:010d}.png' of the dataset index, or the image file's base name with keep_input_filenames.
+    is '{:010d}.png' of the dataset index, or the image file's base name (`current`'s, of a sequence entry) with keep_input_filenames.
 
     Returns None, as the reference; with return_results a dict: per_frame (N x 4 fp64 host tensor, None without ground truth), mean
     and std (four floats each, None without ground truth), time_ms, and output_depth, N x 1 x H x W fp32 on the host -- THE WHOLE
@@ -301,7 +302,7 @@ def run_with_format(image_path,
                     rows.append(ops.eval_metrics(output_depth, ground_truth, ground_truth, min_evaluate_depth, max_evaluate_depth))
                 if writer is not None:
                     if keep_input_filenames:
-                        filenames = [os.path.basename(image_paths[seen + i]) for i in range(n)]
+                        filenames = [os.path.basename(loader.sample_name(image_paths[seen + i])) for i in range(n)]
                     else:
                         filenames = ["{:010d}.png".format(seen + i) for i in range(n)]
                     writer.submit(filenames, image, output_depth, filtered_sparse_depth, ground_truth_samples=samples)

@@ -28,6 +28,12 @@ structural check `kbn_frame_check` there, crosses PCIe packed, and `ops.unpack_p
 on the device -- the same tensors bit for bit.  A batch is all PNG or all packed.  `frame_info`, `encode_frame`, `decode_frame`,
 `check_frame` are the host codec.
 
+Sequence entries: an entry of an image path list is the path of a triplet file -- frames t-1, t, t+1 side by side, what the
+reference's setup scripts write -- or `previous<TAB>current<TAB>next`, the three frames by path (`split_sample` is the one place that
+knows the syntax, `sequence_lines` writes such entries for an ordered sequence).  Both loaders then read every distinct file of a batch
+once, PNG or packed, and `ops.unpack_sequence_frames` / `ops.unpack_packed_sequence_frames` build the triplet path's tensors, bit for
+bit, from the frames where they lie; the inference loader reads `current` alone.  A batch is all triplet files or all sequence entries.
+
 Both loaders stage every batch, PNG or packed, the same way (`_Staging`): one set of flat pinned byte buffers per slot,
 `prefetch + 1` of them, grown with 1/8 of headroom when a batch needs more and never touched before the copies that last used it
 are done.  A submit path lays its files out, fills the set and passes its unpack op to `_Staging.submit`, which copies the used
@@ -169,9 +175,19 @@ def decode_frame(data: bytes, out: Optional[np.ndarray] = None) -> np.ndarray:
 def pack_frames(src_png_paths: Sequence[str], dst_paths: Sequence[str], workers: int = 8) -> Tuple[int, int]:
     """Converts PNG files to packed frames, src_png_paths[i] -> dst_paths[i], on `workers` host threads: decoded with the library's
     PNG reader (a palette becomes RGB), encoded with kbn_frame_encode, written under a temporary name and moved into place.
-    Returns (PNG bytes read, packed bytes written)."""
+    A source may be a sequence entry (split_sample); its destination is then one too, frame for frame, and a frame that several
+    entries name is converted once (map_sample rewrites the entries of a list).  Returns (PNG bytes read, packed bytes written)."""
     if len(src_png_paths) != len(dst_paths):
         raise KbnError(f"pack_frames: {len(src_png_paths)} sources, {len(dst_paths)} destinations")
+    if any("\t" in entry for entry in src_png_paths):
+        pairs = {}
+        for src, dst in zip(src_png_paths, dst_paths):
+            srcs, dsts = split_sample(src), split_sample(dst)
+            if (srcs is None) != (dsts is None):
+                raise KbnError(f"pack_frames: {src!r} and its destination {dst!r} must both be one path or both three")
+            for pair in zip(srcs or (src,), dsts or (dst,)):
+                pairs[pair] = None
+        src_png_paths, dst_paths = [a for a, _ in pairs], [b for _, b in pairs]
 
     def one(pair):
         src, dst = pair
@@ -187,6 +203,64 @@ def pack_frames(src_png_paths: Sequence[str], dst_paths: Sequence[str], workers:
     with ThreadPoolExecutor(max_workers=max(1, int(workers))) as ex:
         sizes = list(ex.map(one, zip(src_png_paths, dst_paths)))
     return sum(s[0] for s in sizes), sum(s[1] for s in sizes)
+
+
+# ------------------------------------------------------------------ sequence entries
+def split_sample(entry: str):
+    """An entry of an image path list -> (previous, current, next) where it names its three frames, `previous<TAB>current<TAB>next`
+    (the left-to-right order of the reference's triplet file, load_image_triplet, src/datasets.py:22-46: image1, image0, image2);
+    None for a plain path, a triplet file's.  Two or four fields, or an empty one, raise KbnError."""
+    if "\t" not in entry:
+        return None
+    fields = entry.split("\t")
+    if len(fields) != 3 or not all(fields):
+        raise KbnError(f"a sample names one triplet file, or previous<TAB>current<TAB>next: {entry!r}")
+    return tuple(fields)
+
+
+def sample_name(entry: str) -> str:
+    """The path an output or log name of a sample derives from: `current` of a sequence entry, the entry itself otherwise."""
+    fields = split_sample(entry)
+    return entry if fields is None else fields[1]
+
+
+def map_sample(entry: str, fn) -> str:
+    """`entry` with `fn` applied to its path, or to each of a sequence entry's three."""
+    fields = split_sample(entry)
+    return fn(entry) if fields is None else "\t".join(fn(path) for path in fields)
+
+
+def sequence_lines(frame_paths: Sequence[str], window: int = 1, ends: str = "drop") -> List[str]:
+    """The sequence entries of one ordered sequence of frames: frame idx with its neighbours idx - window and idx + window.
+    ends "drop": frames without both neighbours are left out (the reference's NYUv2 rule, range(w, n - w)); "repeat": the frame
+    itself stands in for a missing neighbour.  window 0: `p<TAB>p<TAB>p`, the reference's validation and testing images."""
+    window = int(window)
+    if window < 0:
+        raise KbnError(f"sequence_lines: window {window}")
+    if ends not in ("drop", "repeat"):
+        raise KbnError(f"sequence_lines: ends {ends!r}: 'drop' or 'repeat'")
+    paths = list(frame_paths)
+    n = len(paths)
+    for path in paths:
+        if not path or "\t" in path or "\n" in path:
+            raise KbnError(f"sequence_lines: {path!r} cannot be a field of an entry")
+    lines = []
+    for idx in range(window, n - window) if ends == "drop" else range(n):
+        before, after = idx - window, idx + window
+        lines.append("\t".join((paths[before] if before >= 0 else paths[idx], paths[idx], paths[after] if after < n else paths[idx])))
+    return lines
+
+
+def _batch_entries(entries: Sequence[str], what: str):
+    """split_sample of a batch's image entries: a list of (previous, current, next), or None where all are triplet files; a batch
+    that mixes the two raises, naming one of each."""
+    fields = [split_sample(entry) for entry in entries]
+    for entry, f in zip(entries, fields):
+        if (f is None) != (fields[0] is None):
+            form = {True: "a triplet file", False: "a sequence entry"}
+            raise KbnError(f"{what}: a batch must be all triplet files or all sequence entries: {entries[0]!r} is {form[fields[0] is None]}, "
+                           f"{entry!r} is {form[f is None]}")
+    return None if fields[0] is None else fields
 
 
 def _image_info(head: bytes) -> Tuple[int, int, int, int]:
@@ -237,26 +311,26 @@ class _FileHeaders(dict):
         return self[path]
 
 
-def _layout(sizes: Sequence[int]) -> Tuple[List[int], List[int]]:
-    """The files of a batch -- its images, then as many depth maps -- laid out in the two flat staging buffers, each file at a
-    16-byte-aligned offset: the offsets, and the bytes the image and the depth buffer need."""
-    nb = len(sizes) // 2
+def _layout(sizes: Sequence[int], images: Optional[int] = None) -> Tuple[List[int], List[int]]:
+    """The files of a batch -- its `images` image files (half of them by default), then its depth maps -- laid out in the two flat
+    staging buffers, each file at a 16-byte-aligned offset: the offsets, and the bytes the image and the depth buffer need."""
+    ni = len(sizes) // 2 if images is None else images
     at, total = [], [0, 0]
     for j, size in enumerate(sizes):
-        at.append(total[j // nb])
-        total[j // nb] = _align16(total[j // nb] + size)
+        at.append(total[j >= ni])
+        total[j >= ni] = _align16(total[j >= ni] + size)
     return at, total
 
 
-def _places(st: dict, at: Sequence[int], sizes: Sequence[int]) -> List[tuple]:
+def _places(st: dict, at: Sequence[int], sizes: Sequence[int], images: Optional[int] = None) -> List[tuple]:
     """(flat pinned numpy view, offset, size) of every file of a batch -- images, then depth maps -- in the staging set `st`."""
-    nb = len(at) // 2
-    return list(zip([st["image"].numpy()] * nb + [st["depth"].numpy()] * nb, at, sizes))
+    ni = len(at) // 2 if images is None else images
+    return list(zip([st["image"].numpy()] * ni + [st["depth"].numpy()] * (len(at) - ni), at, sizes))
 
 
-def _packed_jobs(st: dict, paths, at, sizes, want) -> List[tuple]:
+def _packed_jobs(st: dict, paths, at, sizes, want, images: Optional[int] = None) -> List[tuple]:
     """_read_packed_into's jobs for the files `paths`, planned with the headers `want`, at _layout's offsets."""
-    return [(path, view, a, size, w) for path, (view, a, size), w in zip(paths, _places(st, at, sizes), want)]
+    return [(path, view, a, size, w) for path, (view, a, size), w in zip(paths, _places(st, at, sizes, images), want)]
 
 
 def _load_intrinsics(st: dict, paths: Sequence[str], starts=None) -> None:
@@ -764,7 +838,8 @@ class InferenceFrameLoader:
     reference src/datasets.py:229-257), in order, the last batch possibly short.  All frames must have
     one size.  Batch i+1 is decoded and copied while the caller works on batch i: `prefetch` batches are in flight, each in one
     of `prefetch + 1` staging sets (`_Staging`) that PNG and packed batches share; files are told apart by their first bytes, read
-    once a path."""
+    once a path.  Of a sequence entry `previous<TAB>current<TAB>next` only `current`, a file one frame wide, is read --
+    PNG or packed -- whatever use_image_triplet says; a batch is all triplet files or all sequence entries."""
 
     def __init__(self, image_paths: Sequence[str], sparse_depth_paths: Sequence[str],
                  intrinsics_paths: Sequence[str], use_image_triplet: bool = True, batch_size: int = 8,
@@ -796,17 +871,20 @@ class InferenceFrameLoader:
     def _submit(self, b: int):
         lo, hi = b * self.batch_size, min((b + 1) * self.batch_size, self.n_sample)
         idx = list(range(lo, hi))
-        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
+        entries = _batch_entries([self.image_paths[i] for i in idx], "InferenceFrameLoader")
+        # a sequence entry: `current` is the frame, a file one frame wide; nothing else of the sample is read
+        triplet = self.use_image_triplet and entries is None
+        paths = ([self.image_paths[i] for i in idx] if entries is None else [e[1] for e in entries]) + [self.sparse_depth_paths[i] for i in idx]
         heads = [self._file_header(path) for path in paths]
         if _one_kind(paths, [packed for _, packed in heads], "InferenceFrameLoader"):
-            return self._submit_packed(b, idx, paths, [info for info, _ in heads])
+            return self._submit_packed(b, idx, paths, [info for info, _ in heads], entries is not None)
         files = list(self.pool.map(_read, paths))
         nb = len(idx)
         wraw, hraw, c, bits = png_info(files[0])
         wd, hd, cd, dbits = png_info(files[nb])
         if bits != 8 or cd != 1:
             raise KbnError("InferenceFrameLoader: expected 8-bit images and single-channel depth PNGs")
-        width = wraw // 3 if self.use_image_triplet else wraw
+        width = wraw // 3 if triplet else wraw
         if (hd, wd) != (hraw, width):
             raise KbnError(f"depth map is {hd} x {wd}, image is {hraw} x {width}")
         for j in range(nb):
@@ -821,21 +899,23 @@ class InferenceFrameLoader:
         decode_png_batch(files, [view[a:a + size] for view, a, size in _places(st, at, sizes)], threads=self.workers)
         return self._staging.submit(st, nb * sizes[0], nb * sizes[nb], nb, lambda img_d, dep_d, k_d: tuple(ops.unpack_frames(
             img_d.view(nb, hraw, wraw, c), dep_d.view(torch.int16 if dbits == 16 else torch.uint8).view(nb, hd, wd),
-            width=width, x_offset=width if self.use_image_triplet else 0)) + (k_d,))
+            width=width, x_offset=width if triplet else 0)) + (k_d,))
 
-    def _submit_packed(self, b: int, idx, paths, heads):
+    def _submit_packed(self, b: int, idx, paths, heads, single: bool = False):
         """_submit for a batch of packed frames: the files go as they are into pinned staging, each at a 16-byte-aligned
-        offset, pass kbn_frame_check there, cross PCIe packed, and ONE ops.unpack_packed_frames launch decodes the middle thirds."""
-        if not self.use_image_triplet:
+        offset, pass kbn_frame_check there, cross PCIe packed, and ONE ops.unpack_packed_frames launch decodes the middle thirds.
+        `single`: the image files are the `current` frames of sequence entries, one frame wide; ops.unpack_packed_sequence_frames
+        decodes them, all three places of a sample's record being that one file."""
+        if not self.use_image_triplet and not single:
             raise KbnError("InferenceFrameLoader: packed images are decoded as triplets; use PNG files with use_image_triplet=False")
         nb = len(idx)
         wraw, hraw, c, bits = heads[0]
         wd, hd, cd, dbits = heads[nb]
         if bits != 8 or cd != 1:
             raise KbnError("InferenceFrameLoader: expected 8-bit images and single-channel depth maps")
-        if wraw % 3:
+        if wraw % 3 and not single:
             raise ValueError("array split does not result in an equal division")     # np.split in the reference's load_image_triplet
-        width = wraw // 3
+        width = wraw if single else wraw // 3
         if (hd, wd) != (hraw, width):
             raise KbnError(f"depth map is {hd} x {wd}, image is {hraw} x {width}")
         if any(h != heads[0] for h in heads[:nb]) or any(h != heads[nb] for h in heads[nb:]):
@@ -845,6 +925,10 @@ class InferenceFrameLoader:
         st = self._staging.acquire(b % (self.prefetch + 1), total[0], total[1], nb)
         _load_intrinsics(st, [self.intrinsics_paths[i] for i in idx])
         _read_packed_into(self.pool, _packed_jobs(st, paths, at, sizes, heads))
+        if single:
+            frames = [(at[j], sizes[j]) * 3 + (at[nb + j], sizes[nb + j], hraw, width, 0, 0) for j in range(nb)]
+            return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_packed_sequence_frames(
+                img_d, dep_d, frames, (hraw, width), channels=c, depth_bits=dbits, middle_only=True) + (k_d,))
         frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, width, 0, 0) for j in range(nb)]
         return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_packed_frames(
             img_d, dep_d, frames, (hraw, width), channels=c, depth_bits=dbits, middle_only=True) + (k_d,))
@@ -961,6 +1045,10 @@ class TrainingFrameLoader:
     prefix of each buffer crosses PCIe as raw bytes in one asynchronous copy on a side stream, and `ops.unpack_train_frames`
     splits, crops and converts there.  A batch of packed frames (module docstring; all of a batch's files or none) skips the decode: the
     files themselves go to pinned staging, pass `kbn_frame_check` there, and `ops.unpack_packed_frames` decodes them on the device.
+    An image entry may be a sequence entry `previous<TAB>current<TAB>next` (module docstring) in place of a triplet file: its
+    three frames must have one size and format and its depth map a frame's size, it is planned and cropped as the triplet file of those
+    frames would be (one seed, the same batches), every distinct file of the batch is read once, and `ops.unpack_sequence_frames` /
+    `ops.unpack_packed_sequence_frames` build the tensors.  A batch is all triplet files or all sequence entries.
     `prefetch` batches are in flight, each in one of the `prefetch + 1` staging sets the two kinds share (`_Staging`: a set is grown
     when a batch needs more, after the copies that last used it).  Without a crop (`shape` None or not positive) the frames of
     a batch must have one size.  An error found while a batch is prepared is raised when that batch is due.  One epoch at a time:
@@ -1040,13 +1128,26 @@ class TrainingFrameLoader:
         return min(self.batch_size, self.n_sample - b * self.batch_size)
 
     # -- on the iterating thread: the batch's raw sizes, its checks and its crops --
-    def _header(self, i: int):
-        return tuple(self._file_header(path)[0] for path in (self.image_paths[i], self.sparse_depth_paths[i]))
+    def _header(self, i: int, fields=None):
+        """(header of sample i's image, header of its depth map); `fields`, a sequence entry's three paths: the one header its frames
+        must share."""
+        if fields is None:
+            return tuple(self._file_header(path)[0] for path in (self.image_paths[i], self.sparse_depth_paths[i]))
+        heads = [self._file_header(path)[0] for path in fields]
+        for path, head in zip(fields, heads):
+            if head != heads[0]:
+                raise KbnError(f"TrainingFrameLoader: the three frames of a sample must have one size and format: {path} is {head[1]} x {head[0]} with "
+                               f"{head[2]} channels of {head[3]} bits, {fields[0]} is {heads[0][1]} x {heads[0][0]} with {heads[0][2]} of {heads[0][3]}")
+        return heads[0], self._file_header(self.sparse_depth_paths[i])[0]
 
     def _plan(self, idx: Sequence[int]):
         """[(sample, raw height, raw width of a third, y_start, x_start)], (h, w), channels, depth bits, whether it is cropped.
-        With crops="global" `idx` is a global batch, checked and drawn for as a whole; _enqueue_planned takes the rank's slice."""
-        heads = [self._header(i) for i in idx]
+        With crops="global" `idx` is a global batch, checked and drawn for as a whole; _enqueue_planned takes the rank's slice.
+        A sequence entry is planned as the triplet file of its three frames would be: its raw width is 3 W."""
+        entries = _batch_entries([self.image_paths[i] for i in idx], "TrainingFrameLoader")
+        heads = [self._header(i) for i in idx] if entries is None else [self._header(i, fields) for i, fields in zip(idx, entries)]
+        if entries is not None:
+            heads = [((3 * w, h, ci, bi), depth) for (w, h, ci, bi), depth in heads]
         (_, _, c, bits), (_, _, cd, dbits) = heads[0]
         if bits != 8 or cd != 1:
             raise KbnError(f"TrainingFrameLoader: expected 8-bit images and single-channel depth PNGs ({self.image_paths[idx[0]]}, {self.sparse_depth_paths[idx[0]]})")
@@ -1077,8 +1178,11 @@ class TrainingFrameLoader:
     def _submit(self, slot: int, plan, shape, c: int, dbits: int, cropped: bool):
         nb = len(plan)
         idx = [p[0] for p in plan]
-        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
         starts = [(y, x) for _, _, _, y, x in plan] if cropped else None
+        entries = _batch_entries([self.image_paths[i] for i in idx], "TrainingFrameLoader")
+        if entries is not None:
+            return self._submit_sequence(slot, plan, shape, c, dbits, starts, entries)
+        paths = [self.image_paths[i] for i in idx] + [self.sparse_depth_paths[i] for i in idx]
         if _one_kind(paths, [self._file_header(path)[1] for path in paths], "TrainingFrameLoader"):      # read already unless the plan comes from load_state_dict
             return self._submit_packed(slot, plan, shape, c, dbits, starts, paths)
         files = list(self.pool.map(_read, paths))
@@ -1108,6 +1212,46 @@ class TrainingFrameLoader:
         _read_packed_into(self.pool, _packed_jobs(st, paths, at, sizes, want))
         frames = [(at[j], sizes[j], at[nb + j], sizes[nb + j], hraw, w, y, x) for j, (_, hraw, w, y, x) in enumerate(plan)]
         return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: ops.unpack_packed_frames(
+            img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,))
+
+    def _submit_sequence(self, slot: int, plan, shape, c: int, dbits: int, starts, entries):
+        """_submit for a batch of sequence entries, PNG or packed: every DISTINCT image file of the batch -- `current`
+        repeats in a `p<TAB>p<TAB>p` entry, neighbouring samples share frames -- is read, and decoded or checked, once, into a place
+        of its own in pinned staging; a sample's record points at its three.  ONE ops.unpack_sequence_frames or
+        ops.unpack_packed_sequence_frames launch crops and converts."""
+        nb = len(plan)
+        place, want = {}, []      # image file -> its index among the batch's image files; the header it was planned with
+        for (_, hraw, w, _, _), fields in zip(plan, entries):
+            for path in fields:
+                if path not in place:
+                    place[path] = len(want)
+                    want.append((w, hraw, c, 8))
+        ni = len(want)
+        paths = list(place) + [self.sparse_depth_paths[p[0]] for p in plan]
+        want += [(w, hraw, 1, dbits) for _, hraw, w, _, _ in plan]
+        packed = _one_kind(paths, [self._file_header(path)[1] for path in paths], "TrainingFrameLoader")
+        if packed:
+            sizes = [os.path.getsize(path) for path in paths]
+        else:
+            files = list(self.pool.map(_read, paths))
+            for path, data, header in zip(paths, files, want):
+                if png_info(data) != header:
+                    raise KbnError(f"TrainingFrameLoader: {path} changed since its header was read")
+            sizes = [hh * ww * cc * (bb // 8) for ww, hh, cc, bb in want]
+        at, total = _layout(sizes, ni)
+        st = self._staging.acquire(slot, total[0], total[1], nb)
+        _load_intrinsics(st, [self.intrinsics_paths[p[0]] for p in plan], starts)
+        if packed:
+            _read_packed_into(self.pool, _packed_jobs(st, paths, at, sizes, want, ni))
+            frames = [sum(((at[place[path]], sizes[place[path]]) for path in fields), ()) + (at[ni + j], sizes[ni + j], hraw, w, y, x)
+                      for j, ((_, hraw, w, y, x), fields) in enumerate(zip(plan, entries))]
+            unpack = ops.unpack_packed_sequence_frames
+        else:
+            decode_png_batch(files, [view[a:a + size] for view, a, size in _places(st, at, sizes, ni)], threads=self.workers)
+            frames = [tuple(at[place[path]] for path in fields) + (at[ni + j], hraw, w, y, x)
+                      for j, ((_, hraw, w, y, x), fields) in enumerate(zip(plan, entries))]
+            unpack = ops.unpack_sequence_frames
+        return self._staging.submit(st, total[0], total[1], nb, lambda img_d, dep_d, k_d: unpack(
             img_d, dep_d, frames, shape, channels=c, depth_bits=dbits) + (k_d,))
 
     def _enqueue(self, idx: Sequence[int], batch=None, first: int = 0, plan=None):

@@ -1447,12 +1447,16 @@ def pack_frames(samples, bits=None, out=None, out_bytes=None, workspace=None):
 
 _TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
 _PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
+_SEQUENCE_FRAME_RECORD = struct.Struct("@4q4i")     # _lib.SequenceFrame's layout: three image offsets, the depth offset, height, width, y_start, x_start
+_PACKED_SEQUENCE_FRAME_RECORD = struct.Struct("@4q4I4i")     # _lib.PackedSequenceFrame's layout: four byte offsets, four file sizes, height, width, y_start, x_start
 
 
-def _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, record, fields, place, max_raw_width=None, align=1):
-    """What unpack_train_frames and unpack_packed_frames (`fn`) check, in one order: the arguments, then every frame, then where the
+def _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, record, fields, place, max_raw_width=None, align=1,
+                    thirds=3):
+    """What the unpack_*_frames wrappers (`fn`) check, in one order: the arguments, then every frame, then where the
     tensors live -- a wrong frame is named on a machine without a GPU too.  `record`: the struct of one frame, its last four fields
-    H, 3 W, y_start, x_start; `fields`: the entries of a frame tuple, which end with H, W, y_start, x_start; `place(i, frame)` checks
+    H, `thirds` x W, y_start, x_start (thirds 3: the record of a triplet file holds its raw width; 1: the sequence records hold a
+    frame's); `fields`: the entries of a frame tuple, which end with H, W, y_start, x_start; `place(i, frame)` checks
     where the frame lies in the two buffers and returns the record's leading fields.  Returns h, w, frames, n and the records."""
     h, w = (int(v) for v in shape)
     if h < 1 or w < 1:
@@ -1473,13 +1477,13 @@ def _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bit
         if len(f) != fields.count(",") + 1:
             raise KbnError(f"{fn}: frame {i}: expected ({fields}), got {f}")
         H, W, y, x = f[-4:]
-        if H < 1 or W < 1 or 3 * W > 0x7fffffff:
+        if H < 1 or W < 1 or thirds * W > 0x7fffffff:
             raise KbnError(f"{fn}: frame {i}: raw size {H} x {W}")
-        if max_raw_width is not None and 3 * W > max_raw_width:
-            raise KbnError(f"{fn}: frame {i}: a packed triplet of {3 * W} columns is wider than the kernel takes ({max_raw_width})")
+        if max_raw_width is not None and thirds * W > max_raw_width:
+            raise KbnError(f"{fn}: frame {i}: a packed {'triplet' if thirds == 3 else 'frame'} of {thirds * W} columns is wider than the kernel takes ({max_raw_width})")
         if y < 0 or y + h > H or x < 0 or x + w > W:
             raise KbnError(f"{fn}: frame {i}: the {h} x {w} crop at ({y}, {x}) leaves the {H} x {W} frame")
-        record.pack_into(records, i * record.size, *place(i, f), H, 3 * W, y, x)
+        record.pack_into(records, i * record.size, *place(i, f), H, thirds * W, y, x)
     for name, t in (("images_u8", images_u8), ("depths_u8", depths_u8)):
         if not t.is_cuda:
             raise KbnError(f"{fn}: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
@@ -1568,6 +1572,87 @@ def unpack_packed_frames(images_u8, depths_u8, frames, shape, channels: int = 3,
                                                                    None if middle_only else image1.data_ptr(),
                                                                    None if middle_only else image2.data_ptr(), depth.data_ptr(), _stream()),
                       nbytes=packed_bytes + float(n * h * w) * (16 if middle_only else 40)), "kbn_unpack_packed_frames_forward")
+    return (image0, depth) if middle_only else (image0, image1, image2, depth)
+
+
+def unpack_sequence_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16):
+    """unpack_train_frames for samples whose three frames lie at three places of their own (kb.loader.split_sample): the
+    same four tensors, bit for bit what the triplet np.concatenate([previous, current, next], axis=1) gives there, and no triplet is
+    assembled (kbn_unpack_sequence_frames_forward, csrc/unpack_sequence.hip: one launch per _lib.KBN_UNPACK_SEQUENCE_MAX_FRAMES samples).
+
+    images_u8 / depths_u8: packed 1-d uint8 device buffers.  frames: one (previous_offset, current_offset, next_offset, depth_offset,
+    H, W, y_start, x_start) a sample -- the byte offsets of its three H x W x channels frames (they may coincide, and samples may
+    share frames) and of its H x W depth samples, and where its crop starts in every frame.  W is a frame's width.  Everything else
+    as unpack_train_frames: image0 is `current`, image1 `previous`, image2 `next`.  No CPU fallback."""
+    fn = "unpack_sequence_frames"
+    channels, depth_bits = int(channels), int(depth_bits)
+
+    def place(i, f):
+        offsets, do, H, W = f[:3], f[3], f[4], f[5]
+        for what, io in zip(("previous", "current", "next"), offsets):
+            if io < 0 or io + H * W * channels > images_u8.numel():
+                raise KbnError(f"{fn}: frame {i}: its {what} frame of {H} x {W} x {channels} at byte {io} leaves the image buffer of {images_u8.numel()} bytes")
+        if do < 0 or do % (depth_bits // 8) or do + H * W * (depth_bits // 8) > depths_u8.numel():
+            raise KbnError(f"{fn}: frame {i}: its {H} x {W} depth map of {depth_bits}-bit samples at byte {do} is misaligned or leaves "
+                           f"the depth buffer of {depths_u8.numel()} bytes")
+        return tuple(offsets) + (do,)
+
+    h, w, frames, n, records = _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, _SEQUENCE_FRAME_RECORD,
+                                               "previous_offset, current_offset, next_offset, depth_offset, H, W, y_start, x_start", place,
+                                               thirds=1)
+    device = images_u8.device
+    image0, image1, image2 = (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(3))
+    depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
+    lib = _lib.load()
+    table = (_lib.SequenceFrame * n).from_buffer(records)
+    with torch.cuda.device(device):
+        check(_launch("unpack_sequence_frames", 0.0,
+                      lambda: lib.kbn_unpack_sequence_frames_forward(images_u8.data_ptr(), images_u8.numel(), depths_u8.data_ptr(), depths_u8.numel(),
+                                                                     table, n, h, w, channels, depth_bits, image0.data_ptr(), image1.data_ptr(),
+                                                                     image2.data_ptr(), depth.data_ptr(), _stream()),
+                      nbytes=float(n * h * w) * (3 * channels + depth_bits // 8 + 40)), "kbn_unpack_sequence_frames_forward")
+    return image0, image1, image2, depth
+
+
+def unpack_packed_sequence_frames(images_u8, depths_u8, frames, shape, channels: int = 3, depth_bits: int = 16, middle_only: bool = False):
+    """unpack_sequence_frames from PACKED files, one per frame (kbn_unpack_packed_sequence_frames_forward, csrc/unpack_sequence.hip:
+    one launch per _lib.KBN_UNPACK_SEQUENCE_MAX_FRAMES samples): what unpack_packed_frames gives for the packed triplet, bit for bit.
+
+    images_u8 / depths_u8: 1-d uint8 device buffers, 16-byte aligned, that hold the files as they are on disk.  frames: one
+    (previous_offset, previous_bytes, current_offset, current_bytes, next_offset, next_bytes, depth_offset, depth_bytes, H, W,
+    y_start, x_start) a sample -- where its three packed H x W x channels frames and its packed H x W depth map lie (offsets
+    multiples of 16; they may coincide and be shared) and where its crop starts in every frame.  Every file must have passed
+    kbn_frame_check (kb.loader.check_frame) on the host.  middle_only: returns (image0, sparse_depth0) and decodes only `current`
+    (all three places are still checked).  A width above _lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH raises KbnError.  No CPU fallback."""
+    fn = "unpack_packed_sequence_frames"
+    channels, depth_bits = int(channels), int(depth_bits)
+
+    def place(i, f):
+        files = (("previous frame", f[0], f[1], images_u8), ("current frame", f[2], f[3], images_u8), ("next frame", f[4], f[5], images_u8),
+                 ("depth map", f[6], f[7], depths_u8))
+        for what, at, size, buf in files:
+            if at < 0 or at % 16 or size < 1 or size > 0xffffffff or at + size > buf.numel():
+                raise KbnError(f"{fn}: frame {i}: its packed {what} of {size} bytes at byte {at} is misaligned or leaves its buffer of {buf.numel()} bytes")
+        return f[0], f[2], f[4], f[6], f[1], f[3], f[5], f[7]
+
+    h, w, frames, n, records = _unpack_records(fn, images_u8, depths_u8, frames, shape, channels, depth_bits, _PACKED_SEQUENCE_FRAME_RECORD,
+                                               "previous_offset, previous_bytes, current_offset, current_bytes, next_offset, next_bytes, "
+                                               "depth_offset, depth_bytes, H, W, y_start, x_start", place,
+                                               max_raw_width=_lib.KBN_UNPACK_PACKED_MAX_RAW_WIDTH, align=16, thirds=1)
+    device = images_u8.device
+    image0 = torch.empty((n, 3, h, w), device=device, dtype=torch.float32)
+    image1, image2 = (None, None) if middle_only else (torch.empty((n, 3, h, w), device=device, dtype=torch.float32) for _ in range(2))
+    depth = torch.empty((n, 1, h, w), device=device, dtype=torch.float32)
+    lib = _lib.load()
+    table = (_lib.PackedSequenceFrame * n).from_buffer(records)
+    packed_bytes = float(sum(f[3] + f[7] if middle_only else f[1] + f[3] + f[5] + f[7] for f in frames))
+    with torch.cuda.device(device):
+        check(_launch("unpack_packed_sequence_frames", 0.0,
+                      lambda: lib.kbn_unpack_packed_sequence_frames_forward(images_u8.data_ptr(), images_u8.numel(), depths_u8.data_ptr(),
+                                                                            depths_u8.numel(), table, n, h, w, channels, depth_bits,
+                                                                            image0.data_ptr(), None if middle_only else image1.data_ptr(),
+                                                                            None if middle_only else image2.data_ptr(), depth.data_ptr(), _stream()),
+                      nbytes=packed_bytes + float(n * h * w) * (16 if middle_only else 40)), "kbn_unpack_packed_sequence_frames_forward")
     return (image0, depth) if middle_only else (image0, image1, image2, depth)
 
 

@@ -1185,6 +1185,59 @@ int kbn_unpack_packed_frames_forward(const unsigned char* images, size_t image_b
                                      const kbn_packed_frame* frames, int n, int height, int width, int image_channels, int depth_bits,
                                      float* image0, float* image1, float* image2, float* sparse_depth0, kbn_stream_t stream);
 
+/* kbn_unpack_train_frames_forward for samples that name their three frames one by one: what load_image_triplet (reference
+ * src/datasets.py:22-46) makes of the concatenation of frames t-1, t, t+1, from the three frames where each lies -- no triplet is
+ * ever assembled.  Frame k of sample i (0 previous -> image1, 1 current -> image0, 2 next -> image2) is height_i x width_i x
+ * image_channels uint8 at byte image_offset_i[k] of `images`; width_i is a FRAME's width W_i, the depth map's too.  The three offsets
+ * of a sample may coincide (the reference's validation and testing triplets are one frame three times, setup_dataset_kitti.py:514-516)
+ * and samples may share frames.  Outputs, crop (random_crop's slices, src/datasets.py:143-148), conversions and the 16-byte-store /
+ * float-by-float split are kbn_unpack_train_frames_forward's; so are the bits, for the triplet np.concatenate makes of the frames.
+ * One launch per KBN_UNPACK_SEQUENCE_MAX_FRAMES samples, the records by value in the kernel arguments.
+ * Checked for every record before anything is launched -- KBN_ERR_INVALID_ARGUMENT: a NULL pointer, n < 1, height or width < 1, a
+ * frame size < 1, a crop that leaves its frame (y_start < 0, y_start + height > height_i, x_start < 0, x_start + width > width_i),
+ * a negative or (16-bit depth) odd offset, one of the three frames or the depth map not inside its buffer; KBN_ERR_UNSUPPORTED:
+ * other image_channels / depth_bits, a crop of more than 2^31 - 1 four-pixel groups. */
+#define KBN_UNPACK_SEQUENCE_MAX_FRAMES 48 /* records a launch of either sequence entry point carries: 48 x 64 bytes of the packed record = 3 KB of the argument block */
+typedef struct kbn_sequence_frame {
+    long long image_offset[3]; /* bytes, into `images`: previous, current, next */
+    long long depth_offset;    /* bytes, into `depths` */
+    int height;                /* rows of each frame and of the depth map */
+    int width;                 /* columns of each frame and of the depth map: W */
+    int y_start, x_start;      /* the crop's first row and first column in every frame */
+} kbn_sequence_frame;
+int kbn_unpack_sequence_frames_forward(const unsigned char* images, size_t image_bytes, const unsigned char* depths, size_t depth_bytes,
+                                       const kbn_sequence_frame* frames, int n, int height, int width, int image_channels,
+                                       int depth_bits, float* image0, float* image1, float* image2, float* sparse_depth0,
+                                       kbn_stream_t stream);
+
+/* kbn_unpack_packed_frames_forward for three packed files a sample: frame k of sample i is a packed file of
+ * image_channels planes of 8 bits, width_i wide, image_bytes_i[k] long, at the 16-byte-aligned offset image_offset_i[k]; the depth map
+ * one plane of depth_bits, width_i wide.  Offsets may coincide and be shared, as above.  image1 and image2 may be NULL: then only the
+ * CURRENT file of every sample is decoded (KBNetInferenceDataset.__getitem__, reference src/datasets.py:259-283, on a sequence entry).
+ * One launch per KBN_UNPACK_SEQUENCE_MAX_FRAMES samples; one workgroup per (sample, which of the three files or the depth map, group of
+ * 8 rows that the crop touches, plane).  Every file starts at segment 0 of its rows, so the crop's first column sits at x_start of
+ * its file, where a triplet's second and third frame start mid-segment unless W % 16 == 0.  The decoder's discipline is
+ * kbn_unpack_packed_frames_forward's: the files must have passed kbn_frame_check; the kernel compares header, table and header bytes
+ * with the record and with each other before it reads, leaves the outputs of a unit that disagrees unwritten, and never reads
+ * outside a file.  The bits are kbn_unpack_sequence_frames_forward's for the decoded samples.
+ * Checked for every record before anything is launched -- KBN_ERR_INVALID_ARGUMENT: a NULL pointer other than image1 / image2 (one
+ * of the two alone is refused), misaligned buffers, n < 1, height or width < 1, a frame size < 1, a crop that leaves its frame, a
+ * negative or misaligned offset, a file (all three are checked, whatever is decoded) too short for its header and table or not
+ * inside its buffer; KBN_ERR_UNSUPPORTED: other image_channels / depth_bits, a width above KBN_UNPACK_PACKED_MAX_RAW_WIDTH. */
+typedef struct kbn_packed_sequence_frame {
+    long long image_offset[3];   /* bytes, into `images`, multiples of 16: previous, current, next */
+    long long depth_offset;      /* bytes, into `depths`; a multiple of 16 */
+    unsigned int image_bytes[3]; /* the three packed files' sizes */
+    unsigned int depth_bytes;    /* the packed depth map's file size */
+    int height;                  /* rows of each frame and of the depth map */
+    int width;                   /* columns of each frame and of the depth map: W */
+    int y_start, x_start;        /* the crop's first row and first column in every frame */
+} kbn_packed_sequence_frame;
+int kbn_unpack_packed_sequence_frames_forward(const unsigned char* images, size_t image_bytes, const unsigned char* depths,
+                                              size_t depth_bytes, const kbn_packed_sequence_frame* frames, int n, int height, int width,
+                                              int image_channels, int depth_bits, float* image0, float* image1, float* image2,
+                                              float* sparse_depth0, kbn_stream_t stream);
+
 /* The device ENCODER of the packed frame store (csrc/pack_frames.hip): n frames of one size -> n file images, each byte
  * for byte what kbn_frame_encode writes for the same samples (header, table, zero padding up to the payload, payload).
  *   kbn_pack_frames_stride           capacity of one frame's slot: kbn_frame_encode_bound rounded up to 16; 0 for sizes the encoder

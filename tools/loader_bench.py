@@ -4,7 +4,10 @@ triplets, 352 x 1216 16-bit sparse depth) -> InferenceFrameLoader -> preprocess 
 Prints decode-only, loader-only (decode + H2D + unpack) and end-to-end frames/s, next to the PIL loop the
 reference runs (one worker, one sample at a time).   usage: loader_bench.py [n_files] [workers] [prefetch] [--packed]
 --packed: the files are also converted to packed frames (kb.loader.pack_frames; both total sizes are printed) and every
-loader figure is taken for both forms in this one run, as the median (min, max) of five one-epoch windows."""
+loader figure is taken for both forms in this one run, as the median (min, max) of five one-epoch windows.
+--sequences: every frame (the middle third of its triplet) is also written as a file of its own, PNG and packed, and listed as the
+sequence entry p<TAB>p<TAB>p, of which the loader reads `current` alone; the bytes on disk and the loader-only figure
+are printed for the triplet files and for the sequence entries, PNG and packed, in this one run; nothing else is run."""
 import os, sys, time, tempfile, statistics
 import numpy as np
 import torch
@@ -14,7 +17,8 @@ import kbnet_amd as kb
 from PIL import Image
 
 PACKED = "--packed" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--packed"]
+SEQUENCES = "--sequences" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--packed", "--sequences")]
 n_files = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 workers = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 prefetch = int(sys.argv[3]) if len(sys.argv) > 3 else 4
@@ -38,6 +42,17 @@ if PACKED:
     raw_bytes = n_files * H * W * (9 + 2)
     print(f"SYNTHETIC files (no real KITTI frame has been measured): PNG {png_bytes / 1e6:.1f} MB, packed {packed_bytes / 1e6:.1f} MB, raw {raw_bytes / 1e6:.1f} MB; "
           f"packed / PNG = {packed_bytes / png_bytes:.3f}, packed / raw = {packed_bytes / raw_bytes:.3f}")
+if SEQUENCES:
+    singles = []
+    for i, p in enumerate(imgs):
+        frame = np.ascontiguousarray(kb.loader.decode_png(open(p, "rb").read())[:, W:2 * W])
+        singles.append(os.path.join(d, f"frame{i}.png")); Image.fromarray(frame).save(singles[-1], compress_level=6)
+    packed_imgs, packed_singles, packed_deps = ([p[:-4] + ".kbf" for p in paths] for paths in (imgs, singles, deps))
+    kb.loader.pack_frames(imgs + singles + deps, packed_imgs + packed_singles + packed_deps, workers=8)
+    entries, packed_entries = kb.loader.sequence_lines(singles, window=0), kb.loader.sequence_lines(packed_singles, window=0)
+    size = lambda paths: sum(os.path.getsize(p) for p in paths) / 1e6
+    print(f"SYNTHETIC files (no real KITTI frame has been measured), image bytes on disk, triplet files | one file a frame: PNG {size(imgs):.1f} MB | "
+          f"{size(singles):.1f} MB; packed {size(packed_imgs):.1f} MB | {size(packed_singles):.1f} MB")
 
 dev = torch.device("cuda:0")
 t0 = time.perf_counter()
@@ -71,6 +86,11 @@ def run_loader(consume, imgs=imgs, deps=deps, windows=None):
     torch.cuda.synchronize()
     return 3 * n_files / (time.perf_counter() - t)
 
+if SEQUENCES:
+    for name, images, depth_maps in (("PNG    triplet ", imgs, deps), ("PNG    sequence", entries, deps), ("packed triplet ", packed_imgs, packed_deps),
+                                     ("packed sequence", packed_entries, packed_deps)):
+        print(f"loader (read/decode + H2D + unpack) {name} : {run_loader(lambda *b: None, images, depth_maps, windows=5)} frames/s")
+    raise SystemExit(0)
 print(f"loader (decode + H2D + unpack)     : {run_loader(lambda *b: None):8.1f} frames/s")
 cfg = kb.kitti_config()
 model = kb.modules.KBNetModel.from_config(cfg, dev)

@@ -8,6 +8,8 @@
 the loaders take packed; GROUND TRUTH lists may be given too (kb.inference.run and train()'s validation read packed ground truth,
 DESIGN 8u).  Intrinsics stay .npy: pass their lists on unchanged.  tools/unpack_dataset.py is the inverse.
 Every listed file src becomes <output_root>/<src without its root or drive, suffix .kbf>; a file listed twice is converted once.
+An image list may hold sequence entries (previous<TAB>current<TAB>next; tools/sequence_lists.py writes them): each of the
+three paths is mapped like any other, every distinct frame is converted once, and the entry is rewritten field by field.
 For every list a new one of the same name is written into --list_dir (default: <output_root>/lists), line for line.
 Prints the total bytes before and after.  No GPU is needed."""
 import argparse
@@ -39,11 +41,13 @@ def main():
     sources, seen = [], set()
     for list_path in args.paths:
         paths = kb.loader.read_paths(list_path)
-        kb.loader.write_paths(os.path.join(list_dir, os.path.basename(list_path)), [packed_path(p, args.output_root) for p in paths])
-        for p in paths:
-            if p not in seen:
-                seen.add(p)
-                sources.append(p)
+        kb.loader.write_paths(os.path.join(list_dir, os.path.basename(list_path)),
+                              [kb.loader.map_sample(p, lambda path: packed_path(path, args.output_root)) for p in paths])
+        for entry in paths:
+            for p in kb.loader.split_sample(entry) or (entry,):
+                if p not in seen:
+                    seen.add(p)
+                    sources.append(p)
     before, after = kb.loader.pack_frames(sources, [packed_path(p, args.output_root) for p in sources], workers=args.workers)
     print(f"{len(sources)} files: {before} bytes of PNG -> {after} bytes packed ({after / max(1, before):.3f} of the PNG size)")
     print(f"path lists written to {list_dir}")

@@ -26,6 +26,13 @@ over the PNG files at 2 and at 8 workers (part 1, the reference-style DataLoader
 with kbn_unpack_train_frames_forward on the same batch (part 2, results compared bit for bit first), and the host time of
 kbn_frame_check with the inflate it stands in for (one thread, per triplet with its depth map).  The files are synthetic.
 
+With --sequences two synthetic sequences, one of each raw size, are written frame by frame -- every frame once -- and,
+from the same frames, the triplet files np.concatenate([previous, current, next], axis=1) of every sample (window 1), both as PNG and
+as packed frames.  In this one process and on this one GPU the run reports the bytes on disk both ways, TrainingFrameLoader over the
+triplet files beside the same loader over sequence entries (PNG and packed, 2 and 8 workers: three opens a sample against one, but a
+third of the bytes), and the four launches -- kbn_unpack_train_frames_forward, kbn_unpack_sequence_frames_forward,
+kbn_unpack_packed_frames_forward, kbn_unpack_packed_sequence_frames_forward -- on one batch, results compared bit for bit first.
+
 One GPU process; nothing is retried."""
 import argparse
 import os
@@ -85,7 +92,7 @@ class ReferenceStyleDataset(torch.utils.data.Dataset):
 
 
 class _Done(Exception):
-    """--packed has written its lines: the default parts are not run."""
+    """--packed or --sequences has written its lines: the default parts are not run."""
 
 
 def epochs(run_epoch, count):
@@ -310,15 +317,196 @@ def packed_run(args, d, images, depths, ks, lines):
     lines.append("5. multi-GPU effect: not measured (one GPU, one process).")
 
 
+def _scene(h, w, s, t):
+    """Frame t of sequence s: the default mode's smooth scene, drifting 7 columns a frame, plus sensor noise."""
+    g = np.random.Generator(np.random.Philox(1000 * (s + 1) + t))
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = 128 + 60 * np.sin((xx + 7 * t) / 90.0 + s) * np.cos(yy / 40.0) + 30 * np.sin((xx + yy + 3 * t) / 17.0)
+    return np.stack([base + g.normal(0, 6, base.shape) + 20 * c for c in range(3)], axis=-1).clip(0, 255).astype(np.uint8)
+
+
+def write_frame(args):
+    d, s, t = args
+    h, w = RAW_SIZES[s]
+    os.makedirs(os.path.join(d, f"seq{s}"), exist_ok=True)
+    Image.fromarray(_scene(h, w, s, t)).save(os.path.join(d, f"seq{s}", f"f{t:04d}.png"), compress_level=6)
+
+
+def write_triplet_sample(args):
+    """Sample (s, t): the triplet file of frames t, t + 1, t + 2 of sequence s, its sparse depth and its intrinsics."""
+    d, s, t, fields = args
+    h, w = RAW_SIZES[s]
+    frames = [kb.loader.decode_png(open(path, "rb").read()) for path in fields]
+    Image.fromarray(np.concatenate(frames, axis=1)).save(os.path.join(d, f"tr{s}_{t}.png"), compress_level=6)
+    g = np.random.Generator(np.random.Philox(5000 * (s + 1) + t))
+    z = (g.random((h, w)) < 0.05) * (g.random((h, w)) * 79 + 1) * 256
+    Image.fromarray(z.astype(np.uint16)).save(os.path.join(d, f"sd{s}_{t}.png"))
+    np.save(os.path.join(d, f"k{s}_{t}.npy"), np.array([[721.5, 0, 609.6], [0, 721.5, 172.9], [0, 0, 1]]))
+
+
+def _to_packed(path):
+    return os.path.splitext(path)[0] + ".kbf"
+
+
+def sequence_batch(entries, triplets, depths, packed):
+    """The first BATCH samples laid out for the four launches (host side, no GPU): {name: (image bytes, depth bytes, record
+    table)} for "train", "sequence" (decoded bytes) and "packed", "packed_sequence" (files as they are on disk), under one set of
+    crops.  Every distinct frame lies once in the sequence buffers."""
+    h, w = SHAPE
+    read = lambda path: open(path, "rb").read()
+    load = (lambda path: read(_to_packed(path))) if packed else (lambda path: kb.loader.decode_png(read(path)).tobytes())
+
+    def lay(blobs):
+        at, total = [], 0
+        for data in blobs:
+            at.append(total)
+            total = (total + len(data) + 15) & ~15
+        host = np.zeros(total, np.uint8)
+        for a, data in zip(at, blobs):
+            host[a:a + len(data)] = np.frombuffer(data, np.uint8)
+        return host, at
+
+    fields = [kb.loader.split_sample(entry) for entry in entries[:BATCH]]
+    distinct = list(dict.fromkeys(path for f in fields for path in f))
+    frame_blobs, triplet_blobs, depth_blobs = [load(p) for p in distinct], [load(p) for p in triplets[:BATCH]], [load(p) for p in depths[:BATCH]]
+    (frame_host, frame_at), (triplet_host, triplet_at), (depth_host, depth_at) = lay(frame_blobs), lay(triplet_blobs), lay(depth_blobs)
+    where = {path: (a, len(data)) for path, a, data in zip(distinct, frame_at, frame_blobs)}
+    np.random.seed(0)
+    sizes = [kb.loader.png_info(read(f[1])[:33])[1::-1] for f in fields]      # (height, width) of `current`
+    starts = [kb.loader.draw_crop(H, W, SHAPE, CROP_TYPE) for H, W in sizes]
+    if packed:
+        triplet_table, sequence_table = (kb._lib.PackedFrame * BATCH)(), (kb._lib.PackedSequenceFrame * BATCH)()
+    else:
+        triplet_table, sequence_table = (kb._lib.TrainFrame * BATCH)(), (kb._lib.SequenceFrame * BATCH)()
+    for j, ((H, W), (y, x), f) in enumerate(zip(sizes, starts, fields)):
+        a, b = triplet_table[j], sequence_table[j]
+        a.image_offset, a.depth_offset, a.height, a.raw_width, a.y_start, a.x_start = triplet_at[j], depth_at[j], H, 3 * W, y, x
+        b.depth_offset, b.height, b.width, b.y_start, b.x_start = depth_at[j], H, W, y, x
+        for k, path in enumerate(f):
+            b.image_offset[k] = where[path][0]
+            if packed:
+                b.image_bytes[k] = where[path][1]
+        if packed:
+            a.image_bytes, a.depth_bytes, b.depth_bytes = len(triplet_blobs[j]), len(depth_blobs[j]), len(depth_blobs[j])
+    names = ("packed", "packed_sequence") if packed else ("train", "sequence")
+    return {names[0]: (triplet_host, depth_host, triplet_table), names[1]: (frame_host, depth_host, sequence_table)}
+
+
+def sequence_kernel_part(dev, entries, triplets, depths, quick):
+    """The two new launches beside the two existing ones on one batch: the same crops, event windows and rotation through output
+    sets; the four results are compared bit for bit first."""
+    lib = kb._lib.load()
+    h, w = SHAPE
+    batches = {**sequence_batch(entries, triplets, depths, False), **sequence_batch(entries, triplets, depths, True)}
+    n_in, n_out = (2, 2) if quick else (4, 8)
+    outs = [[torch.empty((BATCH, c, h, w), device=dev) for c in (3, 3, 3, 1)] for _ in range(n_out)]
+    stream = torch.cuda.current_stream().cuda_stream
+    entry = {"train": lib.kbn_unpack_train_frames_forward, "sequence": lib.kbn_unpack_sequence_frames_forward,
+             "packed": lib.kbn_unpack_packed_frames_forward, "packed_sequence": lib.kbn_unpack_packed_sequence_frames_forward}
+    calls, nbytes = {}, {}
+    for name, (image_host, depth_host, table) in batches.items():
+        ins = [(torch.from_numpy(image_host).to(dev), torch.from_numpy(depth_host).to(dev)) for _ in range(n_in)]
+        nbytes[name] = image_host.nbytes + depth_host.nbytes
+
+        def call(i, ins=ins, table=table, fn=entry[name]):
+            (im, z), o = ins[i % n_in], outs[i % n_out]
+            rc = fn(im.data_ptr(), im.numel(), z.data_ptr(), z.numel(), table, BATCH, h, w, 3, 16, o[0].data_ptr(), o[1].data_ptr(),
+                    o[2].data_ptr(), o[3].data_ptr(), stream)
+            assert rc == 0, rc
+
+        calls[name] = call
+    results = {}
+    for name, call in calls.items():
+        for t in outs[0]:
+            t.fill_(-1.0)
+        call(0)
+        torch.cuda.synchronize()
+        results[name] = [t.clone() for t in outs[0]]
+    for name in ("sequence", "packed", "packed_sequence"):
+        assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(results["train"], results[name])), f"{name} differs"
+    iters = 20 if quick else 400
+    order = ("train", "sequence", "packed", "packed_sequence")
+    first = {name: windows(calls[name], iters) for name in order}
+    again = {name: windows(calls[name], iters) for name in order}
+    us = lambda t: spread([v * 1e3 for v in t])
+    lines = [f"2. kernels: one batch, {BATCH} samples -> {h} x {w}; the four results equal bit for bit; output {BATCH * h * w * 40 / 1e6:.1f} MB; "
+             "two rounds of windows, each launch after the other three"]
+    for name in order:
+        lines.append(f"   kbn_unpack_{name}_frames_forward".ljust(48) + f"input {nbytes[name] / 1e6:5.1f} MB   device {us(first[name])} us a launch, "
+                     f"{us(again[name])} us in the second round")
+    med = lambda name: statistics.median(first[name] + again[name])
+    lines.append(f"   sequence / train = {med('sequence') / med('train'):.2f} x; packed_sequence / packed = {med('packed_sequence') / med('packed'):.2f} x")
+    return lines
+
+
+def sequences_run(args, d, lines):
+    """--sequences: bytes on disk, loader rates of the triplet path beside the sequence path, the four launches."""
+    per = 8 if args.quick else N_FILES // 2      # samples a sequence
+    frames = [[os.path.join(d, f"seq{s}", f"f{t:04d}.png") for t in range(per + 2)] for s in range(2)]
+    samples = [(s, t) for t in range(per) for s in range(2)]      # the two sizes alternate, as in the default mode
+    by_sequence = [kb.loader.sequence_lines(f, window=1, ends="drop") for f in frames]
+    with ThreadPoolExecutor(max_workers=WORKERS) as ex:
+        list(ex.map(write_frame, [(d, s, t) for s in range(2) for t in range(per + 2)]))
+        list(ex.map(write_triplet_sample, [(d, s, t, kb.loader.split_sample(by_sequence[s][t])) for s, t in samples]))
+    lists = {"PNG": {"sequence": [by_sequence[s][t] for s, t in samples], "triplet": [os.path.join(d, f"tr{s}_{t}.png") for s, t in samples],
+                     "depth": [os.path.join(d, f"sd{s}_{t}.png") for s, t in samples]}}
+    ks = [os.path.join(d, f"k{s}_{t}.npy") for s, t in samples]
+    lists["packed"] = {name: [kb.loader.map_sample(entry, _to_packed) for entry in entries] for name, entries in lists["PNG"].items()}
+    for name in ("sequence", "triplet", "depth"):      # sequence entries go through pack_frames as they are: every frame once
+        kb.loader.pack_frames(lists["PNG"][name], lists["packed"][name], workers=WORKERS)
+    size = lambda entries: sum(os.path.getsize(p) for p in dict.fromkeys(path for e in entries for path in (kb.loader.split_sample(e) or (e,))))
+    disk = {(kind, form): size(lists[kind][form]) for kind in lists for form in ("sequence", "triplet")}
+    lines[0] = (f"train_loader_bench --sequences: {len(samples)} SYNTHETIC samples (no real KITTI frame has been measured) of two sequences of {per + 2} frames, "
+                f"batch {BATCH}, crop {SHAPE[0]} x {SHAPE[1]} {' '.join(CROP_TYPE)}")
+    lines.append("0. image bytes on disk, triplet files | one file a frame: " + "; ".join(
+        f"{kind} {disk[(kind, 'triplet')] / 1e6:.1f} MB | {disk[(kind, 'sequence')] / 1e6:.1f} MB ({disk[(kind, 'sequence')] / disk[(kind, 'triplet')]:.3f})"
+        for kind in lists) + f"; {3 * len(samples)} frame slots in the triplets, {2 * (per + 2)} frames")
+    if not torch.cuda.is_available():
+        raise SystemExit("train_loader_bench needs a GPU: a time measured anywhere else says nothing")
+    dev = torch.device("cuda:0")
+    kb._lib.load()
+    lines[0] += f"; {torch.cuda.get_device_name(0)}"
+    need = BATCH / (STEP_MS * 1e-3)
+    lines.append(f"1. TrainingFrameLoader, triplets/s, median (min, max) of the epoch windows (the {STEP_MS} ms step takes {need:.0f} a GPU):")
+    medians = {}
+    for workers in (2, 8):
+        for kind in ("PNG", "packed"):
+            for form in ("triplet", "sequence"):
+                loader = kb.loader.TrainingFrameLoader(lists[kind][form], lists[kind]["depth"], ks, shape=SHAPE, random_crop_type=CROP_TYPE,
+                                                       batch_size=BATCH, shuffle=True, device=dev, workers=workers, prefetch=4)
+
+                def epoch():
+                    n = 0
+                    for _ in range(4):
+                        for inputs in loader:
+                            n += inputs[0].shape[0]
+                    torch.cuda.synchronize()
+                    return n
+
+                rates = epochs(epoch, 2 if args.quick else 8)
+                medians[(kind, form, workers)] = statistics.median(rates)
+                lines.append(f"   {kind:6} {form:8} workers={workers}   {spread(rates)}")
+    lines.append("   sequence / triplet: " + "; ".join(
+        f"{kind} at {workers} workers {medians[(kind, 'sequence', workers)] / medians[(kind, 'triplet', workers)]:.2f}"
+        for kind in ("PNG", "packed") for workers in (2, 8)))
+    lines += sequence_kernel_part(dev, lists["PNG"]["sequence"], lists["PNG"]["triplet"], lists["PNG"]["depth"], args.quick)
+    lines.append("3. multi-GPU effect: not measured (one GPU, one process).")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--packed", action="store_true", help="convert the files to packed frames and compare the packed path with the PNG path")
+    ap.add_argument("--sequences", action="store_true", help="compare sequence entries (one file a frame) with the triplet files of the same frames")
     ap.add_argument("--quick", action="store_true", help="16 files, short windows: a rehearsal, not a measurement")
     args = ap.parse_args()
     n_files = 16 if args.quick else N_FILES
     d = tempfile.mkdtemp(prefix="kbn_train_loader_")
     try:
+        if args.sequences:
+            lines = [""]
+            sequences_run(args, d, lines)
+            raise _Done
         with ThreadPoolExecutor(max_workers=WORKERS) as ex:
             list(ex.map(write_sample, [(d, i) for i in range(n_files)]))
         images = [os.path.join(d, f"im{i}.png") for i in range(n_files)]

@@ -19,7 +19,7 @@ OBJ_DIR = os.path.join(HERE, "csrc", "_obj")
 # longest translation units first: the pool then ends with the short ones
 SOURCES = ["conv_igemm.hip", "conv_dma_t1.hip", "conv_dma_t2.hip", "conv_dma_t4.hip", "conv_split.hip", "upconv_split.hip", "conv_up2x.hip", "kb_pair_nb3.hip",
            "conv_wino.hip", "s2d.hip", "kb1_depth_front.hip", "kb1_front.hip", "kb_pair_nb4.hip", "conv1x1s2_split.hip", "kb_pair.hip", "head.hip", "tail.hip", "kb.hip", "conv_dma.hip",
-           "tune.hip", "abi.hip", "pre_eval.hip", "loss.hip", "loss_backward.hip", "conv_bwd_weight.hip", "posenet_backward.hip", "bn_sync.hip", "conv_affine_backward.hip", "kbnet_backward.hip", "posenet.hip", "conv_affine.hip", "unpack.hip", "unpack_train.hip", "unpack_packed.hip", "unpack_sequence.hip", "pack_frames.hip", "frame_pack.hip", "export_pack.hip", "io_png.hip", "elementwise.hip", "adam.hip", "augment.hip", "multi_copy.hip", "summary.hip", "histogram.hip"]
+           "tune.hip", "abi.hip", "pre_eval.hip", "loss.hip", "loss_backward.hip", "conv_bwd_weight.hip", "posenet_backward.hip", "bn_sync.hip", "conv_affine_backward.hip", "kbnet_backward.hip", "posenet.hip", "conv_affine.hip", "unpack.hip", "unpack_train.hip", "unpack_packed.hip", "unpack_sequence.hip", "pack_frames.hip", "frame_pack.hip", "export_pack.hip", "point_cloud.hip", "io_png.hip", "elementwise.hip", "adam.hip", "augment.hip", "multi_copy.hip", "summary.hip", "histogram.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
          "-Wno-unused-function"]
 

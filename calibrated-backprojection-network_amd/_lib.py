@@ -321,6 +321,8 @@ SIGNATURES = {
     "kbn_pack_frames_stride": (C.c_size_t, [_I, _I, _I, _I]),
     "kbn_pack_frames_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, _I]),
     "kbn_pack_frames_forward": (_I, [_P, _I, _I, _I, _I, _I, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "kbn_point_cloud_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "kbn_point_cloud_forward": (_I, [_P, _L, _P, _F, _F, _P, _F, _F, _I, _I, _I, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "kbn_histogram_forward": (_I, [_P, _L, _P, _P, _P, _P, C.c_size_t, _P]),
     "kbn_crc32c": (C.c_uint, [C.c_char_p, C.c_size_t, C.c_uint]),
 }

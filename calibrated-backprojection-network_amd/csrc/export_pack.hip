@@ -11,18 +11,10 @@
 // of each plane contiguously); it writes 12 contiguous bytes of rgb and 8 of each sample plane, neighbouring lanes neighbouring
 // bytes.  Rows whose width is no multiple of 4, or pointers off a 16-byte boundary, take the same kernel with scalar loads and
 // stores.  Every output byte is written exactly once and nothing outside the three outputs is touched.
+#include "export_rules.h"   // rgb8, depth16
 #include "kbn_common.h"
 
 namespace kbn {
-
-__device__ __forceinline__ unsigned rgb8(float v, float scale, float shift) {
-    const float x = __fadd_rn(__fmul_rn(scale, v), shift);
-    return x >= 255.0f ? 255u : (x >= 0.f ? (unsigned)x : 0u);   // NaN fails both comparisons -> 0
-}
-__device__ __forceinline__ unsigned depth16(float z) {
-    const float v = z * 256.0f;   // exact in fp32
-    return v >= 65535.0f ? 65535u : (v >= 0.f ? (unsigned)v : 0u);
-}
 
 // quads = n * h * ceil(w / 4): thread q owns pixels [4 xq, 4 xq + 4) of row r = q / ceil(w / 4) of the n * h rows
 template <bool VEC>

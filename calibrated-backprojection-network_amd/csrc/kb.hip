@@ -10,6 +10,7 @@
 //                                                     (proj_depth dot product, xyz = coords*z)
 //                                                     happens while the tile is staged, and only
 //                                                     at the even pixels the stride-2 conv reads.
+#include "camera_coordinate.h"
 #include "conv_common.h"
 
 namespace kbn {
@@ -49,7 +50,7 @@ __global__ void camera_coordinates_kernel(const float* __restrict__ kinv, float*
     const float* k = kinv + (long long)b * 9;
     float* o = out + (long long)b * 3 * HW + pix;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) o[(long long)j * HW] = fmaf(k[j * 3 + 1], (float)y, k[j * 3 + 0] * (float)x) + k[j * 3 + 2];
+    for (int j = 0; j < 3; ++j) o[(long long)j * HW] = camera_coordinate(k, j, x, y);
 }
 
 }  // namespace kbn

@@ -22,10 +22,11 @@
 
 #include "frame_pack.h"
 #include "kbn_common.h"
+#include "wg_scan.h"
 
 namespace kbn {
 
-constexpr int PF_THREADS = 256;
+constexpr int PF_THREADS = WG_THREADS;                       // wg_scan.h: the workgroup its sums, scans and flushes serve
 constexpr int PF_TEAMS = PF_THREADS / fp::FP_SEG;             // segments in flight: 16 lanes each
 constexpr int PF_CHUNK = 256;                                 // segments assembled per LDS image
 constexpr int PF_IMAGE_BYTES = PF_CHUNK * 2 * fp::FP_SEG;     // no segment takes more than 16 samples of 16 bits: 8 KB
@@ -42,41 +43,6 @@ __device__ __forceinline__ unsigned pf_field(unsigned a, unsigned pred, int bits
     const unsigned u = (a - pred) & mask;
     const int d = (u >> (bits - 1)) ? (int)u - (int)(mask + 1u) : (int)u;
     return fp::zigzag(d);
-}
-
-// the sum of v over the workgroup, in every thread; `wave_total` is PF_THREADS / 64 words of LDS (reusable after the call)
-__device__ __forceinline__ unsigned pf_block_sum(unsigned v, unsigned* wave_total) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    __syncthreads();   // earlier readers of wave_total are done
-    if ((threadIdx.x & 63) == 0) wave_total[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned total = 0;
-#pragma unroll
-    for (int w = 0; w < PF_THREADS / 64; ++w) total += wave_total[w];
-    return total;
-}
-
-// the inclusive prefix sum of v over the workgroup in thread order; *total receives the workgroup's sum
-__device__ __forceinline__ unsigned pf_block_scan(unsigned v, unsigned* wave_total, unsigned* total) {
-    const int tid = (int)threadIdx.x;
-    unsigned incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned t = __shfl_up(incl, d);
-        if ((tid & 63) >= d) incl += t;
-    }
-    __syncthreads();
-    if ((tid & 63) == 63) wave_total[tid >> 6] = incl;
-    __syncthreads();
-    unsigned sum = 0;
-#pragma unroll
-    for (int w = 0; w < PF_THREADS / 64; ++w) {
-        if (w < (tid >> 6)) incl += wave_total[w];
-        sum += wave_total[w];
-    }
-    *total = sum;
-    return incl;
 }
 
 struct PackFramesParams {
@@ -126,7 +92,7 @@ __global__ __launch_bounds__(PF_THREADS) void pack_sizes_kernel(const PackFrames
             bytes += fp::segment_bytes(n, b, bits, r == 0);
         }
     }
-    const unsigned total = pf_block_sum(bytes, wave_total);
+    const unsigned total = wg_sum(bytes, wave_total);
     if (tid == 0) p.lengths[entry] = (unsigned)nseg + total;
 }
 
@@ -143,7 +109,7 @@ __global__ __launch_bounds__(PF_THREADS) void pack_table_kernel(const PackFrames
         const long long i = at + tid;
         const unsigned v = i < entries ? len[i] : 0u;
         unsigned total;
-        const unsigned incl = pf_block_scan(v, wave_total, &total);
+        const unsigned incl = wg_scan(v, wave_total, &total);
         if (i < entries) word[8 + i] = carry + incl - v;
         carry += total;
     }
@@ -160,22 +126,6 @@ __global__ __launch_bounds__(PF_THREADS) void pack_table_kernel(const PackFrames
 }
 
 // ---- 3. emit ----
-// LDS bytes [phase, phase + bytes) of `image` -> dst[0, bytes), where phase = dst mod 16: 16-byte words that lie inside the range are
-// stored whole, the others byte by byte; nothing else is written
-__device__ __forceinline__ void pf_flush(const unsigned* image, unsigned phase, unsigned char* dst, unsigned bytes) {
-    const unsigned char* image_bytes = reinterpret_cast<const unsigned char*>(image);
-    unsigned char* origin = dst - phase;   // 16-byte aligned
-    const unsigned end = phase + bytes;
-    for (unsigned w = threadIdx.x; w * 16u < end; w += PF_THREADS) {
-        const unsigned lo = w * 16u, hi = lo + 16u;
-        if (lo >= phase && hi <= end) {
-            *reinterpret_cast<uint4*>(origin + lo) = *reinterpret_cast<const uint4*>(image_bytes + lo);
-        } else {
-            for (unsigned i = max(lo, phase); i < min(hi, end); ++i) origin[i] = image_bytes[i];
-        }
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(PF_THREADS) void pack_emit_kernel(const PackFramesParams p) {
     extern __shared__ unsigned seg_at[];   // byte offset of every segment from the (group, plane)'s start, and the payload's length
@@ -209,7 +159,7 @@ __global__ __launch_bounds__(PF_THREADS) void pack_emit_kernel(const PackFramesP
             if (++k == S) { k = 0; ++r; }
         }
         unsigned total;
-        unsigned run = (unsigned)nseg + pf_block_scan(sum, wave_total, &total) - sum;
+        unsigned run = (unsigned)nseg + wg_scan(sum, wave_total, &total) - sum;
         r = e0 / S; k = e0 - r * S;
         for (int e = e0; e < e1; ++e) {
             seg_at[e] = run;
@@ -227,7 +177,7 @@ __global__ __launch_bounds__(PF_THREADS) void pack_emit_kernel(const PackFramesP
         unsigned char* image_bytes = reinterpret_cast<unsigned char*>(image);
         for (unsigned i = tid; i < count; i += PF_THREADS) image_bytes[phase + i] = head[c0 + i];
         __syncthreads();
-        pf_flush(image, phase, dst + c0, count);
+        wg_flush(image, phase, dst + c0, count);
         __syncthreads();
     }
 
@@ -259,7 +209,7 @@ __global__ __launch_bounds__(PF_THREADS) void pack_emit_kernel(const PackFramesP
             if ((unsigned)(v >> 32)) atomicOr(&image[(bit >> 5) + 1u], (unsigned)(v >> 32));
         }
         __syncthreads();
-        pf_flush(image, phase, dst + b0, b1 - b0);
+        wg_flush(image, phase, dst + b0, b1 - b0);
         __syncthreads();
     }
 }

@@ -1,6 +1,7 @@
 """The inference entry point: the reference's run() (src/kbnet.py:676-1026, what run_kbnet.py calls) on this package's device path
 -- score a checkpoint on a list of frames, write results.txt and, with save_outputs, the four directories of PNG files (or, through
-run_with_format(..., output_format="packed"), of packed frames encoded on the device: DESIGN 8u).
+run_with_format(..., output_format="packed"), of packed frames encoded on the device: DESIGN 8u); run_with_point_clouds also writes
+every frame's metric point clouds as binary PLY files, backprojected on the device.
 
     reference, per frame (batch 1)                          here, per batch of any size
     DataLoader(KBNetInferenceDataset), .to(device)          loader.InferenceFrameLoader: decoded on host threads, raw bytes over PCIe
@@ -133,8 +134,8 @@ def run(image_path,
         return_results=False):
     """run_with_format with output_format "png": the reference's run() under its arguments, names and defaults, then keyword-only
     batch_size, workers, png_level and return_results -- the signature of DESIGN 8n, which stays as it is.  Everything is documented
-    at run_with_format, which holds the code."""
-    return run_with_format(**locals())
+    at run_with_format."""
+    return _run(**locals(), output_format="png", point_clouds=None, point_cloud_depth_range=None)
 
 
 def run_with_format(image_path,
@@ -203,8 +204,82 @@ def run_with_format(image_path,
     Differences from the reference, on purpose: batches instead of batch 1; the time line goes to results.txt too and is device time
     (events around preprocess + forward); device 'cpu' and path lists of different lengths raise KbnError; the image files of the
     [-1, 1] and [0, 255] ranges hold the picture (loader.image_export_affine); files are written while the run proceeds."""
+    return _run(**locals(), point_clouds=None, point_cloud_depth_range=None)
+
+
+def run_with_point_clouds(image_path,
+                          sparse_depth_path,
+                          intrinsics_path,
+                          ground_truth_path=None,
+                          # Input settings
+                          input_channels_image=3,
+                          input_channels_depth=2,
+                          normalized_image_range=[0, 1],
+                          outlier_removal_kernel_size=7,
+                          outlier_removal_threshold=1.5,
+                          # Sparse to dense pool settings
+                          min_pool_sizes_sparse_to_dense_pool=[5, 7, 9, 11, 13],
+                          max_pool_sizes_sparse_to_dense_pool=[15, 17],
+                          n_convolution_sparse_to_dense_pool=3,
+                          n_filter_sparse_to_dense_pool=8,
+                          # Depth network settings
+                          n_filters_encoder_image=[48, 96, 192, 384, 384],
+                          n_filters_encoder_depth=[16, 32, 64, 128, 128],
+                          resolutions_backprojection=[0, 1, 2, 3],
+                          n_filters_decoder=[256, 128, 128, 64, 12],
+                          deconv_type="up",
+                          min_predict_depth=1.5,
+                          max_predict_depth=100.0,
+                          # Weight settings
+                          weight_initializer="xavier_normal",
+                          activation_func="leaky_relu",
+                          # Evaluation settings
+                          min_evaluate_depth=0.0,
+                          max_evaluate_depth=100.0,
+                          # Checkpoint settings
+                          checkpoint_path="trained_kbnet",
+                          depth_model_restore_path=None,
+                          # Output settings
+                          save_outputs=False,
+                          keep_input_filenames=False,
+                          # Hardware settings
+                          device="cuda",
+                          *,
+                          output_format="png",
+                          batch_size=8,
+                          workers=8,
+                          png_level=6,
+                          return_results=False,
+                          point_clouds=("output_depth",),
+                          point_cloud_depth_range=None):
+    """run_with_format (its arguments, name for name; everything is documented there) that also writes metric point clouds
+    (DESIGN 8y): per frame checkpoint_path/outputs/point_cloud/<name>.ply for "output_depth" and
+    checkpoint_path/outputs/sparse_point_cloud/<name>.ply for "sparse_depth" in `point_clouds`, <name> being the PNG's with the
+    extension replaced -- binary little-endian PLY files (loader.ply_header, loader.load_point_cloud) of the pixels whose depth is
+    finite, above 0 and inside the closed point_cloud_depth_range (None: no further bound), in row-major order, in the camera frame
+    and in metres, coloured with the image file's pixels.  The points are K^-1 [x y 1]^T z of the fp32 output depth and of the
+    FILTERED sparse depth under the batch's intrinsics, made on the device (ops.point_cloud) and written by loader.PointCloudWriter
+    while the run proceeds, whether or not save_outputs is set.  An unknown cloud name, a repeated one or an empty selection raises
+    KbnError before anything touches the disk or the device.  Everything else -- results.txt, the four directories, the returned
+    dict -- is run_with_format's, byte for byte."""
+    point_clouds = loader.point_cloud_names(point_clouds)      # None is no selection here; _run reads it as "no point clouds"
+    return _run(**locals())
+
+
+def _run(*, image_path, sparse_depth_path, intrinsics_path, ground_truth_path, input_channels_image, input_channels_depth, normalized_image_range,
+         outlier_removal_kernel_size, outlier_removal_threshold, min_pool_sizes_sparse_to_dense_pool, max_pool_sizes_sparse_to_dense_pool,
+         n_convolution_sparse_to_dense_pool, n_filter_sparse_to_dense_pool, n_filters_encoder_image, n_filters_encoder_depth,
+         resolutions_backprojection, n_filters_decoder, deconv_type, min_predict_depth, max_predict_depth, weight_initializer, activation_func,
+         min_evaluate_depth, max_evaluate_depth, checkpoint_path, depth_model_restore_path, save_outputs, keep_input_filenames, device,
+         output_format, batch_size, workers, png_level, return_results, point_clouds, point_cloud_depth_range):
+    """The run behind run, run_with_format and run_with_point_clouds: every argument of theirs, by name, no defaults.  point_clouds
+    None: no point clouds."""
     if output_format not in loader.OUTPUT_FORMATS:
         raise KbnError(f"run: output_format {output_format!r}: expected one of {', '.join(repr(f) for f in loader.OUTPUT_FORMATS)}")
+    if point_clouds is not None:
+        point_clouds = loader.point_cloud_names(point_clouds)
+        if point_cloud_depth_range is not None and not float(point_cloud_depth_range[0]) <= float(point_cloud_depth_range[1]):
+            raise KbnError(f"run: point_cloud_depth_range {point_cloud_depth_range!r}: expected (min, max) with min <= max, or None")
     if device == "cuda" or device == "gpu":
         device = torch.device("cuda")
     else:
@@ -274,6 +349,10 @@ def run_with_format(image_path,
     if save_outputs:
         writer = loader.OutputWriter(output_path, threads=workers, level=png_level, normalized_image_range=normalized_image_range,
                                      file_format=output_format)
+    clouds = None
+    if point_clouds is not None:
+        clouds = loader.PointCloudWriter(output_path, clouds=point_clouds, threads=workers, normalized_image_range=normalized_image_range,
+                                         depth_range=point_cloud_depth_range)
     rows, timers, kept = [], [], None
     seen = 0
     try:
@@ -300,12 +379,15 @@ def run_with_format(image_path,
                     # the validity map of a ground truth is depth > 0 (data_utils.load_depth_with_validity_map), which is what the
                     # kernel asks of its validity plane: the depth serves as both
                     rows.append(ops.eval_metrics(output_depth, ground_truth, ground_truth, min_evaluate_depth, max_evaluate_depth))
-                if writer is not None:
+                if writer is not None or clouds is not None:
                     if keep_input_filenames:
                         filenames = [os.path.basename(loader.sample_name(image_paths[seen + i])) for i in range(n)]
                     else:
                         filenames = ["{:010d}.png".format(seen + i) for i in range(n)]
+                if writer is not None:
                     writer.submit(filenames, image, output_depth, filtered_sparse_depth, ground_truth_samples=samples)
+                if clouds is not None:
+                    clouds.submit(filenames, image, output_depth, filtered_sparse_depth, intrinsics)
                 if return_results:
                     if kept is None:
                         kept = torch.empty((n_sample,) + tuple(output_depth.shape[1:]), dtype=torch.float32).pin_memory()
@@ -330,7 +412,7 @@ def run_with_format(image_path,
         if save_outputs:
             log("Saving outputs to {}".format(output_path), log_path)
     except BaseException:
-        for closing in (writer, truths):
+        for closing in (writer, clouds, truths):
             if closing is not None:
                 try:
                     closing.close()
@@ -341,6 +423,8 @@ def run_with_format(image_path,
         truths.close()
     if writer is not None:
         writer.close()
+    if clouds is not None:
+        clouds.close()
     if not return_results:
         return None
     torch.cuda.current_stream(device).synchronize()      # the copies into `kept`

@@ -44,6 +44,10 @@ The output side (`run_kbnet.py --save_outputs`, reference src/kbnet.py:986-1026)
 and `OutputWriter` for the whole export of a run -- `ops.export_pack` makes the pixels of a batch's files in one launch, a side
 stream copies them to pinned slots, host threads encode and write while the next batch runs (kb.inference.run drives it).
 `read_paths`, `write_paths` and `load_depth_with_validity_map` are the reference's data_utils functions of those names.
+
+Point clouds: `PointCloudWriter` takes the same road for the depth maps backprojected to metric 3-D points --
+`ops.point_cloud` writes the vertex records of binary PLY files on the device, the side stream copies them, host threads only write;
+`ply_header` and `load_point_cloud` are the format and its strict reader.
 """
 
 from __future__ import annotations
@@ -829,6 +833,176 @@ class OutputWriter:
             except Exception:      # noqa: BLE001
                 pass
         return False
+
+
+# ------------------------------------------------------------------------- point clouds
+POINT_CLOUD_EXTENSION = ".ply"
+POINT_CLOUDS = ("output_depth", "sparse_depth")      # what PointCloudWriter and inference.run_with_point_clouds can backproject
+POINT_CLOUD_DIRECTORIES = {"output_depth": "point_cloud", "sparse_depth": "sparse_point_cloud"}
+_PLY_RECORD = {True: np.dtype([("xyz", "<f4", (3,)), ("rgb", "u1", (3,))]), False: np.dtype([("xyz", "<f4", (3,))])}      # packed: 15 and 12 bytes
+
+
+def point_cloud_filename(filename: str) -> str:
+    """The name PointCloudWriter gives the cloud of the frame whose PNG is `filename`: its extension replaced."""
+    return os.path.splitext(filename)[0] + POINT_CLOUD_EXTENSION
+
+
+def point_cloud_names(clouds) -> Tuple[str, ...]:
+    """`clouds` as a tuple, once it is known to be a non-empty subset of POINT_CLOUDS without repeats; KbnError otherwise."""
+    names = (clouds,) if isinstance(clouds, str) else tuple(clouds) if isinstance(clouds, (tuple, list)) else ()
+    if not names or len(set(names)) != len(names) or any(name not in POINT_CLOUDS for name in names):
+        raise KbnError(f"point clouds {clouds!r}: expected a non-empty selection of {', '.join(repr(c) for c in POINT_CLOUDS)}")
+    return names
+
+
+def ply_header(points: int, colour: bool) -> bytes:
+    """The header of the binary PLY files PointCloudWriter writes: fixed ASCII text, `points` vertices of float x, y, z and, with
+    `colour`, uchar red, green, blue.  The body is points x (15 or 12) bytes, packed, little-endian."""
+    points = int(points)
+    if points < 0:
+        raise KbnError(f"ply_header: {points} points")
+    lines = ["ply", "format binary_little_endian 1.0", "comment kbnet_amd point cloud: camera frame, metres", f"element vertex {points}",
+             "property float x", "property float y", "property float z"]
+    if colour:
+        lines += ["property uchar red", "property uchar green", "property uchar blue"]
+    return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
+
+
+def load_point_cloud(path: str):
+    """A file PointCloudWriter wrote -> (xyz float32 M x 3, rgb uint8 M x 3 or None).  A strict reader of exactly those files: another
+    header (any other PLY included), a truncated body or trailing bytes raise KbnError."""
+    data = _read(path)
+    end = data.find(b"end_header\n")
+    lines = data[:end].split(b"\n") if end >= 0 else []
+    count = lines[3][len(b"element vertex "):] if len(lines) > 3 and lines[3].startswith(b"element vertex ") else b""
+    if not count.isdigit() or len(count) > 18:
+        raise KbnError(f"load_point_cloud: {path} does not start with the header ply_header writes")
+    points = int(count)
+    for colour in (True, False):
+        header = ply_header(points, colour)
+        if data.startswith(header):
+            break
+    else:
+        raise KbnError(f"load_point_cloud: {path} does not start with the header ply_header writes")
+    record = _PLY_RECORD[colour]
+    body = len(data) - len(header)
+    if body != points * record.itemsize:
+        raise KbnError(f"load_point_cloud: {path} states {points} points of {record.itemsize} bytes, its body holds {body} bytes")
+    vertices = np.frombuffer(data, dtype=record, count=points, offset=len(header))
+    return np.ascontiguousarray(vertices["xyz"]), (np.ascontiguousarray(vertices["rgb"]) if colour else None)
+
+
+class PointCloudWriter:
+    """Metric point clouds of a run, written WHILE it proceeds: per frame and requested cloud a binary little-endian PLY file (ply_header;
+    load_point_cloud reads it back) of the pixels whose depth is finite, above 0 and inside `depth_range`, in row-major pixel order,
+    in the camera frame, in metres, coloured with the image file's pixels.  `clouds` is a non-empty selection of "output_depth" (the
+    network's depth: output_path/point_cloud/<name>.ply) and "sparse_depth" (the points that went in:
+    output_path/sparse_point_cloud/<name>.ply); their directories are made on construction.  depth_range: (min, max), closed; None
+    keeps every finite depth above 0.
+
+    submit() costs the caller two or three launches of three kernels and no wait for the device:
+      1. ONE ops.intrinsics_inverse call and ONE ops.point_cloud call per requested cloud, on torch's current stream, write the
+         files' vertex records into a device buffer of the writer's own, and their numbers;
+      2. an event is recorded there; the writer's side stream waits for it and copies every frame's SLOT and the counts into one of
+         `in_flight` pinned host slots.  Only the device knows how many points a frame keeps, so the bound is copied, as in
+         OutputWriter's packed path: 15 bytes a pixel and cloud, against the 7 of the PNG path, whatever the density;
+      3. `threads` (at most 16) host threads wait for the slot's copy, then write the header and count x 15 bytes under a temporary
+         name and move the file into place.
+    Slot reuse, back-pressure, error delivery, close() and the context manager are OutputWriter's, and so is the guarantee: what was
+    handed to submit() may be freed or overwritten as soon as it returns.  One writer is driven by one thread."""
+
+    RECORD = 15
+
+    def __init__(self, output_path: str, clouds=("output_depth",), threads: int = 8, in_flight: int = 2, normalized_image_range=(0, 1),
+                 depth_range=None):
+        self.clouds = point_cloud_names(clouds)
+        self.scale, self.shift = image_export_affine(normalized_image_range)
+        self.min_depth, self.max_depth = (0.0, float("inf")) if depth_range is None else (float(v) for v in depth_range)
+        if not self.min_depth <= self.max_depth:
+            raise KbnError(f"PointCloudWriter: depth_range {depth_range!r}: expected (min, max) with min <= max, or None")
+        self.output_path = output_path
+        self.dirpaths = {name: os.path.join(output_path, POINT_CLOUD_DIRECTORIES[name]) for name in self.clouds}
+        for dirpath in self.dirpaths.values():
+            os.makedirs(dirpath, exist_ok=True)
+        self.threads = max(1, min(16, int(threads)))
+        self.pool = ThreadPoolExecutor(max_workers=self.threads)
+        self._slots = [{"key": None, "files": []} for _ in range(max(1, int(in_flight)))]
+        self._serial = 0
+        self._error: Optional[BaseException] = None
+        self._copy_stream = None
+        self._closed = False
+
+    # OutputWriter's helpers, shared: a slot's finished files and their first error, a file placed under a temporary name, the end
+    _drain = OutputWriter._drain
+    _place = staticmethod(OutputWriter._place)
+    close = OutputWriter.close
+    __enter__ = OutputWriter.__enter__
+    __exit__ = OutputWriter.__exit__
+
+    # -- a slot: len(clouds) x capacity file slots of `stride` bytes and as many counts, on the device and pinned --
+    def _slot(self, device, n: int, h: int, w: int) -> dict:
+        slot = self._slots[self._serial % len(self._slots)]
+        self._serial += 1
+        self._drain(slot)
+        if slot["key"] is None or slot["key"][0] != device or slot["key"][2:] != (h, w) or slot["key"][1] < n:
+            stride = _align16(ops.point_cloud_stride(h, w, True))
+            rows = len(self.clouds) * n
+            slot.update(key=(device, n, h, w), stride=stride,
+                        device=torch.empty((rows, stride), dtype=torch.uint8, device=device),
+                        counts=torch.empty(rows, dtype=torch.int64, device=device),
+                        workspace=torch.empty(ops.point_cloud_workspace_bytes(n, h, w), dtype=torch.uint8, device=device),
+                        host=torch.empty((rows, stride), dtype=torch.uint8).pin_memory(),
+                        host_counts=torch.empty(rows, dtype=torch.int64).pin_memory())
+            for name in ("device", "counts"):
+                slot[name].record_stream(self._copy_stream)      # the allocator learns that the side stream reads them
+        return slot
+
+    def submit(self, filenames: Sequence[str], image, output_depth, sparse_depth, intrinsics) -> None:
+        """One batch: image N x 3 x H x W as ops.preprocess normalised it, output_depth and sparse_depth N x 1 x H x W, intrinsics
+        N x 3 x 3 (device, fp32); filenames: N base names, whose extension is replaced by POINT_CLOUD_EXTENSION.  A depth that is
+        not among the writer's clouds may be None."""
+        if self._closed:
+            raise KbnError("PointCloudWriter: submit() after close()")
+        depths = {"output_depth": output_depth, "sparse_depth": sparse_depth}
+        for name, t in [("image", image), ("intrinsics", intrinsics)] + [(name, depths[name]) for name in self.clouds]:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise KbnError(f"PointCloudWriter: {name}: expected a CUDA/HIP tensor (the HIP path has no CPU fallback)")
+        n, h, w = int(image.shape[0]), int(image.shape[-2]), int(image.shape[-1])
+        if len(filenames) != n:
+            raise KbnError(f"PointCloudWriter: {n} frames, {len(filenames)} file names")
+        device = image.device
+        with torch.cuda.device(device):
+            if self._copy_stream is None or self._copy_stream.device != device:
+                self._copy_stream = torch.cuda.Stream(device=device)
+            slot = self._slot(device, n, h, w)
+            capacity = slot["key"][1]
+            rows = [slice(c * capacity, c * capacity + n) for c in range(len(self.clouds))]      # of cloud c, in every buffer
+            kinv = ops.intrinsics_inverse(intrinsics)
+            for name, r in zip(self.clouds, rows):
+                ops.point_cloud(depths[name], kinv, image, min_depth=self.min_depth, max_depth=self.max_depth, scale=self.scale,
+                                shift=self.shift, out=slot["device"][r], out_points=slot["counts"][r], workspace=slot["workspace"])
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(device))
+            self._copy_stream.wait_event(ready)
+            with torch.cuda.stream(self._copy_stream):
+                for r in rows:
+                    slot["host"][r].copy_(slot["device"][r], non_blocking=True)
+                    slot["host_counts"][r].copy_(slot["counts"][r], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+        files, counts = slot["host"].numpy(), slot["host_counts"].numpy()
+        jobs = []
+        for i, filename in enumerate(filenames):
+            for name, r in zip(self.clouds, rows):
+                jobs.append((done, files[r.start + i], counts, r.start + i, h * w, os.path.join(self.dirpaths[name], point_cloud_filename(filename))))
+        slot["files"] = [self.pool.submit(self._write, *job) for job in jobs]
+
+    def _write(self, done, file_slot: np.ndarray, counts: np.ndarray, index: int, pixels: int, path: str) -> None:
+        done.synchronize()      # the slot's copies have landed: the records and their number
+        points = int(counts[index])
+        if not 0 <= points <= pixels:
+            raise KbnError(f"PointCloudWriter: the device reports {points} points for {path}, the frame has {pixels} pixels")
+        self._place(b"".join((ply_header(points, True), memoryview(file_slot[:points * self.RECORD]))), path)
 
 
 # ------------------------------------------------------------------- batched device loader

@@ -1445,6 +1445,101 @@ def pack_frames(samples, bits=None, out=None, out_bytes=None, workspace=None):
     return out, out_bytes
 
 
+POINT_RECORD_BYTES = {False: 12, True: 15}      # a PLY vertex: float x, y, z, and with colour uchar r, g, b; packed
+
+
+def point_cloud_stride(height: int, width: int, colour: bool) -> int:
+    """Bytes of one frame's slot in point_cloud's `out`: a record for every pixel (12 bytes, 15 with colour)."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1 or height * width > 0x7fffffff:
+        raise KbnError(f"point_cloud: {height} x {width} pixels (sizes >= 1, at most 2^31 - 1 pixels a frame)")
+    return height * width * POINT_RECORD_BYTES[bool(colour)]
+
+
+def point_cloud_workspace_bytes(n: int, height: int, width: int) -> int:
+    """Device bytes point_cloud needs as `workspace` for n such frames (kbn_point_cloud_workspace_bytes)."""
+    need = int(_lib.load().kbn_point_cloud_workspace_bytes(int(n), int(height), int(width)))
+    if need == 0:      # a refusal, not "no workspace"
+        raise KbnError(f"point_cloud: no workspace for {n} frames of {height} x {width}")
+    return need
+
+
+@_on_tensor_device
+def point_cloud(depth, intrinsics_inverse, image=None, *, min_depth: float = 0.0, max_depth: float = float("inf"), scale: float = 255.0,
+                shift: float = 0.0, out=None, out_points=None, workspace=None):
+    """A batch of depth maps backprojected to the vertex records of binary PLY files ON THE DEVICE (kbn_point_cloud_forward,
+    csrc/point_cloud.hip) -> (records, points): records[i, :points[i] * record] holds frame i's kept pixels in row-major
+    order as packed little-endian `float x, y, z` (12 bytes), followed by `uchar r, g, b` when an image is given (15 bytes).
+      depth               N x 1 x H x W fp32 with dense planes (a channel slice of a wider tensor is welcome), or N x H x W
+      intrinsics_inverse  N x 3 x 3 fp32: ops.intrinsics_inverse(K).  A point is ops.camera_coordinates' value times the depth,
+                          one fp32 product a component
+      image               None, or N x 3 x H x W fp32: the normalised image; the colour bytes are export_pack's under `scale` and
+                          `shift` (loader.image_export_affine), i.e. the image file's pixels
+      min_depth, max_depth  the closed range of kept depths; NaN, +-Inf, zero and negatives are never kept
+      out        N x stride uint8 with dense rows, stride >= point_cloud_stride(H, W, image is not None); a view of a larger buffer
+                 is welcome.  Bytes past points[i] * record keep what they held.
+      out_points N int64 on the device: the counts are known to the device alone, no host synchronisation here
+      workspace  a dense uint8 device tensor of at least point_cloud_workspace_bytes(N, H, W) bytes; allocated when None
+    Three launches, whatever N is.  CPU tensors raise KbnError (no CPU fallback), so do shapes and dtypes that disagree, naming the
+    offender."""
+    fn = "point_cloud"
+    _require(depth, f"{fn}: depth")
+    d = depth.detach()
+    if d.dim() == 3:
+        d = d.unsqueeze(1)
+    if d.dim() != 4 or d.shape[1] != 1:
+        raise KbnError(f"{fn}: depth has shape {tuple(depth.shape)}, expected N x 1 x H x W or N x H x W")
+    n, h, w = int(d.shape[0]), int(d.shape[2]), int(d.shape[3])
+    if n < 1 or h < 1 or w < 1:
+        raise KbnError(f"{fn}: depth is empty: {tuple(depth.shape)}")
+    if d.stride(3) != 1 or d.stride(2) != w or (n > 1 and d.stride(0) < h * w):
+        d = d.contiguous()
+    device = d.device
+    _require(intrinsics_inverse, f"{fn}: intrinsics_inverse")
+    if tuple(intrinsics_inverse.shape) != (n, 3, 3):
+        raise KbnError(f"{fn}: intrinsics_inverse has shape {tuple(intrinsics_inverse.shape)}, expected {(n, 3, 3)}")
+    kinv = intrinsics_inverse.detach().contiguous()
+    colour = image is not None
+    if colour:
+        _require(image, f"{fn}: image")
+        if tuple(image.shape) != (n, 3, h, w):
+            raise KbnError(f"{fn}: image has shape {tuple(image.shape)}, expected {(n, 3, h, w)} like depth")
+        image = image.detach().contiguous()
+    record = POINT_RECORD_BYTES[colour]
+    stride = point_cloud_stride(h, w, colour)
+    if out is None:
+        out = torch.empty((n, stride), device=device, dtype=torch.uint8)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != device:
+            raise KbnError(f"{fn}: out: expected a tensor on {device} (the HIP path has no CPU fallback)")
+        if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1:
+            raise KbnError(f"{fn}: out is {out.dtype} {tuple(out.shape)}, expected uint8 {n} x stride with dense rows")
+        if out.shape[1] < stride or (n > 1 and out.stride(0) < out.shape[1]):
+            raise KbnError(f"{fn}: out is {tuple(out.shape)} with rows {out.stride(0)} bytes apart: a slot is at least {stride} bytes")
+    out_stride = int(out.stride(0)) if n > 1 else int(out.shape[1])
+    if out_points is None:
+        out_points = torch.empty((n,), device=device, dtype=torch.int64)
+    elif (not isinstance(out_points, torch.Tensor) or not out_points.is_cuda or out_points.device != device or out_points.dtype != torch.int64
+          or tuple(out_points.shape) != (n,) or not out_points.is_contiguous()):
+        raise KbnError(f"{fn}: out_points: expected a contiguous int64 tensor of {n} on {device}")
+    need = point_cloud_workspace_bytes(n, h, w)
+    if workspace is None:
+        workspace = torch.empty((need,), device=device, dtype=torch.uint8)
+    elif (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != device or workspace.dtype != torch.uint8
+          or not workspace.is_contiguous() or workspace.numel() < need):
+        raise KbnError(f"{fn}: workspace: expected a dense uint8 tensor of at least {need} bytes on {device}")
+    lib = _lib.load()
+    batch_stride = int(d.stride(0)) if n > 1 else h * w
+    # algorithmic bytes: the depth read twice (count, emit), the image once, a record written per pixel at most
+    check(_launch("point_cloud", 0.0,
+                  lambda: lib.kbn_point_cloud_forward(d.data_ptr(), batch_stride, image.data_ptr() if colour else None, float(scale),
+                                                      float(shift), kinv.data_ptr(), float(min_depth), float(max_depth), n, h, w,
+                                                      out.data_ptr(), out_stride, out_points.data_ptr(), workspace.data_ptr(),
+                                                      workspace.numel(), _stream()),
+                  nbytes=float(n * h * w) * (8 + (12 if colour else 0) + record)), "kbn_point_cloud_forward")
+    return out, out_points
+
+
 _TRAIN_FRAME_RECORD = struct.Struct("@2q4i")     # _lib.TrainFrame's layout: two byte offsets, raw height, raw width, y_start, x_start
 _PACKED_FRAME_RECORD = struct.Struct("@2q2I4i")     # _lib.PackedFrame's layout: two byte offsets, two file sizes, raw height, raw width, y_start, x_start
 _SEQUENCE_FRAME_RECORD = struct.Struct("@4q4i")     # _lib.SequenceFrame's layout: three image offsets, the depth offset, height, width, y_start, x_start

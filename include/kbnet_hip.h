@@ -1268,6 +1268,37 @@ int kbn_pack_frames_forward(const void* samples, int n, int width, int height, i
                             size_t out_stride, unsigned long long* out_bytes, void* workspace, size_t workspace_bytes,
                             kbn_stream_t stream);
 
+/* Point clouds (csrc/point_cloud.hip): n depth maps of height x width backprojected to the vertex records of binary
+ * little-endian PLY files, on the device.  Frame i's slot, out + i * out_stride, receives one packed record per KEPT pixel in
+ * row-major pixel order -- float x, y, z, then uchar r, g, b when `image` is given: 15 bytes a record, 12 without, no padding --
+ * and out_points[i] their number.
+ *   depth       n x 1 x height x width float32, dense planes, frame i at depth + i * depth_batch_stride (elements): a channel slice
+ *               of a wider tensor works; 4-byte aligned (16-byte loads where an address allows them)
+ *   image       NULL, or n x 3 x height x width float32, contiguous: the NORMALISED image; a byte is kbn_export_pack_forward's rgb
+ *               rule under the same scale and shift, so the colours are the image file's pixels
+ *   kinv        n x 3 x 3 float32: what kbn_intrinsics_inverse(K, 1, 1) wrote
+ *   kept        a pixel is kept iff its depth d is finite, d > 0, d >= min_depth and d <= max_depth: NaN, +-Inf, zero and negatives
+ *               never are (0 and +Inf as the range keep every finite depth above 0)
+ *   point       component j is c_j * d, ONE product rounded to fp32, where c_j is bit for bit what kbn_camera_coordinates stores
+ *               for the pixel: fmaf(k[3j+1], (float)y, k[3j] * (float)x) + k[3j+2] with integer pixel coordinates
+ *               (csrc/camera_coordinate.h states it for both)
+ *   out         any alignment; out_stride >= height * width * record bytes.  Nothing outside [0, out_points[i] * record) of a slot
+ *               is written, nothing outside the slots either.  out_points: 8-byte aligned int64, written by the device.
+ *   workspace   workspace_bytes >= kbn_point_cloud_workspace_bytes(n, height, width) device bytes (4 a tile of 1024 pixels), 4-byte
+ *               aligned; nothing past that size is touched; no allocation in here
+ * Three launches whatever n is (count, scan, emit), no atomics, no host synchronisation: the bytes are a function of the arguments.
+ * Before anything is launched -- KBN_ERR_INVALID_ARGUMENT: a NULL pointer (a NULL image alone is legal), n, height or width < 1, a
+ * misaligned pointer, a short out_stride; KBN_ERR_WORKSPACE: a short workspace; KBN_ERR_UNSUPPORTED: height * width > 2^31 - 1 or
+ * n x ceil(height * width / 1024) > 2^31 - 1 (the grid's first dimension). */
+/* range: n, height, width >= 1 and the two products above; 0 otherwise.  Swept over extreme arguments under the sanitizers by a
+ * program of its own, tests/host_san/point_cloud_size_sweep.cpp (tests/test_point_cloud_sanitizers_cpu.py), not by
+ * tests/host_san/size_sweep.cpp, whose driver links a fixed list of sources and finds its functions by lines that begin
+ * with the return type: hence the comment in front of this one. */
+/* own sweep */ size_t kbn_point_cloud_workspace_bytes(int n, int height, int width);
+int kbn_point_cloud_forward(const float* depth, long long depth_batch_stride, const float* image, float scale, float shift,
+                            const float* kinv, float min_depth, float max_depth, int n, int height, int width, unsigned char* out,
+                            size_t out_stride, long long* out_points, void* workspace, size_t workspace_bytes, kbn_stream_t stream);
+
 /* TensorBoard's default histogram of an fp32 device tensor -- what SummaryWriter.add_histogram(bins='tensorflow') computes on the
  * host, np.histogram(values.astype(float), bins=edges) with min, max, sum and values.dot(values) -- in one pass (csrc/histogram.hip).
  *   x               n float32, dense, 4-byte aligned (16-byte loads from the first 16-byte boundary on)
